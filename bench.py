@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: CTR samples/s, forward+backward, batch 65536 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload neuralcf]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload neuralcf] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step is one Trainer.train_loop body without the optimizer (reference
@@ -10,10 +10,16 @@ synthetic ml-100k-shaped ids already resident in HBM.  With N > 1 every rank
 runs its own batch of 65536 (weak scaling) and the replicated parameters'
 gradients are averaged with one RCCL all-reduce inside the step.
 
-Prints ONE JSON line (rank 0) with the contract keys plus
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0)
+with the contract keys (ms_per_step = wall time of one timed step).  --full adds
+  full_step     the same step + Adam.step(), timed
   roofline      dominant kernel of the step (by measured time), HIP events on the launch stream
-  cpu_baseline  the CPU oracle (oracle/ctr_oracle.py) timed on this box's host cores
   kernels       per-kernel breakdown of one step; gather_roofline = the embedding-stage kernel
+  torch_gpu_baseline / cpu_baseline  the oracle (oracle/ctr_oracle.py) on the same GPU / on the host cores
+
+--dump-outputs DIR writes what the last timed step computed (prob, loss and every
+parameter gradient) as DIR/<name>.npy, float32: inputs and weights are seeded, so
+two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -457,14 +463,57 @@ def roofline_entry(label, rec, traffic=None):
             "algorithmic_bytes": rec["bytes"]}
 
 
+DUMP_BYTES = 63 << 20  # --dump-outputs writes at most 64 MB: the arrays' share, the rest is room for the .npy headers
+
+
+def step_outputs(model, prob, loss):
+    """what a caller of the step receives: the probabilities, the loss and every parameter's gradient (the
+    pending-row buffer of a sparse-mode table)"""
+    from deeplearningrecommendationsystem_amd import sparse
+    out = {"prob": prob, "loss": loss}
+    for name, p in model.named_parameters():
+        g = p.grad
+        if g is None and sparse.state_of(p) is not None:
+            g = sparse.state_of(p).grad
+        if g is not None:
+            out["grad." + name] = g
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """write every array as <dirname>/<name>.npy (float32; float64 stays float64).  The DUMP_BYTES budget is shared
+    out from the smallest array up: an array larger than its share is written as that many of its elements
+    (flattened), at positions drawn by a generator seeded from its name -- the same positions in every run"""
+    import zlib
+
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    for n, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        share = left // (len(items) - n) // t.element_size()
+        if t.numel() > share:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (share,), generator=gen).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        left -= t.numel() * t.element_size()
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="neuralcf")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gather-leg", action="store_true", help="skip metric (ii): the cfg3b embedding-stage timing")
+    ap.add_argument("--full", action="store_true", help="after the headline: the optimizer step, the per-kernel "
+                    "breakdown and rooflines, the cfg3b gather leg and the oracle baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle baselines")
+    ap.add_argument("--no-gather-leg", action="store_true", help="with --full: skip metric (ii), the cfg3b "
+                    "embedding-stage timing")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every launch from Python instead of replaying a hipGraph")
     ap.add_argument("--sparse", action="store_true", help="opt-in sparse mode of the big tables' gradients (SURVEY 8f-3): "
                     "no dense zero-fill in backward, row-wise lazy Adam in full_step; NOT the reference's dense semantics")
@@ -477,6 +526,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                     "the multi-rank path with several ranks sharing one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -521,6 +572,8 @@ def main():
     bucket = GradBucket(model.parameters()) if world > 1 else None
     model.train()
 
+    last = {}  # the probabilities of the latest step, for --dump-outputs
+
     def eager_step():
         model.zero_grad(set_to_none=True)
         # --fresh-ids: a data loader hands over NEW tensors every step -> no exchange plan can be reused
@@ -530,6 +583,7 @@ def main():
         loss.backward()
         if bucket is not None:
             bucket.all_reduce_mean()
+        last["prob"] = prob
         return loss
 
     step = eager_step
@@ -537,6 +591,7 @@ def main():
         # the same fwd + loss + bwd launches, captured once and replayed as one hipGraph
         from deeplearningrecommendationsystem_amd.graph import GraphedStep
         graphed = GraphedStep(model, loss_fn, inputs, y)
+        last["prob"] = graphed.prob
 
         def step():
             loss = graphed()
@@ -564,82 +619,90 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * per_rank * args.steps / elapsed
 
-    # the whole train_loop body: the same step + optimizer.step() (Adam lr 1e-3, weight_decay 1e-5 as
-    # the scripts).  Reported next to the headline, not part of `value`.
-    full_ms = None
-    if world == 1:
-        opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
-        for _ in range(3):
-            step()
-            opt.step()
-        barrier()
-        t1 = time.perf_counter()
-        nfull = max(3, args.steps // 3)
-        for _ in range(nfull):
-            step()
-            opt.step()
-        barrier()
-        full_ms = (time.perf_counter() - t1) / nfull * 1e3
+    last_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(model, last["prob"], loss))
+    out = {
+        "metric": "embedding-stage samples/sec (26-field gather fwd + scatter bwd) at batch 65536"
+                  if args.workload.startswith("gather26") else
+                  f"CTR samples/sec fwd+bwd at global batch {world * per_rank}" if args.shard else
+                  "CTR samples/sec fwd+bwd at batch 65536" if batch_of(args.workload) == BATCH else
+                  f"CTR samples/sec fwd+bwd at batch {batch_of(args.workload)}",
+        "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if args.shard else "weak",
+        "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": desc, "global_batch": world * per_rank,
+                   "parallelism": (f"dp{world}+rowshard{world}" if args.shard else f"dp{world}") if world > 1 or args.shard
+                   else "single"},
+        "loss": last_loss, "launch": "eager" if args.no_graph else "hipGraph replay",
+        **({"exchange": {"layout": f"capacity-bounded x{args.capacity}" if args.capacity else "exact",
+                         "fresh_id_tensors_every_step": bool(args.fresh_ids)}} if args.shard else {}),
+    }
 
-    # per-kernel durations: the same steps again with a HIP event pair around every launch
-    prof = ops.KernelProfiler(spacer_us=60.0)  # GPU kept busy ahead of each bracketed launch: no host gap in the pair
-    ops.set_profiler(prof)
-    for _ in range(args.steps):
-        eager_step()
-    ops.set_profiler(None)
-    kernels = prof.summary()
-    if world > 1:
-        dist.barrier()
+    if args.full:
+        # the whole train_loop body: the same step + optimizer.step() (Adam lr 1e-3, weight_decay 1e-5 as
+        # the scripts).  Reported next to the headline, not part of `value`.
+        full_ms = None
+        if world == 1:
+            opt = Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
+            for _ in range(3):
+                step()
+                opt.step()
+            barrier()
+            t1 = time.perf_counter()
+            nfull = max(3, args.steps // 3)
+            for _ in range(nfull):
+                step()
+                opt.step()
+            barrier()
+            full_ms = (time.perf_counter() - t1) / nfull * 1e3
 
-    gather_leg = None
-    if rank == 0 and world == 1 and not args.no_gather_leg and not args.shard:
-        gather_leg = gather_stage_leg(device)
+        # per-kernel durations: the same steps again with a HIP event pair around every launch
+        prof = ops.KernelProfiler(spacer_us=60.0)  # GPU kept busy ahead of each bracketed launch: no host gap in the pair
+        ops.set_profiler(prof)
+        for _ in range(args.steps):
+            eager_step()
+        ops.set_profiler(None)
+        kernels = prof.summary()
+        if world > 1:
+            dist.barrier()
+
+        gather_leg = None
+        if rank == 0 and world == 1 and not args.no_gather_leg and not args.shard:
+            gather_leg = gather_stage_leg(device)
+        if rank == 0:
+            entries = {k: roofline_entry(k, v, pmc_traffic(args.workload, k)) for k, v in kernels.items()}
+            dominant = max(kernels, key=lambda k: kernels[k]["total_us"])
+            kernel_us = sum(v["total_us"] for v in kernels.values()) / args.steps
+            out.update({
+                "roofline": dict(entries[dominant], note=LABEL_NOTES.get(dominant) or entries[dominant].get("note"),
+                                 kernel_alone_rocprofv3=rocprof_kernel(args.workload, dominant, kernels[dominant]["flops"],
+                                                                       kernels[dominant]["bytes"])),
+                # metric (ii) is defined on the HBM-resident cfg3b shape (gather_stage_leg); the step's own embedding
+                # kernel is reported under its own key -- for NeuralCF / ml-100k vocabularies its tables are cache-resident
+                "gather_roofline": gather_leg,
+                "step_embed_fwd": None if "embed_fwd" not in entries else
+                dict(entries["embed_fwd"],
+                     note="the timed step's embedding-stage launch; ml-100k-sized tables sit in L2 (cache-resident, "
+                          "not an HBM figure)" if args.workload in ("neuralcf", "mf", "pnn", "ffm", "deepcrossing") else None),
+                "kernels": {k: {"avg_us": round(v["avg_us"], 2), "calls_per_step": v["calls"] / args.steps,
+                                "bound": entries[k]["bound"], "frac": round(entries[k]["frac"], 4),
+                                **({"shapes": v["shapes"]} if v["shapes"] > 1 else {})}
+                            for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["total_us"])},
+                "gpu_kernel_us_per_step": round(kernel_us, 1),
+                "full_step": None if full_ms is None else {
+                    "ms_per_step": full_ms, "samples_per_s": per_rank / full_ms * 1e3,
+                    "what": "zero_grad + forward + BCELoss + backward + Adam(lr=1e-3, weight_decay=1e-5).step()" +
+                            (" -- row-wise (lazy) on the sparse-mode tables" if args.sparse else "")},
+            })
+            if world == 1 and not args.no_cpu_baseline and not args.shard and not args.workload.startswith("gather26"):
+                try:
+                    out["torch_gpu_baseline"] = torch_gpu_baseline(args.workload, model, device)
+                except Exception as exc:  # the oracle is CPU test infrastructure first: report, do not fail the bench
+                    out["torch_gpu_baseline"] = {"error": repr(exc)[:200]}
+                out["cpu_baseline"] = cpu_baseline(args.workload, model)
     if rank == 0:
-        entries = {k: roofline_entry(k, v, pmc_traffic(args.workload, k)) for k, v in kernels.items()}
-        dominant = max(kernels, key=lambda k: kernels[k]["total_us"])
-        kernel_us = sum(v["total_us"] for v in kernels.values()) / args.steps
-        out = {
-            "metric": "embedding-stage samples/sec (26-field gather fwd + scatter bwd) at batch 65536"
-                      if args.workload.startswith("gather26") else
-                      f"CTR samples/sec fwd+bwd at global batch {world * per_rank}" if args.shard else
-                      "CTR samples/sec fwd+bwd at batch 65536" if batch_of(args.workload) == BATCH else
-                      f"CTR samples/sec fwd+bwd at batch {batch_of(args.workload)}",
-            "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if args.shard else "weak",
-            "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": desc, "global_batch": world * per_rank,
-                       "parallelism": (f"dp{world}+rowshard{world}" if args.shard else f"dp{world}") if world > 1 or args.shard
-                       else "single"},
-            "loss": float(loss.item()), "launch": "eager" if args.no_graph else "hipGraph replay",
-            **({"exchange": {"layout": f"capacity-bounded x{args.capacity}" if args.capacity else "exact",
-                             "fresh_id_tensors_every_step": bool(args.fresh_ids)}} if args.shard else {}),
-            "roofline": dict(entries[dominant], note=LABEL_NOTES.get(dominant) or entries[dominant].get("note"),
-                             kernel_alone_rocprofv3=rocprof_kernel(args.workload, dominant, kernels[dominant]["flops"],
-                                                                   kernels[dominant]["bytes"])),
-            # metric (ii) is defined on the HBM-resident cfg3b shape (gather_stage_leg); the step's own embedding
-            # kernel is reported under its own key -- for NeuralCF / ml-100k vocabularies its tables are cache-resident
-            "gather_roofline": gather_leg,
-            "step_embed_fwd": None if "embed_fwd" not in entries else
-            dict(entries["embed_fwd"],
-                 note="the timed step's embedding-stage launch; ml-100k-sized tables sit in L2 (cache-resident, "
-                      "not an HBM figure)" if args.workload in ("neuralcf", "mf", "pnn", "ffm", "deepcrossing") else None),
-            "kernels": {k: {"avg_us": round(v["avg_us"], 2), "calls_per_step": v["calls"] / args.steps,
-                            "bound": entries[k]["bound"], "frac": round(entries[k]["frac"], 4),
-                            **({"shapes": v["shapes"]} if v["shapes"] > 1 else {})}
-                        for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["total_us"])},
-            "gpu_kernel_us_per_step": round(kernel_us, 1),
-            "full_step": None if full_ms is None else {
-                "ms_per_step": full_ms, "samples_per_s": per_rank / full_ms * 1e3,
-                "what": "zero_grad + forward + BCELoss + backward + Adam(lr=1e-3, weight_decay=1e-5).step()" +
-                        (" -- row-wise (lazy) on the sparse-mode tables" if args.sparse else "")},
-        }
-        if world == 1 and not args.no_cpu_baseline and not args.shard and not args.workload.startswith("gather26"):
-            try:
-                out["torch_gpu_baseline"] = torch_gpu_baseline(args.workload, model, device)
-            except Exception as exc:  # the oracle is CPU test infrastructure first: report, do not fail the bench
-                out["torch_gpu_baseline"] = {"error": repr(exc)[:200]}
-            out["cpu_baseline"] = cpu_baseline(args.workload, model)
         print(json.dumps(out))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -1,13 +1,14 @@
 #!/bin/bash
 # dev tool: rocprofv3 kernel stats of eager steps for several workloads
 R=$PWD
+export OUT=${OUT:-$R/out}
 cd /tmp && export TMPDIR=/tmp
 for w in "$@"; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$w -- python3 $R/bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-graph > $R/gpurun_out/prof_$w.json 2>$R/gpurun_out/prof_$w.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$w -- python3 $R/bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-graph > $OUT/prof_$w.json 2>$OUT/prof_$w.err
   python3 - "$w" <<'PY'
 import csv,glob,sys
 w=sys.argv[1]
-import os; f=max(glob.glob(f'/root/repo/gpurun_out/prof_{w}/*/*kernel_stats.csv'), key=os.path.getmtime)
+import os; f=max(glob.glob(f'{os.environ["OUT"]}/prof_{w}/*/*kernel_stats.csv'), key=os.path.getmtime)
 rows=list(csv.DictReader(open(f)))
 tot=sum(float(r['TotalDurationNs']) for r in rows)
 print(f"=== {w}: total kernel time per step {tot/23/1e3:.1f} us (23 steps incl warmup+profile pass)")

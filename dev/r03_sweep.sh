@@ -1,16 +1,17 @@
 #!/bin/bash
 # round-3 sweep: full GPU test suite, then one bench line per workload (no CPU baseline), summary table
-mkdir -p gpurun_out/r03s
+export OUT=${OUT:-out}
+mkdir -p $OUT/r03s
 timeout -k 10 600 echo "(suite: dev/r03_suite.sh)"
 for w in neuralcf neuralcf_script mf deepfm pnn ffm deepcrossing widedeep nfm afm lr gather26 gather26zipf deepfm26 pnn26; do
-  timeout -k 10 300 python bench.py --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-gather-leg > gpurun_out/r03s/bench_$w.json 2>gpurun_out/r03s/bench_$w.err || { echo FAIL $w; tail -5 gpurun_out/r03s/bench_$w.err; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-gather-leg > $OUT/r03s/bench_$w.json 2>$OUT/r03s/bench_$w.err || { echo FAIL $w; tail -5 $OUT/r03s/bench_$w.err; }
 done
 for w in din dien deepcross; do
-  timeout -k 10 300 python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-gather-leg > gpurun_out/r03s/bench_$w.json 2>gpurun_out/r03s/bench_$w.err || { echo FAIL $w; tail -5 gpurun_out/r03s/bench_$w.err; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-gather-leg > $OUT/r03s/bench_$w.json 2>$OUT/r03s/bench_$w.err || { echo FAIL $w; tail -5 $OUT/r03s/bench_$w.err; }
 done
-python - <<'PY' | tee gpurun_out/r03s/summary.txt
+python - <<PY | tee $OUT/r03s/summary.txt
 import json,glob
-for f in sorted(glob.glob('gpurun_out/r03s/bench_*.json')):
+for f in sorted(glob.glob('$OUT/r03s/bench_*.json')):
     try:
         d=json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

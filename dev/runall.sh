@@ -1,13 +1,15 @@
 # dev tool: one bench line per workload (no CPU baseline), summary table at the end
+export OUT=${OUT:-out}
+mkdir -p $OUT
 for w in neuralcf mf deepfm pnn ffm deepcrossing widedeep nfm afm lr gather26; do
-  python bench.py --workload $w --steps 30 --warmup 5 --no-cpu-baseline > gpurun_out/bench_$w.json 2>gpurun_out/bench_$w.err || { echo FAIL $w; tail -5 gpurun_out/bench_$w.err; }
+  python bench.py --full --workload $w --steps 30 --warmup 5 --no-cpu-baseline > $OUT/bench_$w.json 2>$OUT/bench_$w.err || { echo FAIL $w; tail -5 $OUT/bench_$w.err; }
 done
 for w in din dien deepcross; do
-  python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/bench_$w.json 2>gpurun_out/bench_$w.err || { echo FAIL $w; tail -5 gpurun_out/bench_$w.err; }
+  python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_$w.json 2>$OUT/bench_$w.err || { echo FAIL $w; tail -5 $OUT/bench_$w.err; }
 done
-python - <<'PY'
+python - <<PY
 import json,glob
-for f in sorted(glob.glob('gpurun_out/bench_*.json')):
+for f in sorted(glob.glob('$OUT/bench_*.json')):
     try:
         d=json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:
