@@ -376,6 +376,16 @@ constexpr int kStripP = 3 * kTile;                        // per wave: tiles A0 
 // coalesced by LDS-DMA, 16-byte chunks XOR-swizzled with the row so that both read patterns (sample-major ds_read_b128,
 // unit-major ds_read_b32) spread over the banks
 constexpr int kSgPU = 0, kSgPI = 1024, kSgY1 = 2048, kSgY2 = 2560, kSgY3 = 2816, kBwdStage = 3072;
+// dynamic LDS of ncfp_bwd_kernel (floats): tower weights, per-wave tiles and staging, then the rows + 1 bucket offsets;
+// the wave sums parked at the end (kCopy per wave) reuse the same space
+constexpr int kBwdLdsMax = 150 * 1024 / 4;
+constexpr int64_t bwd_lds_floats(int64_t rows) {
+  const int64_t main_f = kWFloats + kWaves * (kStripP + kBwdStage) + (rows + 1 + 3) / 4 * 4, copy_f = (int64_t)kWaves * kCopy;
+  return main_f > copy_f ? main_f : copy_f;
+}
+// every table size pattern_ok() (and so the forward) admits, the backward must be able to run: 16384 rows take
+// 18944 + 16388 floats (138 of the 150 KB); the offsets would fit up to 19455 rows
+static_assert(bwd_lds_floats(CTR_NCF_PROJ_MAX_ROWS) <= kBwdLdsMax, "CTR_NCF_PROJ_MAX_ROWS: the backward's offsets do not fit in LDS");
 constexpr int kBwdDma = 12;                               // row fetches per group
 constexpr int kBwdStores = 10;                            // 8 bucket-row pieces + 2 slot records
 
@@ -1241,9 +1251,8 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   const Ids ids{d->user_idx, d->user_stride, d->item_idx, d->item_stride, nu, ni};
   const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, g->gprob, g->ldgprob, d->head_act, d->counts, d->ranks, gzb, aux,
               offs, slabs, stt, rows * 128, g->zero_buf, g->zero_buf ? g->zero_floats : 0};
-  const int64_t main_f = kWFloats + kWaves * (kStripP + kBwdStage) + (rows + 1 + 3) / 4 * 4, copy_f = (int64_t)kWaves * kCopy;
-  const size_t lds_bytes = sizeof(float) * (size_t)(main_f > copy_f ? main_f : copy_f);
-  CTR_REQUIRE(lds_bytes <= 150 * 1024, CTR_ELIMIT);
+  const size_t lds_bytes = sizeof(float) * (size_t)bwd_lds_floats(rows);
+  CTR_REQUIRE(bwd_lds_floats(rows) <= kBwdLdsMax, CTR_ELIMIT);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)lds_bytes) != hipSuccess)
     return CTR_ELAUNCH;

@@ -264,19 +264,22 @@ class ExchangePlan:
       host-known: a FRESH id tensor's lookup is enqueued without any host read; whether a bucket overflowed (or an id
       was outside the table) is MAX-all-reduced on the device, copied to pinned memory and looked at only after the
       whole lookup has been enqueued (``verify``), while the GPU works through it.  An overflow makes every rank
-      rebuild the plan in the exact layout -- slower, never wrong.
+      rebuild the plan in the exact layout -- slower, never wrong.  Without ``capacity_ids`` the slots are sized from
+      each rank's own n, so that state (which also carries the ranks' largest and smallest n) is read before the id
+      exchange instead: one host wait per new plan, and a ragged batch raises on every rank.
 
     A plan is reused by every table looked up with those ids (FFM: two field-aware tables per id column) and by
     every later step that passes the same, unmodified tensor (the reference trains full-batch on the same tensors
     every epoch, scripts/din.py:93-96): those steps run no bucketing and no id exchange, only the two row exchanges."""
 
     __slots__ = ("send_counts", "recv_counts", "perm", "inv", "recv_ids", "n", "cap", "valid", "mark", "_state", "_event",
-                 "verified", "_verdict")
+                 "verified", "_verdict", "equal_n")
 
     def verify(self) -> Optional[str]:
         """None: the plan is good.  'overflow': every rank must rebuild it in the exact layout.  Raises IndexError (on
-        every rank) for ids outside the table.  Host-blocks only until the 32-byte state copy, issued
-        before the lookup's gathers and exchanges, has landed."""
+        every rank) for ids outside the table, and ValueError (on every rank) when the wire was sized from each rank's
+        own n (``equal_n``: no ``capacity_ids``) and the ranks' n differ.  Host-blocks only until the 32-byte state
+        copy, issued before the lookup's gathers and exchanges, has landed."""
         if self.verified:
             return None
         if self._state is not None:
@@ -284,10 +287,16 @@ class ExchangePlan:
                 self._event.synchronize()
             over, bad, n_max, n_negmax = (int(v) for v in self._state.tolist())
             self._state = self._event = None
-            self._verdict = ("bad", bad) if bad else "overflow" if over else None
+            if self.equal_n and n_max != -n_negmax:
+                self._verdict = ("ragged", f"lookups of {-n_negmax} to {n_max} ids on the ranks of this group: a "
+                                           f"capacity-bounded ShardedEmbedding without capacity_ids needs the same "
+                                           f"number of ids on every rank (set capacity_ids for ragged batches)")
+            else:
+                self._verdict = ("bad", f"index out of range in self ({bad} ids outside the table on a rank of this "
+                                        f"group)") if bad else "overflow" if over else None
             self.verified = self._verdict is None
         if isinstance(self._verdict, tuple):        # (every time the cached plan is used again, on every rank)
-            raise IndexError(f"index out of range in self ({self._verdict[1]} ids outside the table on a rank of this group)")
+            raise (ValueError if self._verdict[0] == "ragged" else IndexError)(self._verdict[1])
         return self._verdict
 
 
@@ -345,14 +354,17 @@ def _exact_plan(flat: torch.Tensor, module: "ShardedEmbedding") -> ExchangePlan:
     plan.send_counts, plan.recv_counts, plan.perm, plan.inv, plan.n = send_counts, recv_counts, perm, inv, flat.numel()
     plan.recv_ids = _exchange(send_ids, send_counts, recv_counts, group).long()   # local rows the peers want
     plan.cap, plan.valid, plan.mark, plan._state, plan._event, plan.verified = None, None, plan.recv_ids, None, None, True
-    plan._verdict = None
+    plan._verdict, plan.equal_n = None, False
     return plan
 
 
 def _padded_plan(flat: torch.Tensor, module: "ShardedEmbedding") -> ExchangePlan:
     """no host read: see ExchangePlan.  The wire size must be the same on every rank WITHOUT talking about it: it is
     derived from ``module.capacity_ids`` when that is set (any n up to it is fine, on any rank), else from this call's
-    n -- which then has to be the same on every rank (the equal split of a global batch)."""
+    n -- which then has to be the same on every rank (the equal split of a global batch).  In that second case the
+    reduced state IS read before the id exchange is enqueued (one host wait per new plan, none for a cached one): ranks
+    with different n would enqueue equal-split all-to-alls of different sizes, which hangs or corrupts memory instead
+    of raising; this way every rank raises the same ValueError."""
     be, group, world = module.backend, module.group, module.world
     n = flat.numel()
     if module.capacity_ids is not None and n > module.capacity_ids:
@@ -370,10 +382,13 @@ def _padded_plan(flat: torch.Tensor, module: "ShardedEmbedding") -> ExchangePlan
         plan._event.record()
     else:
         plan._state, plan._event = state, None
+    plan.verified, plan._verdict, plan.equal_n = False, None, module.capacity_ids is None
+    if plan.equal_n:
+        plan.verify()                       # raises on every rank if the n differ (or an id is outside the table)
     recv = _exchange(send, None, None, group)                                   # world*cap int32, -1 = unused slot
     plan.recv_ids, plan.valid, plan.mark = be.recv_rows(recv, module.weight.shape[0])
     plan.send_counts = plan.recv_counts = None
-    plan.perm, plan.inv, plan.n, plan.cap, plan.verified, plan._verdict = perm, inv, n, cap, False, None
+    plan.perm, plan.inv, plan.n, plan.cap = perm, inv, n, cap
     return plan
 
 

@@ -1280,7 +1280,9 @@ def topk_rows(scores: torch.Tensor, k: int, dim: int = -1) -> torch.Tensor:
     """indices of the k best scores along ``dim`` of a 2-D float32 tensor, best first, ties by ascending index
     (csrc/topk.hip) -- the ranking step of every ``recommendation()`` (reference: ``torch.topk(...)[1]``,
     model/mf.py:28-35, neuralcf.py:61-72, pnn.py:133-143, din.py:55-66).  ``dim=0`` ranks columns (AutoRec's
-    item-based variant) and returns (k, cols) like torch.  k up to 4096."""
+    item-based variant) and returns (k, cols) like torch.  k up to TOPK_MAX_K runs the kernel; a larger k (a
+    catalogue of more than 4096 items ranked whole, as MF / NeuralCF do) is a stable descending device sort of the
+    kernel's own 32-bit keys, which gives the same order: NaN first, ties by ascending index."""
     _lib.require_device(scores)
     if scores.dim() != 2 or scores.dtype != torch.float32:
         raise ValueError("topk_rows expects a 2-D float32 tensor")
@@ -1288,6 +1290,11 @@ def topk_rows(scores: torch.Tensor, k: int, dim: int = -1) -> torch.Tensor:
     rows, n = scores.shape[1 - along], scores.shape[along]
     if not 1 <= k <= n:
         raise RuntimeError(f"selected index k out of range: k = {k}, {n} candidates")
+    if k > TOPK_MAX_K:
+        # ordered_key() of csrc/topk.hip: sign bit set -> ~bits, else bits | 2^31 (int64, so no unsigned compare needed)
+        bits = scores.view(torch.int32).to(torch.int64)
+        key = torch.where(bits < 0, ~bits, bits + (1 << 31))
+        return torch.sort(key, dim=along, descending=True, stable=True).indices.narrow(along, 0, k)
     out = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
     rc = _lib.load().ctr_topk_rows(_lib.ptr(scores) if rows else None, scores.stride(1 - along), scores.stride(along), rows, n, k,
                                    _lib.ptr(out) if rows else None, None, _lib.stream_ptr())

@@ -209,3 +209,14 @@ def test_ctypes_signatures_match_header_prototypes(lib):
         # a device `int32_t* err_flag` is passed as a raw pointer; only host int arrays are typed
         norm = ["ptr" if k == "i32*" and g == "ptr" else k for k, g in zip(kinds, got)]
         assert got == norm, f"{name}: header {kinds} vs ctypes {got}"
+
+
+def test_python_mirrors_of_header_limits_match(lib):
+    """the admission checks on the Python side (ops.NcfProj.supported(), ops.topk_rows, ...) read these mirrors: a
+    limit changed in the header alone would send admitted shapes to a library that refuses them"""
+    from deeplearningrecommendationsystem_amd import ops
+    text = open(os.path.join(ROOT, "include", "ctrhip.h")).read()
+    defines = {k: int(v) for k, v in re.findall(r"^#define (CTR_[A-Z0-9_]+) (\d+)\b", text, flags=re.M)}
+    for name in ("CTR_MAX_FIELDS", "CTR_NCF_PROJ_MAX_ROWS", "CTR_NCF_PROJ_COUNT_STRIDE", "CTR_ROWS1_MAX_ROWS"):
+        assert getattr(lib, name) == defines[name], name
+    assert ops.TOPK_MAX_K == defines["CTR_TOPK_MAX_K"]

@@ -299,17 +299,79 @@ def _bucket_worker(rank, world, port, out):
         dist.destroy_process_group()
 
 
-def _run(fn, *args):
+def _ragged_worker(rank, world, port, out):
+    """the capacity-bounded layout without capacity_ids sizes the wire from each rank's own n: ranks that look up
+    different numbers of ids must all raise the same error (not enqueue all-to-alls of different sizes)"""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from deeplearningrecommendationsystem_amd import dist as ctr_dist
+        vocab, dim = 61, 4
+        torch.manual_seed(0)
+        full = torch.randn(vocab, dim)
+        emb = ctr_dist.ShardedEmbedding(vocab, dim, backend=NumpyShardBackend(), average=False, capacity_factor=1.5)
+        emb.load_full_table(full)
+        g = torch.Generator().manual_seed(3 + rank)
+        # 100 ids on rank 0; 40 or 96 on rank 1 (96 gets the same wire size as 100, but only by rounding)
+        for fewer in (40, 96):
+            ragged = torch.randint(0, vocab, (100 if rank == 0 else fewer,), generator=g)
+            assert (emb.capacity(100) == emb.capacity(fewer)) == (fewer == 96)
+            try:
+                emb(ragged)
+                raise AssertionError(f"rank {rank}: a ragged lookup ({fewer} / 100) without capacity_ids was not refused")
+            except ValueError as e:
+                assert f"{fewer} to 100 ids" in str(e) and "capacity_ids" in str(e), str(e)
+        # the group is still usable: equal n on both ranks, rows and gradients against the full table
+        for count in (100, 7):
+            ids = torch.randint(0, vocab, (count,), generator=g)
+            emb.weight.grad = None
+            rows = emb(ids)
+            assert torch.equal(rows, full[ids]) and emb.fallbacks == 0
+            gr = torch.randn(rows.shape, generator=g)
+            (rows * gr).sum().backward()
+            ref = _full_grad([ids], [gr], vocab, dim, rank, world)
+            torch.testing.assert_close(emb.weight.grad[:ref.shape[0]], ref, rtol=1e-6, atol=1e-6)
+        # the same ragged sizes with capacity_ids: the wire is sized for the largest lookup, and they are fine
+        rag = ctr_dist.ShardedEmbedding(vocab, dim, backend=NumpyShardBackend(), average=False, capacity_factor=1.5,
+                                        capacity_ids=100)
+        rag.load_full_table(full)
+        rows = rag(ragged)
+        assert torch.equal(rows, full[ragged]) and rag.fallbacks == 0
+        gr = torch.randn(rows.shape, generator=g)
+        (rows * gr).sum().backward()
+        ref = _full_grad([ragged], [gr], vocab, dim, rank, world)
+        torch.testing.assert_close(rag.weight.grad[:ref.shape[0]], ref, rtol=1e-6, atol=1e-6)
+        out.put((rank, "ok"))
+    except Exception:  # pragma: no cover
+        import traceback
+        out.put((rank, traceback.format_exc()))
+    finally:
+        dist.destroy_process_group()
+
+
+def _run(fn, *args, timeout=120):
+    import time
     ctx = mp.get_context("spawn")
     out = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=fn, args=(r, 2, port) + args + (out,)) for r in range(2)]
     for p in procs:
         p.start()
-    for p in procs:
-        p.join(120)
-    results = dict(out.get(timeout=5) for _ in procs)
-    assert results == {0: "ok", 1: "ok"}, results
+    try:
+        deadline = time.monotonic() + timeout
+        for p in procs:
+            p.join(max(0.0, deadline - time.monotonic()))
+        hung = [r for r, p in enumerate(procs) if p.is_alive()]
+        assert not hung, f"ranks {hung} still running after {timeout} s (a collective that never completes)"
+        dead = {r: p.exitcode for r, p in enumerate(procs) if p.exitcode != 0}
+        assert not dead, f"ranks died with exit codes {dead}"
+        results = dict(out.get(timeout=5) for _ in procs)
+        assert results == {0: "ok", 1: "ok"}, results
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join()
 
 
 @pytest.mark.timeout(180)
@@ -321,6 +383,11 @@ def test_sharded_embedding_two_ranks_matches_full_table():
 @pytest.mark.parametrize("capacity", [None, 1.5])
 def test_sharded_embedding_with_a_new_id_tensor_every_step(capacity):
     _run(_fresh_batches_worker, capacity)
+
+
+@pytest.mark.timeout(120)
+def test_capacity_bounded_lookup_refuses_ragged_batches_on_every_rank():
+    _run(_ragged_worker, timeout=60)
 
 
 @pytest.mark.timeout(180)

@@ -236,17 +236,20 @@ def test_ffm_config3_shape_whole_step_against_oracle(batch):
         torch.testing.assert_close(p.grad.cpu(), want, rtol=1e-4, atol=floor, msg=lambda s, k=k: f"grad {k}: {s}")
 
 
+@pytest.mark.parametrize("batch", [256, 4160])
 @pytest.mark.parametrize("name,dim", [("din", 64), ("dien", 16)])
-def test_sequence_models_config5_backward_against_oracle_on_a_slice(name, dim):
+def test_sequence_models_config5_backward_against_oracle_on_a_slice(name, dim, batch):
     """BASELINE configs[4] tables (1e7 rows; DIN's is 2.56 GB with rows above 2^31 bytes), L = 100: a whole train-loop
-    body on a 256-sample batch that touches the table's edges, against the CPU oracle -- every dense-layer gradient and
-    every touched table row (the padding row 0, the last row, a row above 2^31 bytes among them); rows nobody touched
-    must have no gradient.  The oracle sees the SAME rows through a compacted table (the distinct ids of the batch
+    body on a batch that touches the table's edges, against the CPU oracle -- every dense-layer gradient and every
+    touched table row (the padding row 0, the last row, a row above 2^31 bytes among them); rows nobody touched must
+    have no gradient.  The oracle sees the SAME rows through a compacted table (the distinct ids of the batch
     renumbered 0..n-1: gather and scatter are row copies / row sums, so the arithmetic is unchanged) instead of
-    cloning 2.56 GB and building a dense 1e7-row gradient on the host."""
+    cloning 2.56 GB and building a dense 1e7-row gradient on the host.  Batch 256 puts DIN's fc-stack dW on the tile
+    kernel; 4160 (above 4096, not a multiple of 128) on the direct-to-LDS one (gemm_dlds_dw.hip), as the real batch
+    does (DIEN's narrower fc stack runs in the fused stack kernel at both)."""
     from deeplearningrecommendationsystem_amd import synth
     from deeplearningrecommendationsystem_amd.model import DIEN, DIN
-    vocab, length, batch = 10_000_000, 100, 256
+    vocab, length = 10_000_000, 100
     torch.manual_seed(60 + dim)
     with torch.device(DEV):
         module = (DIN if name == "din" else DIEN)(vocab, dim)
@@ -267,7 +270,10 @@ def test_sequence_models_config5_backward_against_oracle_on_a_slice(name, dim):
     params = {k: v.detach().cpu().clone() for k, v in module.state_dict().items() if k != tname}
     params[tname] = table.detach()[uniq.to(DEV)].cpu()
     chist, ctarget = inv[:batch * length].view(batch, length), inv[batch * length:]
-    prob_ref, loss_ref, grads_ref = orc.step(name, params, [chist, ctarget], y)
+    # in float64: at 4160 samples an fc pre-activation of 5e-9 (DIEN, sample 3275, unit 112) rounds to exactly 0 in a
+    # float32 oracle, whose relu'(0) = 0 then drops that sample's whole row from the fc.0 gradient
+    prob_ref, loss_ref, grads_ref = orc.step(name, params, [chist, ctarget], y, dtype=torch.float64)
+    prob_ref, loss_ref, grads_ref = prob_ref.float(), loss_ref.float(), {k: v.float() for k, v in grads_ref.items()}
     assert float(prob_ref.std()) > 0.003, "degenerate case: the scores do not depend on the rows"
     # ---- the HIP step on the full table
     module.train()

@@ -568,6 +568,42 @@ def test_neuralcf_any_tower_table_row_path_against_oracle_and_per_sample_path(sh
     _check_grads(grads, grads2)
 
 
+@pytest.mark.parametrize("nu,ni", [(4000, 7264), (6000, 10384), (6001, 10384)])
+def test_neuralcf_table_row_path_at_the_edge_of_the_admitted_table_rows(nu, ni):
+    """the cfg2 tower at the largest table NcfProj.supported() admits (CTR_NCF_PROJ_MAX_ROWS = 16384 rows: the backward
+    keeps rows + 1 bucket offsets in LDS, next to 2816 floats of tower weights), one row more (the composed table-row
+    path takes over), and 11264 rows (where the offsets would stop fitting beside the 11008 weight floats of the
+    four-layer tower kernel): forward, BCELoss, backward and every gradient against the CPU oracle, with the first and
+    last row of both tables in the batch"""
+    from deeplearningrecommendationsystem_amd import _lib, synth
+    from deeplearningrecommendationsystem_amd.model import neuralcf as ncf_mod
+    rows = nu + ni
+    batch = max(4 * rows, 65536)
+    projected = rows <= _lib.CTR_NCF_PROJ_MAX_ROWS
+    module = _ncf(nu, ni, 23)
+    gen = synth.generator(rows)
+    u, i = synth.id_batch(batch, nu, ni, gen)
+    u[0], i[0], u[1], i[1] = 0, 0, nu - 1, ni - 1
+    y = synth.labels(batch, True, gen)
+    params = {k: v.detach().clone() for k, v in module.state_dict().items()}
+    prob_ref, loss_ref, grads_ref = orc.step("neuralcf", params, [u, i], y)
+    module = module.to(DEV)
+    ran = []
+    fns = (ncf_mod._NeuralCFProjFunction, ncf_mod._NeuralCFRowsFunction)
+    real = [fn.forward for fn in fns]
+    try:
+        for fn, r in zip(fns, real):
+            fn.forward = staticmethod(lambda *a, fn=fn, r=r: (ran.append(fn.__name__), r(*a))[1])
+        prob, loss, grads = _run(module, [u, i], y)
+    finally:
+        for fn, r in zip(fns, real):
+            fn.forward = staticmethod(r)
+    assert ran == ["_NeuralCFProjFunction" if projected else "_NeuralCFRowsFunction"], ran
+    torch.testing.assert_close(prob, prob_ref, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(loss, loss_ref, rtol=1e-5, atol=1e-6)
+    _check_grads(grads, grads_ref)
+
+
 def test_neuralcf_table_row_path_counters_survive_unusual_call_orders():
     """the sample counters behind the sort-free bucketing (ops.NcfCounts) are cleared by the backward for the next
     forward: training forwards without a backward, two forwards before their backwards, a second backward"""
@@ -893,3 +929,38 @@ def test_batched_recommendation_matches_the_per_user_loop_sequence_models(cls):
             want.append(torch.topk(m(hist, target), k, dim=0).indices.view(1, -1).tolist()[0])
     got = m.recommendation(nu, ni, hist_list, k)
     assert np.array_equal(got, np.array(want))
+
+
+@pytest.mark.parametrize("name", ["mf", "neuralcf"])
+def test_recommendation_ranks_a_catalogue_beyond_the_topk_kernel(name):
+    """MF and NeuralCF rank the WHOLE catalogue (k = num_items, model/mf.py:35, neuralcf.py:70): 5003 items is more than
+    the top-k kernel takes (ops.TOPK_MAX_K), against the oracle's torch.topk; some items are exact copies of others, so
+    their scores tie and may come in either order"""
+    from deeplearningrecommendationsystem_amd import ops
+    from deeplearningrecommendationsystem_amd.model import MatrixFactorization, NeuralCF
+    nu, ni = 5, 5003
+    assert ni > ops.TOPK_MAX_K
+    torch.manual_seed(41)
+    module = MatrixFactorization(nu, ni, 32) if name == "mf" else NeuralCF(nu, ni, 64, [128, 64, 32, 16, 8])
+    with torch.no_grad():
+        for key, p in module.state_dict().items():
+            if "item" in key.lower() and p.dim() == 2 and p.shape[0] == ni:
+                p[4097:4197] = p[10]                 # 100 items that score exactly like item 10
+                p[ni - 1] = p[0]
+    params = {k: v.detach().clone() for k, v in module.state_dict().items()}
+    want, scores = orc.recommend_ids(name, params, nu, ni)
+    module = module.to(DEV).eval()
+    got = module.recommendation(nu, ni)
+    assert got.shape == (nu, ni)
+    assert all(sorted(row.tolist()) == list(range(ni)) for row in got)
+    gu.assert_same_ranking(got, want.numpy(), scores.numpy(), tol=1e-5)
+    # and exactly the order of the device's own scores: descending, equal scores by ascending index
+    with torch.no_grad():
+        if name == "mf":
+            own = ops.linear_fwd(module.user_embeddings.weight, module.item_embeddings.weight, None)
+        else:
+            users = torch.arange(nu, device=DEV).repeat_interleave(ni)
+            own = module(users, torch.arange(ni, device=DEV).repeat(nu)).view(nu, ni)
+    exact = torch.sort(own.double().cpu(), dim=1, descending=True, stable=True).indices
+    assert np.array_equal(got, exact.numpy())
+    assert int((own[:, 4097:4197] == own[:, 10:11]).all(dim=1).sum()) == nu      # the copies did tie

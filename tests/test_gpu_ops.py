@@ -1015,30 +1015,34 @@ def test_sharded_embedding_single_rank_on_gpu(capacity):
 
 
 @pytest.mark.parametrize("rows,n,k", [(943, 1682, 1682), (7, 1682, 10), (3, 1, 1), (5, 4096, 50), (4, 4097, 4096),
-                                      (6, 100000, 20), (2, 1000003, 100), (3, 20000, 1)])
+                                      (6, 100000, 20), (2, 1000003, 100), (3, 20000, 1),
+                                      # k above ops.TOPK_MAX_K: a whole catalogue of more than 4096 items
+                                      (3, 5000, 5000), (2, 100000, 4097), (4, 8193, 8193)])
 def test_topk_rows_ranks_like_torch_with_ties_by_index(rows, n, k):
-    """csrc/topk.hip against torch.topk on CPU (the reference's ranking call, model/mf.py:35): same scores position
-    by position; where scores tie, ascending index (torch leaves the order of ties open)"""
+    """csrc/topk.hip (k <= 4096) and the device sort behind larger k against torch.topk on CPU (the reference's ranking
+    call, model/mf.py:35): same scores position by position; where scores tie, ascending index (torch leaves the order
+    of ties open)"""
     from deeplearningrecommendationsystem_amd import ops
     g = torch.Generator().manual_seed(rows * 31 + n + k)
     scores = torch.randn(rows, n, generator=g)
     if n >= 1682:
         scores[0] = torch.randint(0, 7, (n,), generator=g).float()          # heavy ties: only 7 distinct scores
         scores[1, 5], scores[1, 900] = float("inf"), float("-inf")
-        scores[2 % rows, 17] = float("nan")                                  # NaN ranks first, as in torch
+        scores[min(2, rows - 2), 17] = float("nan")                          # NaN ranks first (above +inf), as in torch
         scores[-1] = 0.25                                                    # one value everywhere: index order
     got = ops.topk_rows(scores.to(DEV), k).cpu()
     assert got.shape == (rows, k) and got.dtype == torch.int64
-    # the exact expected order: stable sort by descending score, NaN first
-    key = torch.where(torch.isnan(scores), torch.full_like(scores, float("inf")), scores)
-    nan_first = torch.isnan(scores).double() * 1e30
-    want = torch.argsort(-(key.double().clamp(-1e300, 1e300).nan_to_num(posinf=1e29, neginf=-1e29) + nan_first), dim=1, stable=True)[:, :k]
+    # the exact expected order: NaN, +inf, finite scores descending, -inf; ties by ascending index (two stable sorts)
+    cls = torch.where(torch.isnan(scores), 3, torch.where(torch.isfinite(scores), 1, torch.where(scores > 0, 2, 0)))
+    by_value = torch.argsort(-torch.where(torch.isfinite(scores), scores.double(), 0.0), dim=1, stable=True)
+    want = by_value.gather(1, torch.argsort(-cls.gather(1, by_value), dim=1, stable=True))[:, :k]
     assert torch.equal(got, want)
     ref = torch.topk(scores, k, dim=1)
     torch.testing.assert_close(torch.gather(scores, 1, got), ref.values, rtol=0, atol=0, equal_nan=True)
     # a column-major view (AutoRec's item-based ranking: topk along dim 0) and a strided row view
     view = scores.to(DEV).t().contiguous().t()                               # same values, column stride != 1
     assert torch.equal(ops.topk_rows(view, k).cpu(), want)
+    assert torch.equal(ops.topk_rows(scores.to(DEV).t(), k, dim=0).cpu(), want.t())   # the same ranking along dim 0
     kk = min(k, rows)
     cols = ops.topk_rows(scores.to(DEV), kk, dim=0).cpu()
     assert cols.shape == (kk, n)
