@@ -15,7 +15,7 @@ import torch  # noqa: F401  (maps libamdhip64 first, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTRHIP_LIB", os.path.join(_HERE, "libctrhip.so"))  # env override: A/B builds
-ABI_VERSION = 33
+ABI_VERSION = 34
 DIN_TRIPLE, DIN_PAIR, DIN_H = 0, 1, 2  # layouts of the DIN attention operand (include/ctrhip.h)
 
 CTR_MAX_FIELDS = 32
@@ -176,6 +176,9 @@ SIGNATURES = {
     "ctr_shard_recv_rows": (_i, [_p, _l, _l, _p, _p, _p, _p]),
     "ctr_rows_zero": (_i, [_p, _l, _l, _i, _p, _l, _p]),
     "ctr_topk_rows": (_i, [_p, _l, _l, _l, _l, _i, _p, _p, _p]),
+    "ctr_cf_knn": (_i, [_p, _l, _l, _p, _l, _l, _i, _p, _p, _p]),
+    "ctr_usercf_scores": (_i, [_p, _l, _l, _l, _p, _p, _i, _p, _l, _p, _l, _p]),
+    "ctr_itemcf_scores": (_i, [_p, _l, _l, _l, _p, _p, _i, _p, _l, _p, _l, _p]),
     "ctr_rows1_scatter": (_i, [_p, _l, _i, _i, _p, _l, _p, _l, _l, _p, _l, _p, _l, _p]),
     "ctr_fold_head_fwd": (_i, [_p, _i, _p, _l, _p, _p, _i, _i, _p, _p, _p]),
     "ctr_fold_head_bwd": (_i, [_p, _i, _p, _l, _p, _i, _i, _p, _p, _p, _p, _l, _p, _p, _p]),

@@ -1300,3 +1300,61 @@ def topk_rows(scores: torch.Tensor, k: int, dim: int = -1) -> torch.Tensor:
                                    _lib.ptr(out) if rows else None, None, _lib.stream_ptr())
     _lib.check(rc, "ctr_topk_rows")
     return out if along == 1 else out.t()
+
+
+CF_KNN_MAX_K = 64   # CTR_CF_KNN_MAX_K: the longest list (k + 1 entries) ctr_cf_knn keeps per row
+
+
+def _cf_operand(x: torch.Tensor, counts: torch.Tensor):
+    _lib.require_device(x, counts)
+    if x.dim() != 2 or x.dtype != torch.int8 or not x.is_contiguous() or x.shape[1] % 64:
+        raise ValueError("expected a contiguous (rows, cols_pad) int8 matrix with cols_pad a multiple of 64")
+    if counts.dtype != torch.int32 or counts.shape != (x.shape[0],) or not counts.is_contiguous():
+        raise ValueError("expected int32 row counts, one per row")
+
+
+def cf_knn(x: torch.Tensor, counts: torch.Tensor, kk: int, q_begin: int = 0, q_count: Optional[int] = None):
+    """per query row of the int8 0/1 matrix ``x`` the ``kk`` best rows by cosine similarity (csrc/knn_cf.hip),
+    descending, ties by ascending index, the row itself included -> (idx int64, sim float32), (q_count, kk); a list
+    shorter than kk ends in -1 / 0.  Query rows are ``[q_begin, q_begin + q_count)``, base rows all of ``x``."""
+    _cf_operand(x, counts)
+    rows = x.shape[0]
+    q_count = rows - q_begin if q_count is None else q_count
+    if not 1 <= kk <= CF_KNN_MAX_K:
+        raise ValueError(f"k + 1 = {kk} neighbours requested: the kernel keeps at most {CF_KNN_MAX_K} (k <= "
+                         f"{CF_KNN_MAX_K - 1})")
+    idx = torch.empty((q_count, kk), dtype=torch.int64, device=x.device)
+    sim = torch.empty((q_count, kk), dtype=torch.float32, device=x.device)
+    rc = _lib.load().ctr_cf_knn(x.data_ptr(), rows, x.shape[1], counts.data_ptr(), q_begin, q_count, kk,
+                                idx.data_ptr(), sim.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_cf_knn")
+    return idx, sim
+
+
+def _cf_scores(fn_name: str, x: torch.Tensor, num_items: int, nbr: torch.Tensor, nsim: torch.Tensor,
+               users: torch.Tensor, table_rows: int) -> torch.Tensor:
+    _lib.require_device(x, nbr, nsim, users)
+    if x.dim() != 2 or x.dtype != torch.int8 or not x.is_contiguous() or x.shape[1] % 64 or x.shape[1] < num_items:
+        raise ValueError("expected the contiguous (num_users, cols_pad) int8 interaction matrix")
+    if nbr.dtype != torch.int64 or nsim.dtype != torch.float32 or nbr.shape != nsim.shape or nbr.dim() != 2 \
+            or not (nbr.is_contiguous() and nsim.is_contiguous()):
+        raise ValueError("neighbours: contiguous int64 indices and float32 similarities of one (n, k) shape")
+    if nbr.shape[0] != table_rows:
+        raise ValueError(f"neighbour table has {nbr.shape[0]} rows, expected {table_rows}")
+    users = users.to(torch.int64).contiguous()
+    out = torch.empty((users.numel(), num_items), dtype=torch.float32, device=x.device)
+    rc = getattr(_lib.load(), fn_name)(x.data_ptr(), x.shape[0], x.shape[1], num_items, nbr.data_ptr(),
+                                       nsim.data_ptr(), nbr.shape[1], users.data_ptr(), users.numel(),
+                                       out.data_ptr(), num_items, _lib.stream_ptr())
+    _lib.check(rc, fn_name)
+    return out
+
+
+def usercf_scores(x, num_items, nbr, nsim, users):
+    """prediction_dating (UserCF_Final.py:26-39) of every item for each user in ``users``; rated items -inf"""
+    return _cf_scores("ctr_usercf_scores", x, num_items, nbr, nsim, users, x.shape[0])
+
+
+def itemcf_scores(x, num_items, nbr, nsim, users):
+    """prediction_item_based (ItemCF_Final.py:27-38) of every item for each user in ``users``; rated items -inf"""
+    return _cf_scores("ctr_itemcf_scores", x, num_items, nbr, nsim, users, num_items)

@@ -70,3 +70,40 @@ def labels(batch: int, shape_2d: bool = True, gen: torch.Generator | None = None
     gen = gen or generator()
     y = (torch.rand(batch, generator=gen) < 0.5).float()
     return y.view(-1, 1) if shape_2d else y
+
+
+def implicit_split(num_users: int = NUM_USERS_ML100K, num_items: int = NUM_ITEMS_ML100K, train_pairs: int = 90_570,
+                   test_per_user: int = 10, seed: int = 5, zipf: float = 1.0):
+    """an implicit-feedback split shaped like ml-100k's ua.base / ua.test: every user has exactly ``test_per_user``
+    test items (as ua.test), training pairs are spread over users with a skewed count and over items by a Zipf-like
+    popularity, no pair is in both splits or twice in one, and every user and every item occurs in training.
+    Returns 0-based int64 ``(train_users, train_items, test_users, test_items)``."""
+    gen = generator(seed)
+    if train_pairs + num_users * test_per_user > num_users * num_items // 2 or train_pairs < num_users + num_items:
+        raise ValueError("split does not fit the matrix")
+    pop = 1.0 / torch.arange(1, num_items + 1, dtype=torch.float64) ** zipf
+    pop = pop[torch.randperm(num_items, generator=gen)]
+    activity = torch.rand(num_users, generator=gen, dtype=torch.float64) ** 3 + 0.05
+    taken = torch.zeros(num_users, num_items, dtype=torch.bool)
+    # every item once in training, each with a random user
+    first_users = torch.randint(0, num_users, (num_items,), generator=gen)
+    taken[first_users, torch.arange(num_items)] = True
+    # every user at least once
+    for u in torch.nonzero(~taken.any(1)).flatten().tolist():
+        taken[u, int(torch.multinomial(pop, 1, generator=gen))] = True
+    # the rest by activity x popularity, without repeats (each round adds at most the pairs still missing)
+    while int(taken.sum()) < train_pairs:
+        left = train_pairs - int(taken.sum())
+        u = torch.multinomial(activity, left, replacement=True, generator=gen)
+        i = torch.multinomial(pop, left, replacement=True, generator=gen)
+        taken[u, i] = True
+    train_u, train_i = torch.nonzero(taken, as_tuple=True)
+    # test: test_per_user unseen items per user, by popularity
+    test = torch.zeros_like(taken)
+    for u in range(num_users):
+        w = pop.clone()
+        w[taken[u]] = 0.0
+        test[u, torch.multinomial(w, test_per_user, replacement=False, generator=gen)] = True
+    test_u, test_i = torch.nonzero(test, as_tuple=True)
+    assert bool(taken.any(1).all()) and bool(taken.any(0).all())
+    return train_u, train_i, test_u, test_i

@@ -562,6 +562,35 @@ int ctr_topk_rows(const float* scores, int64_t row_stride, int64_t col_stride, i
                   int64_t* idx_out, float* val_out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Neighbourhood collaborative filtering (UserCF_Final.py / ItemCF_Final.py), on an int8 0/1 matrix x
+ * (rows x cols_pad, row-major, cols_pad % 64 == 0, zero padded, 16-byte aligned) and its int32 row counts.
+ *
+ * ctr_cf_knn replaces cosine_similarity(data) (UserCF_Final.py:23) / cosine_similarity(data.T) (ItemCF_Final.py:22)
+ * and the per-row sort of recommendations_list (UserCF_Final.py:51-53) / prediction_item_based (ItemCF_Final.py:30-33):
+ * for each query row q in [q_begin, q_begin + q_count) the kk best rows of all `rows` by
+ *   sim = float32(c / sqrt(a b)) evaluated in double (0 when a or b is 0), c = intersection count, a, b = row counts,
+ * descending, ties by ascending index; q itself included (the caller drops position 0 as the reference does).
+ * idx_out / sim_out (q_count, kk) int64 / float32; a list shorter than kk (rows < kk) ends in -1 / 0.
+ * The rows x rows similarity is never written.  kk <= CTR_CF_KNN_MAX_K (CTR_ELIMIT beyond), rows < 2^31.
+ *
+ * ctr_usercf_scores (prediction_dating, UserCF_Final.py:26-39): out[b, i] = sum_j s_j x[v_j, i] / sum_j s_j over the
+ * k neighbours v_j = nbr[u k + j], s_j = nsim[u k + j] of u = users[b] (index -1: no neighbour), float32 accumulated in
+ * neighbour order, 0 when the denominator is 0, -inf where x[u, i] != 0 (rated) or u is outside [0, num_users).
+ * ctr_itemcf_scores (prediction_item_based, ItemCF_Final.py:27-38): out[b, i] = sum_j s_ij x[u, j] / sum_j s_ij over
+ * the k neighbours j = nbr[i k + ..] of item i, same conventions.  cols_pad / 8 <= 65536 (CTR_ELIMIT beyond).
+ * out (batch, ldo) float32, ldo >= num_items; items i < num_items <= cols_pad written.
+ * ---------------------------------------------------------------------- */
+#define CTR_CF_KNN_MAX_K 64
+int ctr_cf_knn(const int8_t* x, int64_t rows, int64_t cols_pad, const int32_t* counts, int64_t q_begin,
+               int64_t q_count, int kk, int64_t* idx_out, float* sim_out, void* stream);
+int ctr_usercf_scores(const int8_t* x, int64_t num_users, int64_t cols_pad, int64_t num_items, const int64_t* nbr,
+                      const float* nsim, int k, const int64_t* users, int64_t batch, float* out, int64_t ldo,
+                      void* stream);
+int ctr_itemcf_scores(const int8_t* x, int64_t num_users, int64_t cols_pad, int64_t num_items, const int64_t* nbr,
+                      const float* nsim, int k, const int64_t* users, int64_t batch, float* out, int64_t ldo,
+                      void* stream);
+
+/* ------------------------------------------------------------------------
  * The host work either side of the step, on the device.
  * ctr_negative_sample (sampler/sampler.py:16-48): for every user u < num_users, num_negatives items drawn
  * uniformly from [0, num_items), each redrawn while bit `item` of the user's row of `excluded`

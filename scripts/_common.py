@@ -75,3 +75,8 @@ def run(trainer, splits, epochs):
         trainer.test_loop(*test[:-1], test_rating=test[-1])
         if epoch % 5 == 4 or epoch == epochs - 1:
             trainer.model_eval(epoch)
+
+
+def implicit_split():
+    """ua.base / ua.test-shaped implicit split (943 x 1682, ~90k training pairs, 10 test items per user), 0-based"""
+    return synth.implicit_split()
