@@ -5,8 +5,8 @@ The mirrors use package-relative imports, so they cannot simply be put on ``sys.
 another top-level name.  A shim package ``compat/<name>/__init__.py`` calls ``alias(...)``:
 every submodule of the real package is registered in ``sys.modules`` under the reference's
 dotted name (same module object, loaded once), and the shim's ``__path__`` is extended over
-``sys.path`` so that submodules the build does not replace (``evaluator.ranking``) still come
-from wherever the caller has them."""
+``sys.path`` so that submodules the build does not replace still come from wherever the caller
+has them."""
 from __future__ import annotations
 
 import importlib

@@ -15,7 +15,7 @@ import torch  # noqa: F401  (maps libamdhip64 first, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTRHIP_LIB", os.path.join(_HERE, "libctrhip.so"))  # env override: A/B builds
-ABI_VERSION = 34
+ABI_VERSION = 35
 DIN_TRIPLE, DIN_PAIR, DIN_H = 0, 1, 2  # layouts of the DIN attention operand (include/ctrhip.h)
 
 CTR_MAX_FIELDS = 32
@@ -179,6 +179,11 @@ SIGNATURES = {
     "ctr_cf_knn": (_i, [_p, _l, _l, _p, _l, _l, _i, _p, _p, _p]),
     "ctr_usercf_scores": (_i, [_p, _l, _l, _l, _p, _p, _i, _p, _l, _p, _l, _p]),
     "ctr_itemcf_scores": (_i, [_p, _l, _l, _l, _p, _p, _i, _p, _l, _p, _l, _p]),
+    "ctr_rank_filter": (_i, [_p, _l, _l, _l, _p, _p, _l, _p, _l, _p, _p, _p]),
+    "ctr_rank_table_slots": (_i, [_l, _l, C.POINTER(C.c_int64)]),
+    "ctr_rank_metrics_lists": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p]),
+    "ctr_rank_mask": (_i, [_p, _l, _l, _l, _p, _p, _l, _p, _p]),
+    "ctr_rank_metrics_scores": (_i, [_p, _l, _l, _l, _p, _l, _l, _p, _p, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_rows1_scatter": (_i, [_p, _l, _i, _i, _p, _l, _p, _l, _l, _p, _l, _p, _l, _p]),
     "ctr_fold_head_fwd": (_i, [_p, _i, _p, _l, _p, _p, _i, _i, _p, _p, _p]),
     "ctr_fold_head_bwd": (_i, [_p, _i, _p, _l, _p, _i, _i, _p, _p, _p, _p, _l, _p, _p, _p]),

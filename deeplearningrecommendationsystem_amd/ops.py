@@ -1296,8 +1296,9 @@ def topk_rows(scores: torch.Tensor, k: int, dim: int = -1) -> torch.Tensor:
         key = torch.where(bits < 0, ~bits, bits + (1 << 31))
         return torch.sort(key, dim=along, descending=True, stable=True).indices.narrow(along, 0, k)
     out = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
-    rc = _lib.load().ctr_topk_rows(_lib.ptr(scores) if rows else None, scores.stride(1 - along), scores.stride(along), rows, n, k,
-                                   _lib.ptr(out) if rows else None, None, _lib.stream_ptr())
+    rc = _timed("topk_rows", lambda: (4 * rows * n + 8 * rows * k, 0), _lib.load().ctr_topk_rows,
+                _lib.ptr(scores) if rows else None, scores.stride(1 - along), scores.stride(along), rows, n, k,
+                _lib.ptr(out) if rows else None, None, _lib.stream_ptr())
     _lib.check(rc, "ctr_topk_rows")
     return out if along == 1 else out.t()
 
@@ -1358,3 +1359,86 @@ def usercf_scores(x, num_items, nbr, nsim, users):
 def itemcf_scores(x, num_items, nbr, nsim, users):
     """prediction_item_based (ItemCF_Final.py:27-38) of every item for each user in ``users``; rated items -inf"""
     return _cf_scores("ctr_itemcf_scores", x, num_items, nbr, nsim, users, num_items)
+
+
+# ---------------------------------------------------------------------------
+# top-k ranking evaluation (csrc/rank_eval.hip); the CSRs are (offsets (rows + 1), ids) int64 device tensors, the
+# offsets already sliced to the rows of the call (they index ``ids`` absolutely)
+# ---------------------------------------------------------------------------
+RANK_MASK_BITS = 0xFFFFFFFF
+RANK_ERR_OFFSETS, RANK_ERR_LENGTH, RANK_ERR_SURVIVOR, RANK_ERR_COUNT = 1, 2, 4, 8
+RANK_MAX_ROWS = 1 << 24
+_RANK_TABLE_SLOTS = 1 << 25   # hash-set workspace of rank_metrics_lists: at most 256 MB (or one user's table)
+
+
+def _i64(*tensors):
+    _lib.require_device(*tensors)
+    for t in tensors:
+        if t is not None and (t.dtype != torch.int64 or not t.is_contiguous()):
+            raise ValueError("expected contiguous int64 tensors")
+
+
+def rank_filter(rec: torch.Tensor, ex_off: torch.Tensor, ex_ids: torch.Tensor, err: torch.Tensor):
+    """remove_itemid's compaction: (out (rows, len), out_len (rows,)); out[u, out_len[u]:] is unwritten (zeros)"""
+    _i64(rec, ex_off, ex_ids)
+    rows, length = rec.shape
+    out = torch.zeros((rows, length), dtype=torch.int64, device=rec.device)
+    out_len = torch.empty(rows, dtype=torch.int64, device=rec.device)
+    rc = _timed("rank_filter", lambda: (16 * rows * length, 0), _lib.load().ctr_rank_filter,
+                _lib.ptr(rec) if rec.numel() else None, length, rows, length, ex_off.data_ptr(),
+                _lib.ptr(ex_ids) if ex_ids.numel() else None, ex_ids.numel(), _lib.ptr(out) if out.numel() else None,
+                length, out_len.data_ptr(), err.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_rank_filter")
+    return out, out_len
+
+
+def rank_metrics_lists(pred: torch.Tensor, pred_len: torch.Tensor, act_off: torch.Tensor, act_ids: torch.Tensor,
+                       alen: torch.Tensor, k: int, err: torch.Tensor) -> torch.Tensor:
+    """(rows, 7) float64 partials (same, rec, real, ap, dcg, idcg, rr) of explicit predicted rows"""
+    _i64(pred, pred_len, act_off, act_ids, alen)
+    rows, length = pred.shape
+    lib = _lib.load()
+    slots = C.c_int64()
+    _lib.check(lib.ctr_rank_table_slots(k, length, C.byref(slots)), "ctr_rank_table_slots")
+    cap = slots.value
+    table = torch.empty(max(cap, min(rows, max(1, _RANK_TABLE_SLOTS // cap)) * cap), dtype=torch.int64,
+                        device=pred.device)
+    parts = torch.empty((rows, 7), dtype=torch.float64, device=pred.device)
+    rc = _timed("rank_metrics_lists", lambda: (8 * rows * length + 8 * act_ids.numel(), 0), lib.ctr_rank_metrics_lists,
+                _lib.ptr(pred) if pred.numel() else None, length, pred_len.data_ptr(), rows, length, act_off.data_ptr(),
+                _lib.ptr(act_ids) if act_ids.numel() else None, act_ids.numel(), alen.data_ptr(), k,
+                table.data_ptr(), table.numel(), parts.data_ptr(), err.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_rank_metrics_lists")
+    return parts
+
+
+def rank_mask(scores: torch.Tensor, ex_off: torch.Tensor, ex_ids: torch.Tensor, err: torch.Tensor) -> None:
+    """write RANK_MASK_BITS over every excluded item of the (rows, n) float32 chunk, in place"""
+    _lib.require_device(scores)
+    _i64(ex_off, ex_ids)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("rank_mask expects a row-major 2-D float32 tensor")
+    rows, n = scores.shape
+    rc = _timed("rank_mask", lambda: (8 * ex_ids.numel() + 4 * ex_ids.numel(), 0), _lib.load().ctr_rank_mask,
+                scores.data_ptr(), scores.stride(0), rows, n, ex_off.data_ptr(),
+                _lib.ptr(ex_ids) if ex_ids.numel() else None, ex_ids.numel(), err.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_rank_mask")
+
+
+def rank_metrics_scores(scores: torch.Tensor, top: torch.Tensor, k: int, act_off: torch.Tensor, act_ids: torch.Tensor,
+                        alen: torch.Tensor, n_real: torch.Tensor, pad: torch.Tensor, parts: torch.Tensor,
+                        err: torch.Tensor) -> None:
+    """partials of masked score rows from their top-min(k, n) into ``parts`` (rows, 7) float64"""
+    _lib.require_device(scores, parts)
+    _i64(top, act_off, act_ids, alen, n_real, pad)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("rank_metrics_scores expects a row-major 2-D float32 tensor")
+    rows, n = scores.shape
+    if parts.dtype != torch.float64 or parts.shape != (rows, 7) or not parts.is_contiguous():
+        raise ValueError("partials: contiguous (rows, 7) float64")
+    rc = _timed("rank_metrics_scores", lambda: (4 * rows * n + 8 * top.numel() + 56 * rows, 0),
+                _lib.load().ctr_rank_metrics_scores, scores.data_ptr(), scores.stride(0), rows, n, top.data_ptr(),
+                top.shape[1], k, act_off.data_ptr(), _lib.ptr(act_ids) if act_ids.numel() else None, act_ids.numel(),
+                alen.data_ptr(), n_real.data_ptr(), pad.data_ptr(), parts.data_ptr(), err.data_ptr(),
+                _lib.stream_ptr())
+    _lib.check(rc, "ctr_rank_metrics_scores")

@@ -591,6 +591,58 @@ int ctr_itemcf_scores(const int8_t* x, int64_t num_users, int64_t cols_pad, int6
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * Top-k ranking evaluation (evaluator/ranking.py: Ranking, and data/reader.py:137-159: remove_itemid).
+ *
+ * Id sets are CSRs over `rows` users: off (rows + 1, absolute into ids, device), ids (nnz, ascending within a row,
+ * device).  Offsets live on the device, so their consistency is checked there: a row with off[u] < 0,
+ * off[u+1] < off[u] or off[u+1] > nnz is read as empty and ORs CTR_RANK_ERR_OFFSETS into *err_flag (device int32,
+ * zeroed by the caller).  The per-user results are written as a (rows, 7) float64 row of partials
+ *   same = |set(a) & set(p[:k])|, rec = |set(p[:k])|, real = |set(a)|,
+ *   ap   = sum_{i<k, p[i] in a} hits_i / (i + 1) / alen[u]       (ranking.py:43-63, alen = len(a) as given),
+ *   dcg  = sum_{j<k, p[j] in a} 1 / log2(j + 2),  idcg = the same sum over min(k, sum_j [p[j] in a]) leading ones
+ *          (ranking.py:76-110: r over the whole p),
+ *   rr   = 1 / (j + 1) for the first p[j] in a over the whole p, else 0 (ranking.py:122-132);
+ * -1 is an ordinary id throughout, as in the reference.  The aggregate (ranking.py:11-41, 65-74, 112-120, 134-141)
+ * is a fixed-order host reduction of the partials.
+ *
+ * ctr_rank_filter (remove_itemid): out[u, :out_len[u]] = the entries of rec[u, :len] not in exclusion row u, in
+ * order.  out may have ld_out >= len; entries past out_len[u] are not written.
+ * ctr_rank_metrics_lists (Ranking on explicit rows): p = pred[u, :pred_len[u]] (pred_len NULL: len), a = the sorted
+ * CSR row u of the actual ids (every entry, pads included), alen[u] its original length.  table: int64 workspace of
+ * table_slots >= ctr_rank_table_slots(k, len) slots (more slots run more users at once); ids must not be INT64_MIN.
+ * ctr_rank_mask: scores[u, id] = bits CTR_RANK_MASK_BITS for every id in [0, n) of exclusion row u.  That float is the
+ * lowest key of ctr_topk_rows' order, below -inf and every other NaN.
+ * ctr_rank_metrics_scores (Ranking(a, remove_itemid(..(topk_rows(s, n))..)) without the full ranking): row u of the
+ * masked scores has n_real[u] survivors; p = the survivors in ctr_topk_rows' order followed by pad[u] times -1.
+ * topk (rows, kt), kt = min(k, n), is ctr_topk_rows of the masked rows.  The first hit of MRR comes from one pass over
+ * the row: the survivors ordered above the best relevant one.  A survivor that is NaN or -inf ORs
+ * CTR_RANK_ERR_SURVIVOR, a survivor count other than n_real[u] CTR_RANK_ERR_COUNT, n_real or pad out of range
+ * CTR_RANK_ERR_LENGTH (then the row is treated as empty); the partials of such a row are not meaningful.
+ * k >= 1 (CTR_EINVAL otherwise); rows <= CTR_RANK_MAX_ROWS (CTR_ELIMIT beyond).
+ * ---------------------------------------------------------------------- */
+#define CTR_RANK_MAX_ROWS (1ll << 24)
+#define CTR_RANK_MASK_BITS 0xffffffffu
+#define CTR_RANK_ERR_OFFSETS 1
+#define CTR_RANK_ERR_LENGTH 2
+#define CTR_RANK_ERR_SURVIVOR 4
+#define CTR_RANK_ERR_COUNT 8
+int ctr_rank_filter(const int64_t* rec, int64_t ld_rec, int64_t rows, int64_t len, const int64_t* ex_off,
+                    const int64_t* ex_ids, int64_t ex_nnz, int64_t* out, int64_t ld_out, int64_t* out_len,
+                    int32_t* err_flag, void* stream);
+int ctr_rank_table_slots(int64_t k, int64_t len, int64_t* slots);   /* *slots (host) = smallest power of two
+                                                                      >= max(64, 2 min(k, len)) */
+int ctr_rank_metrics_lists(const int64_t* pred, int64_t ld_pred, const int64_t* pred_len, int64_t rows, int64_t len,
+                           const int64_t* act_off, const int64_t* act_ids, int64_t act_nnz, const int64_t* alen,
+                           int64_t k, int64_t* table, int64_t table_slots, double* partials, int32_t* err_flag,
+                           void* stream);
+int ctr_rank_mask(float* scores, int64_t ld, int64_t rows, int64_t n, const int64_t* ex_off, const int64_t* ex_ids,
+                  int64_t ex_nnz, int32_t* err_flag, void* stream);
+int ctr_rank_metrics_scores(const float* scores, int64_t ld, int64_t rows, int64_t n, const int64_t* topk, int64_t kt,
+                            int64_t k, const int64_t* act_off, const int64_t* act_ids, int64_t act_nnz,
+                            const int64_t* alen, const int64_t* n_real, const int64_t* pad, double* partials,
+                            int32_t* err_flag, void* stream);
+
+/* ------------------------------------------------------------------------
  * The host work either side of the step, on the device.
  * ctr_negative_sample (sampler/sampler.py:16-48): for every user u < num_users, num_negatives items drawn
  * uniformly from [0, num_items), each redrawn while bit `item` of the user's row of `excluded`
