@@ -76,6 +76,17 @@ __device__ __forceinline__ void ctr_atomic_add_global(float* p, float v) {
   (void)__builtin_amdgcn_global_atomic_fadd_f32((CTR_GLOBAL float*)p, v);
 }
 
+// LDS-DMA of one wave instruction: lane L's 16 bytes from g land at lds_base + 16 L.
+// (m0 is a reserved register: the compiler only sets it right in front of an instruction that reads it,
+// never keeps a value there, and rejects it as a clobber)
+__device__ __forceinline__ void ctr_dma16(const float* g, uint32_t lds_base) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds_base) : "memory");
+}
+// byte address of an LDS pointer, as ds_* instructions and m0 take it
+__device__ __forceinline__ uint32_t ctr_lds_addr(const float* p) {
+  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
+}
+
 // Unsigned division by a run-time constant without the ~40-instruction u64/u32
 // software divide (Hacker's Delight 10-9 / libdivide "branchfree" form), exact for
 // every 32-bit numerator:  q = (t + ((n - t) >> s1)) >> s2,  t = mulhi(m, n).

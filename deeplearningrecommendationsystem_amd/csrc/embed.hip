@@ -288,22 +288,10 @@ embed_ids_fast_kernel(const TablePtrs T, int nfields, int lpr, int width, const 
     }
     ctr_f32x4 v[UNROLL];
 #pragma unroll
-    for (int k = 0; k < UNROLL; ++k) {
-#ifdef CTR_NT_LOADS
-      v[k] = __builtin_nontemporal_load((const CTR_GLOBAL ctr_f32x4*)(src[k]));
-#else
-      v[k] = *(const CTR_GLOBAL ctr_f32x4*)(src[k]);
-#endif
-    }
+    for (int k = 0; k < UNROLL; ++k) v[k] = *(const CTR_GLOBAL ctr_f32x4*)(src[k]);
 #pragma unroll
     for (int k = 0; k < UNROLL; ++k)
-      if (live[k]) {
-#ifdef CTR_NT_STORES
-        __builtin_nontemporal_store(v[k], (CTR_GLOBAL ctr_f32x4*)(dst[k]));
-#else
-        *(CTR_GLOBAL ctr_f32x4*)(dst[k]) = v[k];
-#endif
-      }
+      if (live[k]) *(CTR_GLOBAL ctr_f32x4*)(dst[k]) = v[k];
   }
 }
 
@@ -322,17 +310,13 @@ bool try_fast_ids(const ctr_field_t* f, int n, int64_t batch, float* out, int64_
     T.p[i] = f[i].table;
     T.vocab[i] = f[i].vocab;
   }
-#ifndef CTR_FAST_UNROLL
-#define CTR_FAST_UNROLL 2  // A/B on MI355X (dev/gather_ab.py): 1/2/4/8 x grid caps are within 2 %, 2 x 8192 best on Zipf ids
-#endif
-  constexpr int kUnroll = CTR_FAST_UNROLL;
+  // A/B on MI355X (retired script, in git history): unroll 1/2/4/8 x grid caps within 2 %, 2 x 8192 best on Zipf ids
+  constexpr int kUnroll = 2;
+  constexpr int64_t kMaxGrid = 256 * 32;
   const uint32_t items = (uint32_t)(batch * n);
   const uint32_t per_block = (kBlock / lpr) * kUnroll;
   int64_t grid = ctr_ceil_div(items, per_block);
-#ifndef CTR_FAST_GRID
-#define CTR_FAST_GRID (256 * 32)
-#endif
-  if (grid > CTR_FAST_GRID) grid = CTR_FAST_GRID;
+  if (grid > kMaxGrid) grid = kMaxGrid;
   hipLaunchKernelGGL(embed_ids_fast_kernel<kUnroll>, dim3((unsigned)grid), dim3(kBlock), 0, st, T, n, lpr, w, f[0].idx,
                      items, out, ldo, err_flag, ctr_fastdiv((uint32_t)n));
   *rc = ctr_launch_status();
@@ -595,27 +579,21 @@ bool try_fast_ids_bwd(const ctr_field_t* f, int n, int64_t batch, const float* g
   bool small_vocab = true;
   for (int i = 0; i < n; ++i) small_vocab = small_vocab && f[i].vocab < (1 << 24);
   if (hot_mode && small_vocab && n <= 255 && w <= 32 && items >= 512u * 1024u) {
-    static const int hot_wgs = [] { const char* e = getenv("CTR_EMBED_HOT_WGS"); return e ? atoi(e) : 256; }();
-    static const int hot_slots = [] { const char* e = getenv("CTR_EMBED_HOT_SLOTS"); return e ? atoi(e) : 11; }();
-    static const int hot_threads = [] { const char* e = getenv("CTR_EMBED_HOT_THREADS"); return e ? atoi(e) : 1024; }();
-    const uint32_t per = (uint32_t)ctr_ceil_div(items, hot_wgs);
+    constexpr int kHotWgs = 256;
+    const uint32_t per = (uint32_t)ctr_ceil_div(items, kHotWgs);
     const unsigned grid = (unsigned)ctr_ceil_div(items, per);
-#define CTR_HOT_LAUNCH(L)                                                                                              \
-  do {                                                                                                                 \
-    const size_t lds = ((size_t)1 << L) * w * sizeof(float);                                                           \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(embed_ids_hot_bwd_kernel<L>),                                \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {                     \
-      *rc = CTR_ELAUNCH;                                                                                               \
-      return true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL(embed_ids_hot_bwd_kernel<L>, dim3(grid), dim3(hot_threads), lds, st, G, n, wshift, f[0].idx, items,  \
-                       gout, ldo, ctr_fastdiv((uint32_t)n), per);                                                      \
-  } while (0)
-    if (hot_slots == 9 || ((size_t)2048 * w * sizeof(float) > 140 * 1024 && hot_slots > 9)) CTR_HOT_LAUNCH(9);
-    else if (hot_slots == 10) CTR_HOT_LAUNCH(10);
-    else CTR_HOT_LAUNCH(11);
-#undef CTR_HOT_LAUNCH
-    *rc = ctr_launch_status();
+    // 2^11 accumulator rows, or 2^9 where those would take more than 140 KiB of LDS (width 32)
+    auto launch = [&](auto kernel, int slots_log2) {
+      const size_t lds = ((size_t)1 << slots_log2) * w * sizeof(float);
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds) != hipSuccess)
+        return CTR_ELAUNCH;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), lds, st, G, n, wshift, f[0].idx, items, gout, ldo,
+                         ctr_fastdiv((uint32_t)n), per);
+      return ctr_launch_status();
+    };
+    *rc = (size_t)2048 * w * sizeof(float) > 140 * 1024 ? launch(embed_ids_hot_bwd_kernel<9>, 9)
+                                                        : launch(embed_ids_hot_bwd_kernel<11>, 11);
     return true;
   }
   const int grid = ctr_stream_grid((int64_t)items * w, kBlock);

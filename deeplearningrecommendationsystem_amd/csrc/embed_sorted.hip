@@ -149,10 +149,6 @@ __global__ void __launch_bounds__(kBlock) sort_scatter_kernel(const SortJobs J, 
 }
 
 __device__ __forceinline__ void flush_run(float* grad, int row, int width, int c, const float4& acc) {
-#ifdef CTR_SEG_NOATOMIC
-  if (acc.x == 1234.5f) grad[0] = acc.y;
-  return;
-#endif
   float* p = grad + (int64_t)row * width + c;
   ctr_atomic_add_global(p + 0, acc.x);
   ctr_atomic_add_global(p + 1, acc.y);

@@ -119,9 +119,6 @@ __device__ __forceinline__ f32x4 lds_read128(uint32_t byte_addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
   return v;
 }
-__device__ __forceinline__ uint32_t lds_addr(const float* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
 // byte offset inside a stage of the two 16-byte chunks (kk = 8h .. 8h+3, 8h+4 .. 8h+7) of tile row `row`
 __device__ __forceinline__ void frag_offsets(int row, int h, uint32_t (&off)[2]) {
   const int sw = (row >> 1) & 3;
@@ -242,8 +239,8 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
       int refill = stage + 2;
       refill = refill >= kStages ? refill - kStages : refill;
       f32x4 fa[2], fb[NT][2];
-      const uint32_t abase = lds_addr(s_a[0]) + (uint32_t)stage * (kBM * kBK * 4);
-      const uint32_t bbase = lds_addr(s_b[0]) + (uint32_t)stage * (BN * kBK * 4);
+      const uint32_t abase = ctr_lds_addr(s_a[0]) + (uint32_t)stage * (kBM * kBK * 4);
+      const uint32_t bbase = ctr_lds_addr(s_b[0]) + (uint32_t)stage * (BN * kBK * 4);
 #pragma unroll
       for (int v = 0; v < 2; ++v) fa[v] = lds_read128(abase + aoff[v]);
 #pragma unroll

@@ -41,17 +41,6 @@ __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
 }
 
-// one wave instruction: lane L's 16 bytes land at lds_base + 16 L
-// (m0 is a reserved register: the compiler only sets it right in front of an instruction that reads it,
-// never keeps a value there, and rejects it as a clobber)
-__device__ __forceinline__ void dma16(const float* g, uint32_t lds_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds_base) : "memory");
-}
-
-__device__ __forceinline__ uint32_t lds_addr(const float* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
-
 // copy rows [row0, row0+16) x columns [col0, col0+W) of a row-major matrix into a [16][W] stage
 template <int W>
 __device__ __forceinline__ void fetch(float* stage, const float* __restrict__ src, int64_t ld, int64_t row0,
@@ -70,7 +59,7 @@ __device__ __forceinline__ void fetch(float* stage, const float* __restrict__ sr
     // the end: no load leaves the matrix, the reader adds the shift (tail_shift), the rest is dropped
     int col = col0 + cc * 4;
     col = col < cols_total - 4 ? col : cols_total - 4;
-    dma16(src + gr * ld + col, __builtin_amdgcn_readfirstlane(lds_addr(stage + q0 * 4)));
+    ctr_dma16(src + gr * ld + col, __builtin_amdgcn_readfirstlane(ctr_lds_addr(stage + q0 * 4)));
   }
 }
 

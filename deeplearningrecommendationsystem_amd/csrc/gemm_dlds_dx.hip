@@ -46,16 +46,6 @@ __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
 }
 
-// (m0 is a reserved register: the compiler only sets it right in front of an instruction that reads it,
-// never keeps a value there, and rejects it as a clobber)
-__device__ __forceinline__ void dma16(const float* g, uint32_t lds_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds_base) : "memory");
-}
-
-__device__ __forceinline__ uint32_t lds_addr(const float* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
-
 // [128 rows][16 units] tile, slot q (16 B) = row q/4, unit chunk (q & 3) ^ ((row >> 1) & 3)
 __device__ __forceinline__ void fetch_rows(float* stage, const float* __restrict__ src, int64_t ld, int64_t row0,
                                            int64_t rows_total, int u0, int u_total, int lane, int wave) {
@@ -68,7 +58,7 @@ __device__ __forceinline__ void fetch_rows(float* stage, const float* __restrict
     gr = gr < rows_total ? gr : rows_total - 1;
     int u = u0 + c * 4;
     u = u < u_total - 4 ? u : u_total - 4;
-    dma16(src + gr * ld + u, __builtin_amdgcn_readfirstlane(lds_addr(stage + q0 * 4)));
+    ctr_dma16(src + gr * ld + u, __builtin_amdgcn_readfirstlane(ctr_lds_addr(stage + q0 * 4)));
   }
 }
 
@@ -96,7 +86,7 @@ __device__ __forceinline__ void fetch_w(float* stage, const float* __restrict__ 
     // (fetch_rows: chunks crossing n start at n-4)
     int u = u0 + (row & ~3);
     u = (u < u_total - 4 ? u : u_total - 4) + (row & 3);
-    dma16(w + (int64_t)u * ldw + col, __builtin_amdgcn_readfirstlane(lds_addr(stage + q0 * 4)));
+    ctr_dma16(w + (int64_t)u * ldw + col, __builtin_amdgcn_readfirstlane(ctr_lds_addr(stage + q0 * 4)));
   }
 }
 

@@ -44,9 +44,6 @@ __device__ __forceinline__ f32x4 lds_read128(uint32_t byte_addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
   return v;
 }
-__device__ __forceinline__ uint32_t lds_addr(const float* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
 
 __global__ void __launch_bounds__(kThreads, 1)
 gemm_wide_fwd_kernel(const WideArgs a) {
@@ -94,7 +91,7 @@ gemm_wide_fwd_kernel(const WideArgs a) {
       boff[i][v] = (uint32_t)(kTM * kBK * 4) + (uint32_t)(rb * 4 + ((2 * h + v) ^ ((rb >> 1) & 3))) * 16u;
     }
   }
-  const uint32_t base0 = lds_addr(lds);
+  const uint32_t base0 = ctr_lds_addr(lds);
 
   // a workgroup walks the column tiles of ITS row tiles back to back: the 256 x k operand rows are then re-read from this
   // XCD's L2 (neighbouring workgroups sit on different XCDs: splitting a row tile's columns over them fetched X from

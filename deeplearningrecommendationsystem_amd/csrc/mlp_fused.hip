@@ -774,14 +774,6 @@ mlp_bwd_kernel(const StackDesc dk, const float* __restrict__ x, int64_t ldx, int
                const HeadBwdDesc hb) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ StackDesc s_desc;  // see mlp_fwd_kernel
-#ifdef CTR_MLP_TIMING
-  uint64_t stamps[16];
-  int nstamp = 0;
-#define CTR_STAMP() do { if (nstamp < 16) stamps[nstamp++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define CTR_STAMP() do {} while (0)
-#endif
-  CTR_STAMP();
   for (int i = threadIdx.x; i < (int)(sizeof(StackDesc) / 4); i += blockDim.x)
     reinterpret_cast<uint32_t*>(&s_desc)[i] = reinterpret_cast<const uint32_t*>(&dk)[i];
   __syncthreads();
@@ -799,7 +791,6 @@ mlp_bwd_kernel(const StackDesc dk, const float* __restrict__ x, int64_t ldx, int
   float* tq = tp + 32 * sa;
   stage_weights(s_w, d, false);
   __syncthreads();
-  CTR_STAMP();
 
   floatx16 dw[MAXT];  // dW accumulator tiles of every layer, alive across all row tiles
 #pragma unroll
@@ -981,7 +972,6 @@ mlp_bwd_kernel(const StackDesc dk, const float* __restrict__ x, int64_t ldx, int
         __builtin_amdgcn_wave_barrier();
         // (bias gradient: taken from the gZ fragments of the dW products below -- a column's 32 values are the 16
         // of each half-wave's fragment -- instead of 32 more LDS reads per column)
-        CTR_STAMP();
         // dW_l[n][k] += sum_rows gZ[row][n] X[row][k]: contraction = the 32 rows, 16 steps.
         // The accumulator index must be a compile-time constant (a run-time index would
         // send the tiles to scratch), so walk every slot and take this layer's ones.
@@ -1055,7 +1045,6 @@ mlp_bwd_kernel(const StackDesc dk, const float* __restrict__ x, int64_t ldx, int
           }
         }
         __builtin_amdgcn_wave_barrier();
-        CTR_STAMP();
         // dX_l = gZ W_l (32 x k): over X_l in LDS (the next layer's gY) or, for layer 0, to HBM
         {
           const float* wl = s_w + L.w_off;
@@ -1118,9 +1107,7 @@ mlp_bwd_kernel(const StackDesc dk, const float* __restrict__ x, int64_t ldx, int
     } else {
       for (int lq = 0; lq < nlayers; ++lq) layer(lq);
     }
-    CTR_STAMP();
   }
-  CTR_STAMP();
 
   // workgroup partial of dW / db -> one slab in the workspace.  No LDS atomics: ds_add_f32
   // from 4 waves ran at ~200 cycles per wave-instruction here (100K cycles for the 128x64
@@ -1209,15 +1196,15 @@ mlp_bwd_kernel(const StackDesc dk, const float* __restrict__ x, int64_t ldx, int
       ws[(int64_t)blockIdx.x * slab + off + i] = v;
     }
   }
-  CTR_STAMP();
-#ifdef CTR_MLP_TIMING
-  if (threadIdx.x == 0)
-    for (int i = 0; i < 16; ++i)
-      ws[(int64_t)gridDim.x * slab + blockIdx.x * 16 + i] = i < nstamp ? (float)(stamps[i] - stamps[0]) : -1.0f;
-#endif
 }
 
 // ------------------------------------------------------------------ host
+// CTR_MLP_16=0 keeps the tile-walking kernels of this file in place of mlp_mfma16.hip's, for A/B
+bool mlp16_enabled() {
+  static const bool on = [] { const char* e = getenv("CTR_MLP_16"); return !(e && e[0] == '0'); }();
+  return on;
+}
+
 struct Built {
   StackDesc d;
   size_t lds_bytes;
@@ -1351,8 +1338,7 @@ static int mlp_fwd_impl(const float* x, int64_t ldx, int64_t m, const ctr_mlp_la
     if (matches<NcfTowerShape, false>(layers, nlayers, b.d)) {
       // activations in matrix-core operand layout, sixteen samples per wave (mlp_mfma16.hip); CTR_MLP_16=0 keeps
       // the tile-walking kernels below
-      static const bool m16 = [] { const char* e = getenv("CTR_MLP_16"); return !(e && e[0] == '0'); }();
-      if (m16) {
+      if (mlp16_enabled()) {
         rc = ctr_ncf16_fwd(x, ldx, m, layers, head, st);
         if (rc != CTR_ELIMIT) return rc;
       }
@@ -1424,8 +1410,7 @@ extern "C" int ctr_embed_mlp_head_fwd(const ctr_field_t* fields, int nfields, in
   if (batch == 0) return CTR_OK;
   CTR_REQUIRE(head->w && head->c && head->out && head->ldout >= 1, CTR_EINVAL);
   CTR_REQUIRE(head->act >= CTR_ACT_NONE && head->act <= CTR_ACT_SIGMOID, CTR_EINVAL);
-  static const bool m16 = [] { const char* e = getenv("CTR_MLP_16"); return !(e && e[0] == '0'); }();
-  if (!m16 || nlayers != 4 || batch < 1024 || !ctr_aligned16(out) || ldo % 4 != 0) return CTR_ELIMIT;
+  if (!mlp16_enabled() || nlayers != 4 || batch < 1024 || !ctr_aligned16(out) || ldo % 4 != 0) return CTR_ELIMIT;
   for (int l = 0; l < nlayers; ++l)
     if (!layers[l].w || !layers[l].y || !ctr_aligned16(layers[l].w)) return CTR_ELIMIT;
   return ctr_ncf16_gather_fwd(fields, nfields, batch, out, ldo, err_flag, write_x, layers, head, fold, (hipStream_t)stream);
@@ -1517,9 +1502,8 @@ static int mlp_head_bwd_impl(const ctr_field_t* fields, int nfields, const float
   hipStream_t st = (hipStream_t)stream;
   // activations and gradients in matrix-core operand layout, sixteen samples per wave (mlp_mfma16.hip; same slab
   // layout); CTR_MLP_16=0 keeps the tile-walking kernels below
-  static const bool m16 = [] { const char* e = getenv("CTR_MLP_16"); return !(e && e[0] == '0'); }();
   bool done16 = false;
-  if (m16 && gx && slab == ctr_ncf16_slab_floats()) {
+  if (mlp16_enabled() && gx && slab == ctr_ncf16_slab_floats()) {
     int g16 = 0;
     rc = fields ? ctr_ncf16_gather_bwd(fields, nfields, m, layers, hg, gx, ldgx, workspace, workspace_floats, &g16, zero_buf,
                                        zero_floats, st)

@@ -293,9 +293,6 @@ ncf16_bwd_kernel(const Tower T, const float* __restrict__ x, int64_t ldx, int64_
   uint32_t uo[4] = {0, 0, 0, 0}, io[4] = {0, 0, 0, 0};
   bool rlive = false;
   auto rows_for = [&](int64_t g) {
-#ifdef CTR_STAMPS_HOT
-    g &= 63;   // timing experiment: every wave reads cache-resident rows (results are wrong)
-#endif
     const int64_t row = g * 16 + lo;
     rlive = g < groups && row < m;
     rc = (uint32_t)(rlive ? row : (m - 1));

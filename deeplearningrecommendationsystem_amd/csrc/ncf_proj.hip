@@ -179,7 +179,8 @@ struct Fwd {
 };
 
 // How the loops of this file are written (what the first version got wrong, found with cycle stamps, an ablation and
-// the TA / TCP counters: dev/r03_ablate.sh, dev/ncfp_stamps.py, profiles/r03_ncfp_*):
+// the TA / TCP counters: dev/ncfp_stamps.py, profiles/r03_ncfp_*; the ablation's kernel variants and their script were
+// retired and are in git history):
 //  * hipcc puts a `s_waitcnt vmcnt(0)` INSIDE every conditional block that consumes a load (`live ? a[i] + b[i] : 0`
 //    becomes a branch around two loads, their wait and the add): a fetch written that way is a chain of round trips.
 //    Every load here is unconditional (rows past the batch are clamped), every store too (lanes without a sample write
@@ -200,18 +201,9 @@ struct Fwd {
 //   [kDma row fetches] [2 id loads] [kStores stores]
 // so `vmcnt(kStores)` at the head of the next group means: its rows are staged and its successor's ids are here, while
 // this group's stores may still be on their way.
-__device__ __forceinline__ void dma16(const float* g, uint32_t lds_base) {
-  // (m0 is a reserved register: the compiler only sets it right in front of an instruction that reads it)
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds_base) : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr(const float* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
 constexpr int kFwdStage = 4 * 16 * 64;   // floats per wave: P_U, P_I, GMF_U, GMF_I rows of sixteen samples
 constexpr int kFwdStores = 5;            // y1 x 2, y2, y3, prob
 
-// DBG != 0: timing experiments (dev/r03_ablate.sh; results are wrong): 2 no layers, 4 no y stores, 16 no prob store, 32 no row fetch
-template <int DBG>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   if ((int)blockIdx.x >= F.rank.first) {
@@ -225,7 +217,7 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   const int lane = threadIdx.x & 63, q = lane >> 4, n = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* stage = s_hw + 80 + wave * kFwdStage;        // this wave's rows: [table][row][chunk ^ row] x 16 bytes
-  const uint32_t stage_addr = lds_addr(stage);
+  const uint32_t stage_addr = ctr_lds_addr(stage);
   const int64_t groups = (m + 15) / 16;
   const int64_t wave0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6, nwaves = ((int64_t)F.rank.first * kThreads) >> 6;
   const uint32_t nu = (uint32_t)F.ids.nu, ni = (uint32_t)F.ids.ni;
@@ -235,13 +227,8 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   auto issue_ids = [&](int64_t g) {
     int64_t row = g * 16 + n;
     row = row < m ? row : m - 1;
-    if constexpr (DBG & 8) {
-      idu = (row * 7) % F.ids.nu;
-      idi = (row * 13) % F.ids.ni;
-    } else {
-      idu = F.ids.uidx[row * F.ids.ustride];
-      idi = F.ids.iidx[row * F.ids.istride];
-    }
+    idu = F.ids.uidx[row * F.ids.ustride];
+    idi = F.ids.iidx[row * F.ids.istride];
   };
   // stage 2: the four rows of every sample of the group by LDS-DMA.  Instruction k of a table moves
   // rows 4k .. 4k+3: lane l fetches chunk (l % 16) ^ row of row 4k + l / 16 into slot (row, l % 16).
@@ -259,8 +246,7 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const float* g_ = tabs[t] + ((t & 1) ? ir : ur) * 64u + col;
-        if constexpr (DBG & 32) asm volatile("" ::"v"(g_));
-        else dma16(g_, stage_addr + (uint32_t)((t * 16 + 4 * k) * 256));
+        ctr_dma16(g_, stage_addr + (uint32_t)((t * 16 + 4 * k) * 256));
       }
     }
   };
@@ -315,20 +301,14 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
     issue_ids(g + 2 * nwaves);
     STAMP(0, stamp++);
     f32x4 y1[2], y2[1], y3[1];
-    if constexpr (DBG & 2) {
-      y1[0] = a0[0] + a0[2]; y1[1] = a0[1] + a0[3]; y2[0] = y1[0] * y1[1]; y3[0] = y2[0] + y1[0];
-    } else {
-      layer_fwd<0, 4>(s_w, s_b, lane, q, a0, y1);
-      layer_fwd<1, 2>(s_w, s_b, lane, q, y1, y2);
-      layer_fwd<2, 1>(s_w, s_b, lane, q, y2, y3);
-    }
+    layer_fwd<0, 4>(s_w, s_b, lane, q, a0, y1);
+    layer_fwd<1, 2>(s_w, s_b, lane, q, y1, y2);
+    layer_fwd<2, 1>(s_w, s_b, lane, q, y2, y3);
     STAMP(0, stamp++);
-    if constexpr (!(DBG & 4)) {
 #pragma unroll
-      for (int b = 0; b < 2; ++b) stg4(T.y[0] + srow * T.ldy[0] + 16 * b + 4 * q, y1[b]);
-      stg4(T.y[1] + srow * T.ldy[1] + 4 * q, y2[0]);
-      stg4(T.y[2] + (q < 2 ? srow : m) * T.ldy[2] + 4 * (q & 1), y3[0]);
-    }
+    for (int b = 0; b < 2; ++b) stg4(T.y[0] + srow * T.ldy[0] + 16 * b + 4 * q, y1[b]);
+    stg4(T.y[1] + srow * T.ldy[1] + 4 * q, y2[0]);
+    stg4(T.y[2] + (q < 2 ? srow : m) * T.ldy[2] + 4 * (q & 1), y3[0]);
     // head: prob = act([gmf | h] . wfold + cfold); the four lanes of a sample hold 16 + (q < 2 ? 4 : 0) terms each
     float dot = 0.0f;
 #pragma unroll
@@ -345,11 +325,10 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
     }
     dot += __shfl_xor(dot, 16, 64);
     dot += __shfl_xor(dot, 32, 64);
-    if constexpr (!(DBG & 16)) F.out[srow * F.ldout] = ctr_act(dot + hc, F.act);   // (the four lanes of a sample agree)
-    else asm volatile("" ::"v"(dot));
+    F.out[srow * F.ldout] = ctr_act(dot + hc, F.act);   // (the four lanes of a sample agree)
     STAMP(0, stamp++);
     // the next group's rows and its successor's ids are older than this group's kFwdStores stores
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DBG & 4) ? ((DBG & 16) ? 0 : 1) : kFwdStores) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kFwdStores) : "memory");
     asm volatile("" : "+v"(idu), "+v"(idi));
   }
 }
@@ -421,7 +400,7 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   float* tA = lds + kWFloats + wave * kStripP;
   float* tB = tA + 2 * kTile;
   float* stage = lds + kWFloats + kWaves * kStripP + wave * kBwdStage;
-  const uint32_t stage_addr = lds_addr(stage);
+  const uint32_t stage_addr = ctr_lds_addr(stage);
   const int64_t nrows = B.ids.nu + B.ids.ni;
   int* s_off = reinterpret_cast<int*>(lds + kWFloats + kWaves * (kStripP + kBwdStage));   // nrows + 1 exclusive offsets
   const int64_t groups = (m + 15) / 16;
@@ -470,8 +449,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
       const int src = (lane & 48) | row;                   // a lane of this quarter that holds sample row's ids
       const uint32_t ur = (uint32_t)__shfl((int)r.u, src, 64), ir = (uint32_t)__shfl((int)r.i, src, 64);
       const uint32_t col = 4u * (uint32_t)(lo ^ row);
-      dma16(pu + ur * 64u + col, stage_addr + (uint32_t)((kSgPU + 4 * k * 64) * 4));
-      dma16(pi + ir * 64u + col, stage_addr + (uint32_t)((kSgPI + 4 * k * 64) * 4));
+      ctr_dma16(pu + ur * 64u + col, stage_addr + (uint32_t)((kSgPU + 4 * k * 64) * 4));
+      ctr_dma16(pi + ir * 64u + col, stage_addr + (uint32_t)((kSgPI + 4 * k * 64) * 4));
     }
     {
       // Y1 (32 floats a row): instruction k moves rows 8k .. 8k+7, lane l chunk (l % 8) ^ sw1(row) of row 8k + l / 8
@@ -481,19 +460,19 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
         const int row = 8 * k + (lane >> 3);
         int64_t gr = g16 + row;
         gr = gr < m ? gr : m - 1;
-        dma16(T.y[0] + gr * T.ldy[0] + 4 * ((lane & 7) ^ sw1(row)), stage_addr + (uint32_t)((kSgY1 + 8 * k * 32) * 4));
+        ctr_dma16(T.y[0] + gr * T.ldy[0] + 4 * ((lane & 7) ^ sw1(row)), stage_addr + (uint32_t)((kSgY1 + 8 * k * 32) * 4));
       }
       {   // Y2 (16 floats): lane l chunk (l % 4) ^ sw2(row) of row l / 4
         const int row = lane >> 2;
         int64_t gr = g16 + row;
         gr = gr < m ? gr : m - 1;
-        dma16(T.y[1] + gr * T.ldy[1] + 4 * ((lane & 3) ^ sw2(row)), stage_addr + (uint32_t)(kSgY2 * 4));
+        ctr_dma16(T.y[1] + gr * T.ldy[1] + 4 * ((lane & 3) ^ sw2(row)), stage_addr + (uint32_t)(kSgY2 * 4));
       }
       {   // Y3 (8 floats): lane l chunk (l % 2) ^ sw3(row) of row (l / 2) % 16 (the upper half-wave repeats the lower)
         const int row = (lane >> 1) & 15;
         int64_t gr = g16 + row;
         gr = gr < m ? gr : m - 1;
-        dma16(T.y[2] + gr * T.ldy[2] + 4 * ((lane & 1) ^ sw3(row)), stage_addr + (uint32_t)(kSgY3 * 4));
+        ctr_dma16(T.y[2] + gr * T.ldy[2] + 4 * ((lane & 1) ^ sw3(row)), stage_addr + (uint32_t)(kSgY3 * 4));
       }
     }
     r.gp = B.gprob[rc * B.ldgp];
@@ -1152,11 +1131,18 @@ extern "C" __attribute__((visibility("default"))) int ctr_ncfp_debug_stamps(unsi
 }
 #endif
 
+// launch geometry (the round-3 sweeps that chose these values are in git history)
+constexpr int kRankSplit = 50;      // per cent of a training batch whose ranks the projection launch takes
+constexpr int kFwdWgs = 256;        // per-sample workgroups of the forward, at most
+constexpr int kBwdWgs = 256;        // per-sample workgroups of the backward, at most: one slab each
+constexpr int kSlabsMax = 768;      // workspace_floats() reserves slabs for this many backward workgroups
+static_assert(kBwdWgs <= kSlabsMax, "the backward's slabs must fit the workspace");
+
 static int64_t workspace_floats(int64_t batch, int64_t num_users, int64_t num_items) {
   const int64_t rows = num_users + num_items;
   const int64_t groups = ctr_ceil_div(batch > 0 ? batch : 1, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
-  if (grid > 768) grid = 768;
+  if (grid > kSlabsMax) grid = kSlabsMax;
   // buckets (2B + 1, 64) | slot records (2B + 1, 4) | segment sums (rows, 128) | offsets (rows + 1) | slabs
   // (the spare slot 2B takes the stores of samples without a slot: bad ids, the padding lanes of the last group)
   return (2 * batch + 1) * kN0 + (2 * batch + 1) * 4 + rows * 128 + (rows + 1 + 3) / 4 * 4 + grid * (int64_t)kSlab;
@@ -1186,8 +1172,7 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   const int64_t pwaves = ctr_ceil_div(nu, 16) + ctr_ceil_div(ni, 16);
   const Ids ids{d->user_idx, d->user_stride, d->item_idx, d->item_stride, nu, ni};
   // training: the samples' ranks, part in this launch, part in the next (RankJob)
-  static const int rank_split = [] { const char* e = getenv("CTR_NCFP_RANK_SPLIT"); return e ? atoi(e) : 50; }();   // per cent (sweep: dev/r03_rank_split.sh)
-  const int64_t m_first = d->training ? d->batch * rank_split / 100 / kThreads * kThreads : 0;
+  const int64_t m_first = d->training ? d->batch * kRankSplit / 100 / kThreads * kThreads : 0;
   const int proj_blocks = (int)ctr_ceil_div(pwaves, kWaves) + 1;
   int64_t rank_a = ctr_ceil_div(m_first, kThreads);
   if (rank_a > 256) rank_a = 256;
@@ -1200,27 +1185,17 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   const int64_t groups = ctr_ceil_div(d->batch, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
   // one workgroup per CU, every wave walks several groups: 25.6 us at batch 65536 against 28 us with two per CU
-  static const int fwd_wgs = [] { const char* e = getenv("CTR_NCFP_FWD_WGS"); return e ? atoi(e) : 256; }();
-  if (grid > fwd_wgs) grid = fwd_wgs;
+  if (grid > kFwdWgs) grid = kFwdWgs;
   // rank workgroups (training): one sample per thread up to a chip's worth of them, behind the per-sample ones
   int64_t rank_blocks = d->training ? ctr_ceil_div(d->batch - m_first, kThreads) : 0;
   if (rank_blocks > 256) rank_blocks = 256;
   const Fwd F{ids, d->ptab, d->gmf_user, d->gmf_item, d->wfold, d->prob, d->ldprob, d->head_act, d->err_flag,
               RankJob{ids, d->counts, d->ranks, m_first, d->training ? d->batch : m_first, (int)grid}};
-  static const int dbg = [] { const char* e = getenv("CTR_NCFP_DBG"); return e ? atoi(e) : 0; }();
   constexpr size_t fwd_lds = sizeof(float) * (kWFloats + kBFloats + 80 + kWaves * kFwdStage);
-  switch (dbg) {
-#define CTR_DBG_CASE(V)                                                                                                  \
-  case V:                                                                                                                \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_fwd_kernel<V>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            (int)fwd_lds) != hipSuccess)                                                                 \
-      return CTR_ELAUNCH;                                                                                                \
-    hipLaunchKernelGGL(ncfp_fwd_kernel<V>, dim3((unsigned)(grid + rank_blocks)), dim3(kThreads), fwd_lds, st, T, d->batch, F); \
-    break
-    CTR_DBG_CASE(54); CTR_DBG_CASE(62); CTR_DBG_CASE(8);
-    default: CTR_DBG_CASE(0);
-#undef CTR_DBG_CASE
-  }
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)fwd_lds) != hipSuccess)
+    return CTR_ELAUNCH;
+  hipLaunchKernelGGL(ncfp_fwd_kernel, dim3((unsigned)(grid + rank_blocks)), dim3(kThreads), fwd_lds, st, T, d->batch, F);
   return ctr_launch_status();
 }
 
@@ -1246,8 +1221,7 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   float* slabs = ws;
   const int64_t groups = ctr_ceil_div(m, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
-  static const int bwd_wgs = [] { const char* e = getenv("CTR_NCFP_BWD_WGS"); return e ? atoi(e) : 256; }();
-  if (grid > bwd_wgs) grid = bwd_wgs;
+  if (grid > kBwdWgs) grid = kBwdWgs;
   const Ids ids{d->user_idx, d->user_stride, d->item_idx, d->item_stride, nu, ni};
   const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, g->gprob, g->ldgprob, d->head_act, d->counts, d->ranks, gzb, aux,
               offs, slabs, stt, rows * 128, g->zero_buf, g->zero_buf ? g->zero_floats : 0};
@@ -1269,12 +1243,6 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   for (int l = 0; l < kL; ++l) {
     S.gw[l] = g->layers[l + 1].gw;
     S.gb[l] = g->layers[l + 1].gb;
-  }
-  {
-    // timing experiments (results are wrong): CTR_NCFP_SEG_DBG bit 0 drops the segment-sum workgroups, bit 1 the slab ones
-    static const int sdbg = [] { const char* e = getenv("CTR_NCFP_SEG_DBG"); return e ? atoi(e) : 0; }();
-    if (sdbg & 1) S.seg_blocks = 0;
-    if (sdbg & 2) S.red_blocks = 0;
   }
   if (phases & 2)
     hipLaunchKernelGGL(ncfp_segsum_kernel, dim3((unsigned)(S.seg_blocks + S.red_blocks + 1)), dim3(kThreads), 0, st, S);

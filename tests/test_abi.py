@@ -108,6 +108,34 @@ def test_product_never_imports_the_oracle():
                 assert "oracle" not in src.replace("no oracle", ""), f"{f} mentions the oracle"
 
 
+def test_every_environment_switch_is_documented():
+    """every variable the kernels or the package read is a row of dev/README.md's switch table, so tunables and
+    ablations cannot come back into the product build unnoticed"""
+    pkg = os.path.join(ROOT, "deeplearningrecommendationsystem_amd")
+    read = {}
+    csrc = os.path.join(pkg, "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h", ".inc")):
+            for name in re.findall(r'\bgetenv\(\s*"([A-Za-z0-9_]+)"\s*\)', open(os.path.join(csrc, f)).read()):
+                read.setdefault(name, f)
+    py_read = re.compile(r"""os\.(?:environ\.get\(|environ\[|getenv\()\s*["']([A-Za-z0-9_]+)["']""")
+    for base, _, files in os.walk(pkg):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                for name in py_read.findall(open(os.path.join(base, f)).read()):
+                    read.setdefault(name, os.path.relpath(os.path.join(base, f), ROOT))
+    assert {"CTR_MLP_16", "CTR_EMBED_HOT", "CTR_NCF_PROJ", "CTRHIP_LIB"} <= set(read), sorted(read)
+    doc = open(os.path.join(ROOT, "dev", "README.md")).read()
+    table = doc[doc.index("## A/B switches"):]
+    table = table[:table.index("\n## ")] if "\n## " in table else table
+    documented = set()
+    for line in table.splitlines():
+        if line.startswith("| `"):
+            documented.update(re.findall(r"`([A-Za-z0-9_]+)`", line.split("|")[1]))
+    missing = {name: where for name, where in read.items() if name not in documented}
+    assert not missing, f"environment switches missing from dev/README.md's switch table: {missing}"
+
+
 def _parse_header_prototypes():
     """{name: (ret, [arg ctypes])} derived from the declarations in include/ctrhip.h"""
     text = open(os.path.join(ROOT, "include", "ctrhip.h")).read()

@@ -102,12 +102,14 @@ def test_embedding_stage_26_fields_1e6_rows_batch_65536():
         _check_scatter(stage.tables[f].grad, idx[:, f], gout[:, f * dim:(f + 1) * dim], dim, [0, vocab - 1])
 
 
-def test_embedding_stage_scatter_under_a_zipf_law_hot_rows_summed_in_lds():
+@pytest.mark.parametrize("dim", [16, 32])
+def test_embedding_stage_scatter_under_a_zipf_law_hot_rows_summed_in_lds(dim):
     """the cfg3b scatter with Zipf ids (rank r with P(rank <= r) = log r / log V): the rows a workgroup hits repeatedly
     are summed in an LDS cache before they reach the table gradient (embed_ids_hot_bwd_kernel) -- every row against
-    fp64 sums built on the host, for the hottest rows (thousands of contributions) and for rows hit once"""
+    fp64 sums built on the host, for the hottest rows (thousands of contributions) and for rows hit once.  Width 16
+    takes the cache of 2^11 rows, width 32 the one of 2^9 (2^11 rows of 32 floats would not fit the LDS)"""
     from deeplearningrecommendationsystem_amd.model import EmbeddingStage
-    fields, vocab, dim, batch = 26, 1_000_000, 16, 65536
+    fields, vocab, batch = 26, 1_000_000, 65536
     with torch.device(DEV):
         stage = EmbeddingStage(fields, vocab, dim)
     gen = torch.Generator().manual_seed(27)
