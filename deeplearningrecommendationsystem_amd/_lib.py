@@ -15,13 +15,14 @@ import torch  # noqa: F401  (maps libamdhip64 first, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTRHIP_LIB", os.path.join(_HERE, "libctrhip.so"))  # env override: A/B builds
-ABI_VERSION = 35
+ABI_VERSION = 36
 DIN_TRIPLE, DIN_PAIR, DIN_H = 0, 1, 2  # layouts of the DIN attention operand (include/ctrhip.h)
 
 CTR_MAX_FIELDS = 32
 CTR_NCF_PROJ_MAX_ROWS = 16384
 CTR_NCF_PROJ_COUNT_STRIDE = 16
 CTR_ROWS1_MAX_ROWS = 32768
+CTR_GDCF_MAX_DIM = 256
 FIELD_ID_I64, FIELD_ID_F32, FIELD_BAG, FIELD_DENSE, FIELD_PROD_I64 = range(5)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = range(3)
 
@@ -179,6 +180,9 @@ SIGNATURES = {
     "ctr_cf_knn": (_i, [_p, _l, _l, _p, _l, _l, _i, _p, _p, _p]),
     "ctr_usercf_scores": (_i, [_p, _l, _l, _l, _p, _p, _i, _p, _l, _p, _l, _p]),
     "ctr_itemcf_scores": (_i, [_p, _l, _l, _l, _p, _p, _i, _p, _l, _p, _l, _p]),
+    "ctr_gdcf_workspace_bytes": (_i, [_l, _l, _i, C.POINTER(C.c_int64)]),
+    "ctr_gdcf_rows": (_i, [_p, _p, _l, _l, _i, _p, _l, _p, _p, _p, _l, _p]),
+    "ctr_gdcf_cols": (_i, [_p, _p, _l, _l, _i, _p, _l, _p, _p, _p]),
     "ctr_rank_filter": (_i, [_p, _l, _l, _l, _p, _p, _l, _p, _l, _p, _p, _p]),
     "ctr_rank_table_slots": (_i, [_l, _l, C.POINTER(C.c_int64)]),
     "ctr_rank_metrics_lists": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p]),

@@ -1362,6 +1362,69 @@ def itemcf_scores(x, num_items, nbr, nsim, users):
 
 
 # ---------------------------------------------------------------------------
+# GDCF: BCEWithLogits over the full implicit matrix (csrc/gdcf.hip); the m x n scores are never written
+# ---------------------------------------------------------------------------
+GDCF_MAX_DIM = _lib.CTR_GDCF_MAX_DIM
+
+
+def _gdcf_operands(p: torch.Tensor, q: torch.Tensor, y: torch.Tensor, y_rows: int, y_cols: int, what: str):
+    _lib.require_device(p, q, y)
+    for t, name in ((p, "P"), (q, "Q")):
+        if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"gdcf: {name} must be a contiguous 2-D float32 tensor, got {tuple(t.shape)} {t.dtype}")
+    if p.shape[1] != q.shape[1]:
+        raise ValueError(f"gdcf: P has {p.shape[1]} columns, Q {q.shape[1]}")
+    k = p.shape[1]
+    if not 1 <= k <= GDCF_MAX_DIM:
+        raise ValueError(f"gdcf: k = {k} outside [1, {GDCF_MAX_DIM}] (CTR_GDCF_MAX_DIM)")
+    if p.shape[0] < 1 or q.shape[0] < 1:
+        raise ValueError("gdcf: P and Q need at least one row")
+    if y.dim() != 2 or y.dtype != torch.int8 or not y.is_contiguous() or y.shape[0] != y_rows \
+            or y.shape[1] % 64 or y.shape[1] < y_cols:
+        raise ValueError(f"gdcf: {what} must be the contiguous ({y_rows}, pad64({y_cols})) int8 matrix, got "
+                         f"{tuple(y.shape)} {y.dtype}")
+    return k
+
+
+def gdcf_rows(p: torch.Tensor, q: torch.Tensor, y: torch.Tensor, grad: bool = True):
+    """row pass: (loss, dP) with loss a 0-dim float32 device tensor, the mean of softplus(s) - y s over the m x n
+    matrix, and dP = (sigmoid(S) - Y) Q / (m n); ``grad=False`` forms the scores only and returns (loss, None).
+    ``y`` is ImplicitMatrix.data, (m, cols_pad) int8, columns >= n ignored."""
+    m, n = p.shape[0], q.shape[0]
+    k = _gdcf_operands(p, q, y, m, n, "the interaction matrix")
+    lib = _lib.load()
+    ws = C.c_int64()
+    _lib.check(lib.ctr_gdcf_workspace_bytes(m, n, k, C.byref(ws)), "ctr_gdcf_workspace_bytes")
+    parts = torch.empty(ws.value // 8, dtype=torch.float64, device=p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    gp = torch.empty_like(p) if grad else None
+    rc = _timed("gdcf_rows" if grad else "gdcf_rows_loss",
+                lambda: (4 * (m * k + n * k) + m * y.shape[1] + (4 * m * k if grad else 0),
+                         (4 if grad else 2) * m * n * k),
+                lib.ctr_gdcf_rows, p.data_ptr(), q.data_ptr(), m, n, k, y.data_ptr(), y.shape[1], loss.data_ptr(),
+                _lib.ptr(gp), parts.data_ptr(), ws.value, _lib.stream_ptr())
+    _lib.check(rc, "ctr_gdcf_rows")
+    return loss, gp
+
+
+def gdcf_cols(p: torch.Tensor, q: torch.Tensor, yt: torch.Tensor, gout: torch.Tensor) -> torch.Tensor:
+    """column pass: dQ = gout * (sigmoid(S) - Y)^T P / (m n), ``gout`` the loss's upstream gradient (one float32 on
+    the device, read there: no host synchronisation).  ``yt`` is ImplicitMatrix.transposed(), (n, pad64(m)) int8."""
+    m, n = p.shape[0], q.shape[0]
+    k = _gdcf_operands(p, q, yt, n, m, "the transposed interaction matrix")
+    _lib.require_device(gout)
+    if gout.numel() != 1 or gout.dtype != torch.float32:
+        raise ValueError("gdcf: the upstream gradient must be one float32")
+    gout = gout.reshape(1).contiguous()
+    gq = torch.empty_like(q)
+    rc = _timed("gdcf_cols", lambda: (4 * (m * k + 2 * n * k) + n * yt.shape[1], 4 * m * n * k),
+                _lib.load().ctr_gdcf_cols, p.data_ptr(), q.data_ptr(), m, n, k, yt.data_ptr(), yt.shape[1],
+                gout.data_ptr(), gq.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_gdcf_cols")
+    return gq
+
+
+# ---------------------------------------------------------------------------
 # top-k ranking evaluation (csrc/rank_eval.hip); the CSRs are (offsets (rows + 1), ids) int64 device tensors, the
 # offsets already sliced to the rows of the call (they index ``ids`` absolutely)
 # ---------------------------------------------------------------------------

@@ -591,6 +591,28 @@ int ctr_itemcf_scores(const int8_t* x, int64_t num_users, int64_t cols_pad, int6
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * GDCF (GDCF_Final.py): matrix factorisation on the full implicit matrix.  BCEWithLogitsLoss, mean reduction, over
+ * all m x n entries of the 0/1 matrix Y (m = num_users, n = num_items) with scores S = P Q^T:
+ *   loss = sum_{u,i} (softplus(s_ui) - y_ui s_ui) / (m n),  G = sigmoid(S) - Y,  dP = G Q / (m n),  dQ = G^T P / (m n).
+ * p (m, k) and q (n, k) float32 row-major with leading dimension k; 1 <= k <= CTR_GDCF_MAX_DIM (CTR_ELIMIT beyond).
+ * The m x n scores are never written: two fused fp32 matrix-core passes, 1/(m n) evaluated in double, no atomics, so
+ * every output is bitwise reproducible.  Padding columns of the int8 matrices (>= num_items, resp. >= num_users) are
+ * excluded from the loss and the gradients.
+ *
+ * ctr_gdcf_rows (the forward): *loss (device float32) and, when grad_p is not NULL, grad_p (m, k) = dP.  y is the
+ * (m, ldy) int8 matrix, ldy % 64 == 0, ldy >= n, 16-byte aligned.  workspace: device memory of at least
+ * ctr_gdcf_workspace_bytes(m, n, k) bytes (float64 partials of the loss).
+ * ctr_gdcf_cols (the backward of q): grad_q (n, k) = gout[0] * dQ with gout a device float32 (the upstream gradient
+ * of the loss).  yt is the transposed (n, ldyt) int8 matrix, ldyt % 64 == 0, ldyt >= m, 16-byte aligned.
+ * ---------------------------------------------------------------------- */
+#define CTR_GDCF_MAX_DIM 256
+int ctr_gdcf_workspace_bytes(int64_t num_users, int64_t num_items, int k, int64_t* bytes /*host, out*/);
+int ctr_gdcf_rows(const float* p, const float* q, int64_t num_users, int64_t num_items, int k, const int8_t* y,
+                  int64_t ldy, float* loss, float* grad_p, void* workspace, int64_t workspace_bytes, void* stream);
+int ctr_gdcf_cols(const float* p, const float* q, int64_t num_users, int64_t num_items, int k, const int8_t* yt,
+                  int64_t ldyt, const float* gout, float* grad_q, void* stream);
+
+/* ------------------------------------------------------------------------
  * Top-k ranking evaluation (evaluator/ranking.py: Ranking, and data/reader.py:137-159: remove_itemid).
  *
  * Id sets are CSRs over `rows` users: off (rows + 1, absolute into ids, device), ids (nnz, ascending within a row,
