@@ -18,11 +18,13 @@ static inline int64_t ctr_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / 
 
 static inline bool ctr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// memory-bound grids: enough blocks to fill 256 CUs x 8, grid-stride the rest (guide G11)
+constexpr int kCtrCUs = 256;  // compute units of the MI355X
+
+// memory-bound grids: enough blocks to fill the CUs x 8, grid-stride the rest (guide G11)
 static inline int ctr_stream_grid(int64_t work_items, int per_block) {
   int64_t g = ctr_ceil_div(work_items, per_block);
   if (g < 1) g = 1;
-  if (g > 256 * 8) g = 256 * 8;
+  if (g > kCtrCUs * 8) g = kCtrCUs * 8;
   return (int)g;
 }
 

@@ -2,31 +2,22 @@
 // (global_load_lds_dwordx4, gfx950): no staging registers, no ds_write, and a THREE-stage LDS
 // ring, so the loads of pipeline slot g+2 are issued at step g and have two steps to land
 // (the register-staged tile kernel of linear.hip has one; PMC: 43 % of its wave time in vmcnt).
+// gemm_ring.h has the stage format, the ring and the tile policy.
 //
 // Tile 128 x (32*NT) per 256-thread workgroup, 16-deep steps, persistent over the M tiles like
-// linear.hip.  A direct load writes lane L's 16 bytes at M0 + 16*L: the LDS image of a wave's
-// instruction is one contiguous 1 KB run and cannot be padded, so bank conflicts are avoided by
-// choosing WHICH global chunk each lane fetches: slot q of a stage (16 B each, row = q/4) holds
-// k-chunk (q & 3) ^ ((row >> 1) & 3) of its row -- the 8 rows a quarter-wave reads with one
-// ds_read_b128 then cover all 32 banks.
-// The 16-byte direct loads only need 4-byte aligned addresses (measured: rows with an odd leading
-// dimension run at the same rate), so any X / W layout with K >= 4 is taken.  Rows past M / N are
-// clamped to the last row: their products are computed and dropped.  Contraction tail (K % 16 != 0):
-// a chunk that would cross the end of its row is fetched from K-4 instead, so no load ever leaves
-// the matrix; the X fragment zeroes the positions that are duplicates or past K, W is left as is
-// (finite, multiplied by zero).
-#include "ctr_common.h"
+// linear.hip; both operands are swizzled tiles read along the contraction.  Any X / W layout with
+// K >= 4 is taken (measured: rows with an odd leading dimension run at the same rate).  Products of
+// rows past M / N are computed and dropped.  Contraction tail (K % 16 != 0): the X fragment zeroes
+// the positions that are duplicates or past K, W is left as is (finite, multiplied by zero).
+#include "gemm_ring.h"
 
 #include <type_traits>
 
+using namespace gemm_ring;
+
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int kThreads = 256;
 constexpr int kBM = 128;
-constexpr int kBK = 16;
-constexpr int kStages = 3;
 
 struct DldsArgs {
   const float* x; int64_t ldx;
@@ -42,12 +33,6 @@ struct DldsArgs {
   const float* dot_w; const float* dot_b; float* dot_out; int64_t lddot;
 };
 
-// s_waitcnt vmcnt(N) only (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14)
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-
 // fetch one operand tile (ROWS x 16 floats) into a stage: chunk slot q = 64*wave + lane + 256*i
 template <int ROWS>
 __device__ __forceinline__ void fetch(float* stage, const float* __restrict__ src, int64_t ld, int64_t row0,
@@ -56,18 +41,11 @@ __device__ __forceinline__ void fetch(float* stage, const float* __restrict__ sr
   constexpr int kIters = (kChunks + kThreads - 1) / kThreads;
 #pragma unroll
   for (int i = 0; i < kIters; ++i) {
-    // first slot of this wave's instruction (uniform).  A tile of fewer chunks than threads is fetched twice
-    // (same bytes to the same slots): every wave then has the same number of loads in flight, which
-    // the vmcnt bookkeeping of the ring relies on
-    int q0 = 64 * wave + kThreads * i;
-    if (kChunks % kThreads != 0 && q0 >= kChunks) q0 -= kChunks;
+    const int q0 = wave_slot0<kChunks>(wave, i);
     const int q = q0 + lane;
-    const int row = q >> 2, c = (q & 3) ^ ((row >> 1) & 3);
-    int64_t gr = row0 + row;
+    int64_t gr = row0 + slot_row(q);
     gr = gr < rows_total ? gr : rows_total - 1;
-    int64_t kc = k0 + c * 4;
-    kc = kc < k_total - 4 ? kc : k_total - 4;
-    const float* g = src + gr * ld + kc;
+    const float* g = src + gr * ld + chunk_start(k0 + slot_chunk(q) * 4, k_total);
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                      (__attribute__((address_space(3))) void*)(stage + q0 * 4), 16, 0, 0);
   }
@@ -85,45 +63,27 @@ struct TileLanes {
 template <int ROWS>
 __device__ __forceinline__ void tile_lanes(TileLanes<ROWS>& t, const float* __restrict__ src, int64_t ld, int64_t row0,
                                            int64_t rows_total, int lane, int wave) {
-  constexpr int kChunks = ROWS * 4;
 #pragma unroll
   for (int i = 0; i < TileLanes<ROWS>::kIters; ++i) {
-    int q0 = 64 * wave + kThreads * i;
-    if (kChunks % kThreads != 0 && q0 >= kChunks) q0 -= kChunks;
-    const int q = q0 + lane;
-    const int row = q >> 2, c = (q & 3) ^ ((row >> 1) & 3);
-    int64_t gr = row0 + row;
+    const int q = wave_slot0<ROWS * 4>(wave, i) + lane;
+    int64_t gr = row0 + slot_row(q);
     gr = gr < rows_total ? gr : rows_total - 1;
-    t.p[i] = src + gr * ld + c * 4;
+    t.p[i] = src + gr * ld + slot_chunk(q) * 4;
   }
 }
 template <int ROWS>
 __device__ __forceinline__ void fetch_inside(float* stage, const TileLanes<ROWS>& t, int64_t k0, int wave) {
-  constexpr int kChunks = ROWS * 4;
 #pragma unroll
-  for (int i = 0; i < TileLanes<ROWS>::kIters; ++i) {
-    int q0 = 64 * wave + kThreads * i;
-    if (kChunks % kThreads != 0 && q0 >= kChunks) q0 -= kChunks;
+  for (int i = 0; i < TileLanes<ROWS>::kIters; ++i)
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(t.p[i] + k0),
-                                     (__attribute__((address_space(3))) void*)(stage + q0 * 4), 16, 0, 0);
-  }
+                                     (__attribute__((address_space(3))) void*)(stage + wave_slot0<ROWS * 4>(wave, i) * 4),
+                                     16, 0, 0);
 }
 
-// The operand fragments are read with ds_read_b128 written as asm: the compiler cannot tell which
-// stage an LDS-DMA load targets and would put s_waitcnt vmcnt(0) in front of every ordinary LDS read --
-// waiting for the loads issued a moment ago, i.e. no pipeline at all.  The waits are placed by hand
-// (wait_vmcnt before the barrier, lds_fence after the reads).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 lds_read128(uint32_t byte_addr) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
-  return v;
-}
 // byte offset inside a stage of the two 16-byte chunks (kk = 8h .. 8h+3, 8h+4 .. 8h+7) of tile row `row`
 __device__ __forceinline__ void frag_offsets(int row, int h, uint32_t (&off)[2]) {
-  const int sw = (row >> 1) & 3;
 #pragma unroll
-  for (int v = 0; v < 2; ++v) off[v] = (uint32_t)(row * 4 + ((2 * h + v) ^ sw)) * 16u;
+  for (int v = 0; v < 2; ++v) off[v] = (uint32_t)chunk_slot(row, 2 * h + v) * 16u;
 }
 
 template <int NT>
@@ -164,12 +124,6 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
   if (a.dot_out && a.dot_b) dotb = a.dot_b[0];
   wait_vmcnt<0>();  // ... and landed before the ring starts, so that no later use of bj waits on the queue
 
-  auto advance = [&](int64_t& t, int& k) {
-    if (++k == nk) {
-      k = 0;
-      t += gridDim.x;
-    }
-  };
   TileLanes<kBM> la;
   TileLanes<BN> lb;
   int64_t la_tile = -1;
@@ -191,10 +145,10 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
   // slots g+1 and g+2 relative to the one being multiplied
   int64_t t1 = tile, t2;
   int k1 = 0, k2;
-  advance(t1, k1);
+  ring_advance(t1, k1, nk);
   t2 = t1;
   k2 = k1;
-  advance(t2, k2);
+  ring_advance(t2, k2, nk);
   issue(0, tile, 0);
   if (t1 < mtiles) issue(1, t1, k1);
   int stage = 0;
@@ -236,8 +190,6 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
       if (t1 < mtiles) wait_vmcnt<kPerSlot>();
       else wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
-      int refill = stage + 2;
-      refill = refill >= kStages ? refill - kStages : refill;
       f32x4 fa[2], fb[NT][2];
       const uint32_t abase = ctr_lds_addr(s_a[0]) + (uint32_t)stage * (kBM * kBK * 4);
       const uint32_t bbase = ctr_lds_addr(s_b[0]) + (uint32_t)stage * (BN * kBK * 4);
@@ -247,9 +199,9 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
       for (int n = 0; n < NT; ++n)
 #pragma unroll
         for (int v = 0; v < 2; ++v) fb[n][v] = lds_read128(bbase + boff[v] + (uint32_t)n * (32 * kBK * 4));
-      if (t2 < mtiles) issue(refill, t2, k2);
-      advance(t1, k1);
-      advance(t2, k2);
+      if (t2 < mtiles) issue(ring_refill(stage), t2, k2);
+      ring_advance(t1, k1, nk);
+      ring_advance(t2, k2, nk);
       // every fragment register passes through the wait, so no MFMA can be scheduled above it
       if constexpr (NT == 1)
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0][0]), "+v"(fb[0][1]));
@@ -277,9 +229,8 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
         for (int n = 0; n < NT; ++n)
           acc[n][t % CH] =
               __builtin_amdgcn_mfma_f32_32x32x2f32(fa[t >> 2][t & 3], fb[n][t >> 2][t & 3], acc[n][t % CH], 0, 0, 0);
-      stage = stage + 1 == kStages ? 0 : stage + 1;
+      stage = ring_next(stage);
     }
-    // C/D map of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     float pdot[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) pdot[e] = 0.0f;
@@ -297,7 +248,7 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
         if (grouped) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int64_t i = first + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int64_t i = mfma_row(first, e, h);
             v[e] += i < edge ? r0v[n] : r1v[n];
           }
         } else if (a.res) {
@@ -305,7 +256,7 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
           float rv[16];
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int64_t i = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int64_t i = mfma_row(i0 + 32 * wave, e, h);
             const int64_t ri = a.res_group > 1 ? (int64_t)ctr_div((uint32_t)(i < a.m ? i : 0), a.res_div) : i;
             rv[e] = i < a.m ? ctr_ldg(a.res + ri * a.ldr + j) : 0.0f;
           }
@@ -318,7 +269,7 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
         uint32_t word = 0;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int64_t i = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+          const int64_t i = mfma_row(i0 + 32 * wave, e, h);
           const float o = ctr_act(v[e], a.act);
           if (i < a.m) ctr_stg(a.y + i * a.ldy + j, o);
           pdot[e] = fmaf(o, dwj[n], pdot[e]);
@@ -351,7 +302,7 @@ gemm_fwd_dlds_kernel(const DldsArgs a) {
       stage(std::integral_constant<int, 1>{}, r & 2, 2);
       const float t = pdot[0] + __shfl_xor(pdot[0], 1, 64);
       const int e = r >> 1;
-      const int64_t i = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const int64_t i = mfma_row(i0 + 32 * wave, e, h);
       if ((r & 1) == 0 && i < a.m) a.dot_out[i * a.lddot] = t + dotb;
     }
   }
@@ -367,15 +318,11 @@ static int launch_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, 
                       int64_t ldr, float* y, int64_t ldy, int64_t m, int n, int k, int act, hipStream_t st,
                       int res_group = 1, uint32_t* mask = nullptr, int64_t ldmask = 0, const float* dot_w = nullptr,
                       const float* dot_b = nullptr, float* dot_out = nullptr, int64_t lddot = 0) {
-  int nt = n <= 32 ? 1 : (n <= 64 ? 2 : 4);
   const int64_t mtiles = ctr_ceil_div(m, kBM);
-  // few rows (a table of ~1000 rows instead of a batch): 128 x 128 tiles would leave most CUs without a workgroup
-  // (943 x 256: 16 of them) -- narrower column tiles re-read the few rows from L2 and fill the chip
-  while (nt > 1 && !dot_out && mtiles * ctr_ceil_div(n, 32 * nt) < 128) nt >>= 1;
+  int nt = pick_nt(n);
+  if (!dot_out) nt = narrow_nt(nt, mtiles, n);  // (the head needs whole rows in one workgroup)
   const int64_t ny = ctr_ceil_div(n, 32 * nt);
-  int64_t gx = 256 * 3 / ny;  // rounded down: a workgroup beyond the resident 3 per CU would start a second round
-  if (gx > mtiles) gx = mtiles;
-  if (gx < 1) gx = 1;
+  const int64_t gx = ring_grid(3, ny, mtiles);
   CTR_REQUIRE(ny <= 65535, CTR_ELIMIT);
   CTR_REQUIRE(res_group >= 1 && (res_group == 1 || m < (1ll << 32)), CTR_ELIMIT);
   CTR_REQUIRE(!mask || (n % 32 == 0 && ldmask >= n / 32), CTR_EINVAL);

@@ -1,13 +1,13 @@
 // Weight gradient  gW[n, :k] += sum_m gZ[m, n] X[m, :k],  gb[n] += sum_m gZ[m, n],  gZ = gY * act'(Y),
 // with the three streamed operands (gY, Y, X) copied global -> LDS directly (global_load_lds_dwordx4)
-// through a three-stage ring, like the forward kernel of gemm_dlds.hip.
+// through the three-stage ring of gemm_ring.h.
 //
 // The contraction runs over the batch, so both MFMA operands are read "down the rows" of their
 // row-major tiles: lane (r, h) takes element [8h + t][32*tile + r] for t = 0..7 -- 32 consecutive
 // floats per half-wave and instruction, conflict-free without any swizzle, and the LDS image is the
-// plain row-major tile the direct loads produce.  act'(Y) is applied to the gY values as they are
+// plain [16][W] tile the direct loads produce.  act'(Y) is applied to the gY values as they are
 // read; rows past the end of a workgroup's row range are zeroed there too (their loads are clamped
-// to a valid row).  The 16-byte loads only need 4-byte aligned addresses; see fetch() for the column tails.
+// to a valid row).
 //
 // Output tile: 128 x 32*NT per 256-thread workgroup (which side is units: see SWAP), the batch cut into
 // `parts` row ranges (multiples of 16 rows); every workgroup stores its partial tile into its part's
@@ -15,16 +15,13 @@
 //
 // The direct loads are issued from inline asm, which keeps them out of the compiler's waitcnt
 // bookkeeping (it would otherwise put vmcnt(0) in front of every LDS read); the waits are explicit.
-#include "ctr_common.h"
+#include "gemm_ring.h"
+
+using namespace gemm_ring;
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int kThreads = 256;
-constexpr int kAW = 128;  // units per workgroup
-constexpr int kBK = 16;   // batch rows per pipeline step
-constexpr int kStages = 3;
+constexpr int kAW = 128;  // units per workgroup; kBK = batch rows per pipeline step
 
 struct DwArgs {
   const float* gy; int64_t ldgy;
@@ -36,42 +33,9 @@ struct DwArgs {
   int want_bias;
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-
-// copy rows [row0, row0+16) x columns [col0, col0+W) of a row-major matrix into a [16][W] stage
-template <int W>
-__device__ __forceinline__ void fetch(float* stage, const float* __restrict__ src, int64_t ld, int64_t row0,
-                                      int64_t row_last, int col0, int cols_total, int lane, int wave) {
-  constexpr int kPerRow = W / 4, kChunks = 16 * kPerRow;
-  constexpr int kIters = (kChunks + kThreads - 1) / kThreads;
-#pragma unroll
-  for (int i = 0; i < kIters; ++i) {
-    int q0 = 64 * wave + kThreads * i;
-    if (kChunks % kThreads != 0 && q0 >= kChunks) q0 -= kChunks;  // narrow tile: fetched twice, same bytes
-    const int q = q0 + lane;
-    const int row = q / kPerRow, cc = q % kPerRow;
-    int64_t gr = row0 + row;
-    gr = gr < row_last ? gr : row_last;
-    // a chunk that would cross the end of the row (or lies past it) is fetched from 4 floats before
-    // the end: no load leaves the matrix, the reader adds the shift (tail_shift), the rest is dropped
-    int col = col0 + cc * 4;
-    col = col < cols_total - 4 ? col : cols_total - 4;
-    ctr_dma16(src + gr * ld + col, __builtin_amdgcn_readfirstlane(ctr_lds_addr(stage + q0 * 4)));
-  }
-}
-
 // SWAP = false: the 128-wide side of the tile are units (operand gZ, columns n0..), the 32*NT side inputs (X).
 // SWAP = true : the 128-wide side are inputs (X, columns k0..), the 32*NT side units (gZ) -- for layers with
 //               fewer than 128 units, which would leave half of the unswapped tile empty.
-// logical column `col` of a matrix with `total` columns sits this many floats further right in its
-// (shifted) last chunk
-__device__ __forceinline__ int tail_shift(int col, int total) {
-  return (total & 3) && col >= (total & ~3) && col < total ? 4 - (total & 3) : 0;
-}
-
 template <int NT, int ACT, bool SWAP>
 __global__ void __launch_bounds__(kThreads, 2)
 gemm_dw_dlds_kernel(const DwArgs a) {
@@ -112,9 +76,9 @@ gemm_dw_dlds_kernel(const DwArgs a) {
 
   auto issue = [&](int stage, int s) {
     const int64_t row0 = mb + (int64_t)s * kBK;
-    fetch<ZW>(s_gy[stage], a.gy, a.ldgy, row0, a.m - 1, n0, a.n, lane, wave);
-    if (has_y) fetch<ZW>(s_y[stage], a.y, a.ldy, row0, a.m - 1, n0, a.n, lane, wave);
-    fetch<XW>(s_x[stage], a.x, a.ldx, row0, a.m - 1, k0, a.k, lane, wave);
+    fetch_plain<ZW, 1>(s_gy[stage], a.gy, a.ldgy, row0, a.m - 1, n0, a.n, lane, wave);
+    if (has_y) fetch_plain<ZW, 1>(s_y[stage], a.y, a.ldy, row0, a.m - 1, n0, a.n, lane, wave);
+    fetch_plain<XW, 1>(s_x[stage], a.x, a.ldx, row0, a.m - 1, k0, a.k, lane, wave);
   };
   if (steps > 0) issue(0, 0);
   if (steps > 1) issue(1, 1);
@@ -126,9 +90,7 @@ gemm_dw_dlds_kernel(const DwArgs a) {
     else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    int refill = stage + 2;
-    refill = refill >= kStages ? refill - kStages : refill;
-    if (s + 2 < steps) issue(refill, s + 2);
+    if (s + 2 < steps) issue(ring_refill(stage), s + 2);
 
     const int64_t row = mb + (int64_t)s * kBK + 8 * h;
     // gZ element [8h + t][col] of the stage, zero past the end of the row range
@@ -162,15 +124,15 @@ gemm_dw_dlds_kernel(const DwArgs a) {
 #pragma unroll
       for (int t = 0; t < 8; ++t) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[t], fb[t], acc[nb], 0, 0, 0);
     }
-    stage = stage + 1 == kStages ? 0 : stage + 1;
+    stage = ring_next(stage);
   }
-  // C/D map: column (B side) = lane & 31, row (A side) = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+  // C/D map: the column is on the B side, the row on the A side
   float* out = a.ws + (int64_t)blockIdx.x * a.slab;
 #pragma unroll
   for (int nb = 0; nb < NT; ++nb) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int arow = 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h, bcol = 32 * nb + r;
+      const int arow = mfma_row(32 * wave, e, h), bcol = 32 * nb + r;
       const int un = SWAP ? n0 + bcol : n0 + arow;
       const int kc = SWAP ? k0 + arow : k0 + bcol;
       if (un < a.n && kc < a.k) ctr_stg(out + (int64_t)un * a.k + kc, acc[nb][e]);
@@ -200,20 +162,15 @@ int ctr_gemm_dlds_dw(const float* x, int64_t ldx, const float* y, int64_t ldy, c
                      float* gb, int64_t m, int n, int k, int act, float* workspace, int64_t workspace_floats,
                      hipStream_t st) {
   // the 128-wide side goes to whichever of (units, inputs) pads less
-  auto padded = [](int64_t wide, int64_t narrow) {
-    const int nt = narrow <= 32 ? 1 : (narrow <= 64 ? 2 : 4);
-    return ctr_ceil_div(wide, kAW) * kAW * ctr_ceil_div(narrow, 32 * nt) * 32 * nt;
-  };
   const bool swap = n < 96 || (k >= 96 && padded(k, n) < padded(n, k));
   const int wide = swap ? k : n, narrow = swap ? n : k;
-  const int nt = narrow <= 32 ? 1 : (narrow <= 64 ? 2 : 4);
+  const int nt = pick_nt(narrow);
   const int64_t ty = ctr_ceil_div(wide, kAW), tz = ctr_ceil_div(narrow, 32 * nt);
   const int64_t slab = (int64_t)n * k + (gb ? n : 0);
   // one round of the 2 resident workgroups per CU: more, shorter row ranges only add slab traffic (measured:
   // 65536 x 256 x 512 takes 200 us with 512 workgroups, 221-228 us with 768-1536)
   // (rounded down: 540 workgroups would run as a full round plus a round of 28)
-  int64_t parts = 256 * 2 / (ty * tz);
-  if (parts < 1) parts = 1;
+  int64_t parts = ring_grid(2, ty * tz, /*no row-tile bound: the parts are cut from the batch below*/ INT64_MAX);
   if (parts * slab > workspace_floats) parts = workspace_floats / slab;
   if (parts < 1) return CTR_ELIMIT;
   int64_t rows = ctr_ceil_div(ctr_ceil_div(m, parts), kBK) * kBK;

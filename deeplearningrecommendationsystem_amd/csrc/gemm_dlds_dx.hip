@@ -1,27 +1,21 @@
 // Input gradient  gX[m, :k] (=|+=) sum_n gZ[m, n] W[n, :k],  gZ = gY * act'(Y),  with gY, Y and W copied
-// global -> LDS directly (global_load_lds_dwordx4) through a three-stage ring; see gemm_dlds.hip for the
-// ring and gemm_dlds_dw.hip for why the loads are issued from asm.
+// global -> LDS directly (global_load_lds_dwordx4) through a three-stage ring; gemm_ring.h has the stage
+// format and the ring, gemm_dlds_dw.hip says why the loads are issued from asm.
 //
 // Tile 128 rows x 32*NT input columns per 256-thread workgroup, persistent over the row tiles; a step
-// contracts 16 units.  gY / Y tiles are [128][16] with the chunk swizzle of gemm_dlds.hip (read with
-// ds_read_b128 along the units), the W tile is the plain row-major [16][32*NT] block and is read down
-// its rows (32 consecutive floats per half-wave: conflict-free).  act'(Y) is applied as gY is read.
-// The 16-byte direct loads only need 4-byte aligned addresses, so any layout with n, k >= 4 is taken.
-// No load leaves its matrix: a chunk that would cross the end of a row is fetched from 4 floats before
-// the end instead.  Along the units (contraction tail, n % 16 != 0) the gY fragment zeroes the
-// positions that are then duplicates or past n; along W's columns (k % 4 != 0) the reader adds the
-// shift to its column index.
-#include "ctr_common.h"
+// contracts 16 units.  gY / Y tiles are swizzled [128][16] tiles (read along the units), the W tile is
+// the plain [16][32*NT] block and is read down its rows (32 consecutive floats per half-wave:
+// conflict-free).  act'(Y) is applied as gY is read.  Any layout with n, k >= 4 is taken.  Along the
+// units (contraction tail, n % 16 != 0) the gY fragment zeroes the positions that are duplicates or
+// past n; along W's columns (k % 4 != 0) the reader adds tail_shift to its column index.
+#include "gemm_ring.h"
 #include <stdlib.h>
+
+using namespace gemm_ring;
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int kThreads = 256;
 constexpr int kBM = 128;
-constexpr int kBK = 16;
-constexpr int kStages = 3;
 
 struct DxArgs {
   const float* gy; int64_t ldgy;
@@ -41,52 +35,17 @@ struct DxArgs {
   const int64_t* sc_idx; const float* sc_attn; const float* sc_gpool; int64_t sc_ldgp; float* sc_table; int64_t sc_vocab;
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-
-// [128 rows][16 units] tile, slot q (16 B) = row q/4, unit chunk (q & 3) ^ ((row >> 1) & 3)
+// swizzled [128 rows][16 units] tile
 __device__ __forceinline__ void fetch_rows(float* stage, const float* __restrict__ src, int64_t ld, int64_t row0,
                                            int64_t rows_total, int u0, int u_total, int lane, int wave) {
 #pragma unroll
   for (int i = 0; i < kBM * 4 / kThreads; ++i) {
-    const int q0 = 64 * wave + kThreads * i;
+    const int q0 = wave_slot0<kBM * 4>(wave, i);
     const int q = q0 + lane;
-    const int row = q >> 2, c = (q & 3) ^ ((row >> 1) & 3);
-    int64_t gr = row0 + row;
+    int64_t gr = row0 + slot_row(q);
     gr = gr < rows_total ? gr : rows_total - 1;
-    int u = u0 + c * 4;
-    u = u < u_total - 4 ? u : u_total - 4;
+    const int u = chunk_start(u0 + slot_chunk(q) * 4, u_total);
     ctr_dma16(src + gr * ld + u, __builtin_amdgcn_readfirstlane(ctr_lds_addr(stage + q0 * 4)));
-  }
-}
-
-// logical column `col` of a matrix with `total` columns sits this many floats further right in its
-// (shifted) last chunk
-__device__ __forceinline__ int tail_shift(int col, int total) {
-  return (total & 3) && col >= (total & ~3) && col < total ? 4 - (total & 3) : 0;
-}
-
-// plain [16 units][W columns] block of the weight
-template <int W>
-__device__ __forceinline__ void fetch_w(float* stage, const float* __restrict__ w, int64_t ldw, int u0, int u_total,
-                                        int col0, int cols_total, int lane, int wave) {
-  constexpr int kPerRow = W / 4, kChunks = 16 * kPerRow;
-  constexpr int kIters = (kChunks + kThreads - 1) / kThreads;
-#pragma unroll
-  for (int i = 0; i < kIters; ++i) {
-    int q0 = 64 * wave + kThreads * i;
-    if (kChunks % kThreads != 0 && q0 >= kChunks) q0 -= kChunks;  // narrow tile: fetched twice, same bytes
-    const int q = q0 + lane;
-    const int row = q / kPerRow, cc = q % kPerRow;
-    int col = col0 + cc * 4;
-    col = col < cols_total - 4 ? col : cols_total - 4;
-    // row = 4*chunk + j of the step follows the unit the gY fragment holds at that position
-    // (fetch_rows: chunks crossing n start at n-4)
-    int u = u0 + (row & ~3);
-    u = (u < u_total - 4 ? u : u_total - 4) + (row & 3);
-    ctr_dma16(w + (int64_t)u * ldw + col, __builtin_amdgcn_readfirstlane(ctr_lds_addr(stage + q0 * 4)));
   }
 }
 
@@ -117,23 +76,20 @@ gemm_dx_dlds_kernel(const DxArgs a) {
 #pragma unroll
   for (int nb = 0; nb < NT; ++nb) padacc[nb] = 0.0f;
 
-  auto advance = [&](int64_t& t, int& ks) {
-    if (++ks == nk) {
-      ks = 0;
-      t += gridDim.x;
-    }
-  };
   auto issue = [&](int stage, int64_t t, int ks) {
     fetch_rows(s_gy[stage], a.gy, a.ldgy, t * kBM, a.m, ks * kBK, a.n, lane0, wave);
     if (has_y) fetch_rows(s_y[stage], a.y, a.ldy, t * kBM, a.m, ks * kBK, a.n, lane0, wave);
-    fetch_w<BW>(s_w[stage], a.w, a.ldw, ks * kBK, a.n, c0, a.k, lane0, wave);
+    // plain [16 units][BW columns] block of the weight: row 4*chunk + j of the step follows the unit the gY
+    // fragment holds at that position (chunks crossing n start at n-4)
+    fetch_plain<BW, 4>(s_w[stage], a.w, a.ldw, ks * kBK, a.n - 4, c0, a.k, lane0, wave);
   };
+  // slots g+1 and g+2 relative to the one being multiplied
   int64_t t1 = tile, t2;
   int k1 = 0, k2;
-  advance(t1, k1);
+  ring_advance(t1, k1, nk);
   t2 = t1;
   k2 = k1;
-  advance(t2, k2);
+  ring_advance(t2, k2, nk);
   issue(0, tile, 0);
   if (t1 < mtiles) issue(1, t1, k1);
   int stage = 0;
@@ -142,7 +98,7 @@ gemm_dx_dlds_kernel(const DxArgs a) {
     int lane = lane0;
     asm volatile("" : "+v"(lane));
     const int r = lane & 31, h = lane >> 5;
-    const int arow = 32 * wave + r, sw = (arow >> 1) & 3;
+    const int arow = 32 * wave + r;
     int wcol[NT];
 #pragma unroll
     for (int nb = 0; nb < NT; ++nb) wcol[nb] = 32 * nb + r + tail_shift(c0 + 32 * nb + r, a.k);
@@ -191,15 +147,13 @@ gemm_dx_dlds_kernel(const DxArgs a) {
       else wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      int refill = stage + 2;
-      refill = refill >= kStages ? refill - kStages : refill;
-      if (t2 < mtiles) issue(refill, t2, k2);
-      advance(t1, k1);
-      advance(t2, k2);
+      if (t2 < mtiles) issue(ring_refill(stage), t2, k2);
+      ring_advance(t1, k1, nk);
+      ring_advance(t2, k2, nk);
       float fa[8];
 #pragma unroll
       for (int v = 0; v < 2; ++v) {
-        const int slot = arow * 4 + ((2 * h + v) ^ sw);
+        const int slot = chunk_slot(arow, 2 * h + v);
         const float4 g = *reinterpret_cast<const float4*>(&s_gy[stage][slot * 4]);
         fa[4 * v + 0] = g.x; fa[4 * v + 1] = g.y; fa[4 * v + 2] = g.z; fa[4 * v + 3] = g.w;
         if (has_y) {
@@ -227,9 +181,8 @@ gemm_dx_dlds_kernel(const DxArgs a) {
         for (int t = 0; t < 8; ++t)
           acc[nb][t % CH] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[t], fb[t], acc[nb][t % CH], 0, 0, 0);
       }
-      stage = stage + 1 == kStages ? 0 : stage + 1;
+      stage = ring_next(stage);
     }
-    // C/D map: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     if constexpr (EPI == 2) {
       const int64_t first = i0 + 32 * wave;
 #pragma unroll
@@ -240,7 +193,7 @@ gemm_dx_dlds_kernel(const DxArgs a) {
           float v = acc[nb][0][e];
 #pragma unroll
           for (int c = 1; c < CH; ++c) v += acc[nb][c][e];
-          const int rho = (e & 3) + 8 * (e >> 2);
+          const int rho = mfma_row(e);
           const int id0 = __builtin_amdgcn_readlane(idrow, rho), id1 = __builtin_amdgcn_readlane(idrow, rho + 4);
           const float at0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, attnrow), rho));
           const float at1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, attnrow), rho + 4));
@@ -269,11 +222,10 @@ gemm_dx_dlds_kernel(const DxArgs a) {
         for (int q = 0; q < NB; ++q) {
           const int col = c0 + 32 * (nb0 + q) + r;
           if (a.xmask) {
-            // register e holds rows (e & 3) + 8 (e >> 2) [+ 4 in the upper half-wave]: their words sit in those
-            // lanes of mrow
+            // register e holds rows mfma_row(e) [+ 4 in the upper half-wave]: their words sit in those lanes of mrow
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-              const int rho = (e & 3) + 8 * (e >> 2);
+              const int rho = mfma_row(e);
               const uint32_t w0 = __builtin_amdgcn_readlane(mrow[nb0 + q], rho);
               const uint32_t w1 = __builtin_amdgcn_readlane(mrow[nb0 + q], rho + 4);
               xv[q][e] = (((h ? w1 : w0) >> r) & 1u) ? 1.0f : 0.0f;
@@ -281,7 +233,7 @@ gemm_dx_dlds_kernel(const DxArgs a) {
           } else {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-              const int64_t i = first + (e & 3) + 8 * (e >> 2) + 4 * h;
+              const int64_t i = mfma_row(first, e, h);
               xv[q][e] = (a.xin && i < a.m && col < a.k) ? ctr_ldg(a.xin + i * a.ldxin + col) : 1.0f;
             }
           }
@@ -303,7 +255,7 @@ gemm_dx_dlds_kernel(const DxArgs a) {
             float s0 = 0.0f, s1 = 0.0f;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-              const int64_t i = first + (e & 3) + 8 * (e >> 2) + 4 * h;
+              const int64_t i = mfma_row(first, e, h);
               if (i < a.m) {
                 ctr_stg(a.gx + i * a.ldgx + col, v[e]);
                 if (i < edge) s0 += v[e];
@@ -341,7 +293,7 @@ gemm_dx_dlds_kernel(const DxArgs a) {
           float old[16];
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int64_t i = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int64_t i = mfma_row(i0 + 32 * wave, e, h);
             old[e] = i < a.m ? ctr_ldg(a.gx + i * a.ldgx + col) : 0.0f;
           }
 #pragma unroll
@@ -349,7 +301,7 @@ gemm_dx_dlds_kernel(const DxArgs a) {
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int64_t i = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+          const int64_t i = mfma_row(i0 + 32 * wave, e, h);
           if (i < a.m) ctr_stg(a.gx + i * a.ldgx + col, v[e]);
         }
       }
@@ -396,16 +348,12 @@ struct DxEpilogue {
 static int launch_dx(const float* w, int64_t ldw, const float* y, int64_t ldy, const float* gy, int64_t ldgy, float* gx,
                      int64_t ldgx, int accumulate, int64_t m, int n, int k, int act, hipStream_t st,
                      const DxEpilogue& ep = DxEpilogue()) {
-  int nt = k <= 32 ? 1 : (k <= 64 ? 2 : 4);
   const int64_t mtiles = ctr_ceil_div(m, kBM);
-  while (nt > 1 && !ep.on && mtiles * ctr_ceil_div(k, 32 * nt) < 128) nt >>= 1;   // few rows: see gemm_dlds.hip
+  int nt = pick_nt(k);
+  if (!ep.on) nt = narrow_nt(nt, mtiles, k);
   const int64_t ny = ctr_ceil_div(k, 32 * nt);
-  // rounded down: a workgroup beyond the resident ones would start a second round.  Two per CU with a Y tile in the
-  // ring (72 KB of LDS); without one (48 KB, <= 144 registers) three fit
-  constexpr int wgs_plain = 3;
-  int64_t gx_ = 256 * (act == CTR_ACT_NONE ? wgs_plain : 2) / ny;
-  if (gx_ > mtiles) gx_ = mtiles;
-  if (gx_ < 1) gx_ = 1;
+  // two workgroups per CU with a Y tile in the ring (72 KB of LDS); without one (48 KB, <= 144 registers) three fit
+  const int64_t gx_ = ring_grid(act == CTR_ACT_NONE ? 3 : 2, ny, mtiles);
   CTR_REQUIRE(ny <= 65535, CTR_ELIMIT);
   const DxArgs a{gy, ldgy, act == CTR_ACT_NONE ? nullptr : y, ldy, w, ldw, gx, ldgx, m, n, k, accumulate,
                  ep.xin, ep.ldxin, ep.act_in, ep.gsum, ep.ldgsum, ep.group, ep.xmask, ep.ldxmask,

@@ -10,20 +10,17 @@
 // Taken by ctr_linear_fwd when it applies (ctr_gemm_wide_ok): n a multiple of 256, k a multiple of 16 and >= 256, aligned
 // operands, a batch of at least 4096 rows, no residual -- and CTR_GEMM_WIDE=1: this first version reaches 96.3 TF on
 // 65536 x 256 x 512 in the microbenchmark (gemm_dlds.hip 90.5, hipBLASLt 106.7) but loses inside the models' steps;
-// profiles/r03_gemm_wide.txt has both measurements and what it still lacks.  Operands stream global -> LDS with the same 16-byte-chunk
-// layout, swizzle and ring of three stages as gemm_dlds.hip.
-#include "ctr_common.h"
+// profiles/r03_gemm_wide.txt has both measurements and what it still lacks.  Operands stream global -> LDS as swizzled
+// tiles through the three-stage ring of gemm_ring.h.
+#include "gemm_ring.h"
 
 #include <stdlib.h>
 
+using namespace gemm_ring;
+
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kThreads = 256;
-constexpr int kTM = 256, kTN = 256, kBK = 16;
-constexpr int kStages = 3;
+constexpr int kTM = 256, kTN = 256;
 constexpr int kStageFloats = (kTM + kTN) * kBK;      // one stage: the A tile, then the B tile
 constexpr int kLoads = (kTM + kTN) * 4 / kThreads;   // 16-byte chunks a thread requests per step: 8
 
@@ -34,16 +31,6 @@ struct WideArgs {
   float* y; int64_t ldy;
   int64_t m; int n; int k; int act;
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ f32x4 lds_read128(uint32_t byte_addr) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
-  return v;
-}
 
 __global__ void __launch_bounds__(kThreads, 1)
 gemm_wide_fwd_kernel(const WideArgs a) {
@@ -57,20 +44,18 @@ gemm_wide_fwd_kernel(const WideArgs a) {
   const int nk = a.k / kBK;
 
   // per-lane source rows of the 8 chunks this thread requests per step (rows past the batch re-read the last row:
-  // their outputs are not stored).  Chunk slot q = 64 * wave + lane + 256 * i: tile row q / 4, 16-byte chunk
-  // (q % 4) ^ ((row / 2) % 4) of the step -- the layout gemm_dlds.hip reads back without bank conflicts.
+  // their outputs are not stored)
   const float* src[kLoads];
   auto set_tile = [&](int64_t t) {
     const int64_t i0 = (t / ntiles) * kTM, j0 = (int64_t)(t % ntiles) * kTN;
 #pragma unroll
     for (int i = 0; i < kLoads; ++i) {
-      const int q = 64 * wave + lane + kThreads * i;          // 0 .. 2047: A chunks, then B chunks
+      const int q = wave_slot0<(kTM + kTN) * 4>(wave, i) + lane;   // 0 .. 2047: A chunks, then B chunks
       const bool isb = q >= kTM * 4;
       const int qq = isb ? q - kTM * 4 : q;
-      const int row = qq >> 2, c = (qq & 3) ^ ((row >> 1) & 3);
-      int64_t gr = (isb ? j0 : i0) + row;
+      int64_t gr = (isb ? j0 : i0) + slot_row(qq);
       if (!isb) gr = gr < a.m ? gr : a.m - 1;
-      src[i] = (isb ? a.w + gr * a.ldw : a.x + gr * a.ldx) + c * 4;
+      src[i] = (isb ? a.w + gr * a.ldw : a.x + gr * a.ldx) + slot_chunk(qq) * 4;
     }
   };
   auto issue = [&](int stage, int k) {
@@ -78,7 +63,8 @@ gemm_wide_fwd_kernel(const WideArgs a) {
 #pragma unroll
     for (int i = 0; i < kLoads; ++i)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + (int64_t)k * kBK),
-                                       (__attribute__((address_space(3))) void*)(st + (64 * wave + kThreads * i) * 4), 16, 0, 0);
+                                       (__attribute__((address_space(3))) void*)(st + wave_slot0<(kTM + kTN) * 4>(wave, i) * 4), 16,
+                                       0, 0);
   };
   // fragment byte offsets inside a stage: A rows wr*128 + 32 i + r, B rows wc*128 + 32 j + r (B tile behind the A tile)
   uint32_t aoff[4][2], boff[4][2];
@@ -87,8 +73,8 @@ gemm_wide_fwd_kernel(const WideArgs a) {
     const int ra = wr * 128 + 32 * i + r, rb = wc * 128 + 32 * i + r;
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
-      aoff[i][v] = (uint32_t)(ra * 4 + ((2 * h + v) ^ ((ra >> 1) & 3))) * 16u;
-      boff[i][v] = (uint32_t)(kTM * kBK * 4) + (uint32_t)(rb * 4 + ((2 * h + v) ^ ((rb >> 1) & 3))) * 16u;
+      aoff[i][v] = (uint32_t)chunk_slot(ra, 2 * h + v) * 16u;
+      boff[i][v] = (uint32_t)(kTM * kBK * 4) + (uint32_t)chunk_slot(rb, 2 * h + v) * 16u;
     }
   }
   const uint32_t base0 = ctr_lds_addr(lds);
@@ -130,9 +116,7 @@ gemm_wide_fwd_kernel(const WideArgs a) {
         fa[i][1] = lds_read128(sb + aoff[i][1]);
         fb[i][1] = lds_read128(sb + boff[i][1]);
       }
-      int refill = stage + 2;
-      refill = refill >= kStages ? refill - kStages : refill;
-      if (ks + 2 < nk) issue(refill, ks + 2);
+      if (ks + 2 < nk) issue(ring_refill(stage), ks + 2);
       // every fragment register passes through its wait, so no MFMA that uses it can be scheduled above it
       asm volatile("s_waitcnt lgkmcnt(8)"
                    : "+v"(fa[0][0]), "+v"(fa[1][0]), "+v"(fa[2][0]), "+v"(fa[3][0]), "+v"(fb[0][0]), "+v"(fb[1][0]),
@@ -155,9 +139,8 @@ gemm_wide_fwd_kernel(const WideArgs a) {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][1][t], fb[j][1][t], acc[i][j], 0, 0, 0);
-      stage = stage + 1 == kStages ? 0 : stage + 1;
+      stage = ring_next(stage);
     }
-    // C/D map of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t col = j0 + wc * 128 + 32 * j + r;
@@ -168,11 +151,11 @@ gemm_wide_fwd_kernel(const WideArgs a) {
         float* yp = a.y + row0 * a.ldy + col;
         if (row0 + 28 < a.m) {                 // (uniform per half-wave block except in the batch's last tile)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) ctr_stg(yp + ((e & 3) + 8 * (e >> 2)) * a.ldy, ctr_act(acc[i][j][e] + bj, a.act));
+          for (int e = 0; e < 16; ++e) ctr_stg(yp + mfma_row(e) * a.ldy, ctr_act(acc[i][j][e] + bj, a.act));
         } else {
 #pragma unroll
           for (int e = 0; e < 16; ++e)
-            if (row0 + (e & 3) + 8 * (e >> 2) < a.m) ctr_stg(yp + ((e & 3) + 8 * (e >> 2)) * a.ldy, ctr_act(acc[i][j][e] + bj, a.act));
+            if (row0 + mfma_row(e) < a.m) ctr_stg(yp + mfma_row(e) * a.ldy, ctr_act(acc[i][j][e] + bj, a.act));
         }
       }
     }
@@ -195,7 +178,7 @@ int ctr_gemm_wide_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, 
                       int64_t m, int n, int k, int act, hipStream_t st) {
   const WideArgs a{x, ldx, w, ldw, bias, y, ldy, m, n, k, act};
   const int64_t mtiles = ctr_ceil_div(m, kTM);
-  const int64_t grid = mtiles < 256 ? mtiles : 256;          // one row tile (all its column tiles) per workgroup and round
+  const int64_t grid = mtiles < kCtrCUs ? mtiles : kCtrCUs;  // one row tile (all its column tiles) per workgroup and round
   constexpr int lds_bytes = kStages * kStageFloats * (int)sizeof(float);   // 96 KB
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_wide_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           lds_bytes) != hipSuccess)

@@ -16,15 +16,13 @@
 //   backward dX  gX = gZ W                  A = gZ (KC)   B = W  (KS)
 //   backward dW  gW += gZ^T X               A = gZ (KS)   B = X  (KS), split over m, fp32 atomics
 // with gZ = gY * act'(Y) formed while staging (never materialised).
-#include "ctr_common.h"
+#include "gemm_ring.h"   // vector types, kThreads, kBK, the C/D row map and the tile policy
+
+using namespace gemm_ring;
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int kThreads = 256;
 constexpr int kBM = 128;
-constexpr int kBK = 16;             // contraction depth of one pipeline step
 constexpr int kHalf = kBK / 2;      // values per lane and step: the lane halves take kk = kHalf*h + t
 constexpr int kKcStride = kBK + 4;  // floats; 80 B rows: 8 consecutive rows cover all 32 banks with b128 reads
 // resident workgroups per CU = waves per SIMD: four.  The forward (both operands KC) needs exactly
@@ -282,18 +280,12 @@ gemm_tile_kernel(const ASrc a, const BSrc b, const Epi epi, int64_t M, int N, in
   int64_t tile = blockIdx.x;
   if (tile >= mtiles || nk <= 0) return;
   // (tile, step) of the pipeline slot one / two steps ahead of the one being multiplied
-  auto advance = [&](int64_t& t, int& k) {
-    if (++k == nk) {
-      k = 0;
-      t += gridDim.x;
-    }
-  };
   int64_t t1 = tile, t2 = tile;
   int k1 = 0, k2 = 0;
-  advance(t1, k1);
+  ring_advance(t1, k1, nk);
   t2 = t1;
   k2 = k1;
-  advance(t2, k2);
+  ring_advance(t2, k2, nk);
   sa.load(a, tile * kBM, kb, a_in);
   sb.load(b, j0, kb, b_in);
   sa.store(s_a[0]);
@@ -327,8 +319,8 @@ gemm_tile_kernel(const ASrc a, const BSrc b, const Epi epi, int64_t M, int N, in
         sa.load(a, t2 * kBM, kb + (int64_t)k2 * kBK, a_in);
         sb.load(b, j0, kb + (int64_t)k2 * kBK, b_in);
       }
-      advance(t1, k1);
-      advance(t2, k2);
+      ring_advance(t1, k1, nk);
+      ring_advance(t2, k2, nk);
       float fa[kHalf];
       read_frag<AMODE, kBM>(s_a[cur], 32 * wave + r, h, fa);
       float fb[NT][kHalf];
@@ -356,14 +348,13 @@ gemm_tile_kernel(const ASrc a, const BSrc b, const Epi epi, int64_t M, int N, in
       cur ^= 1;
     }
 
-    // C/D map of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       const int64_t j = j0 + 32 * n + r;
       if (j < N) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int64_t i = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+          const int64_t i = mfma_row(i0 + 32 * wave, e, h);
           float v = acc[n][0][e];
 #pragma unroll
           for (int c = 1; c < CH; ++c) v += acc[n][c][e];
@@ -394,8 +385,6 @@ inline PlainSrc plain(const float* p, int64_t ld, int64_t rows, int64_t cols) {
   return s;
 }
 
-inline int pick_nt(int n) { return n <= 32 ? 1 : (n <= 64 ? 2 : 4); }
-
 // contraction chunks the launch really makes (chunks are whole 32-deep steps)
 inline int effective_splits(int64_t K, int64_t splits) {
   const int64_t k_chunk = ctr_ceil_div(ctr_ceil_div(K, splits), kBK) * kBK;
@@ -405,15 +394,13 @@ inline int effective_splits(int64_t K, int64_t splits) {
 template <int AMODE, int BMODE, class ASrc, class BSrc, class Epi>
 int launch(const ASrc& a, const BSrc& b, const Epi& e, int64_t M, int N, int64_t K, int splits, float* bias_grad,
            hipStream_t st, int64_t bias_slab_stride = 0, int bias_from_b = 0) {
-  int nt = pick_nt(N);
   const int64_t k_chunk = ctr_ceil_div(ctr_ceil_div(K, splits), kBK) * kBK;
   const int zs = (int)ctr_ceil_div(K, k_chunk);
   // as many workgroups as stay resident, each walking its share of the M tiles
   const int64_t mtiles = ctr_ceil_div(M, kBM);
-  // a handful of tiles for 256 CUs (products over ~1000 table rows): narrower column tiles instead
-  while (nt > 1 && mtiles * ctr_ceil_div(N, 32 * nt) * zs < 128) nt >>= 1;
-  const int64_t others = ctr_ceil_div(N, 32 * nt) * zs;
-  int64_t gx = ctr_ceil_div(256 * wg_per_cu(AMODE, BMODE), others);
+  const int nt = narrow_nt(pick_nt(N), mtiles, N, zs);
+  // (rounded UP, as this kernel's grid always was; the ring kernels' ring_grid rounds down)
+  int64_t gx = ctr_ceil_div(kCtrCUs * wg_per_cu(AMODE, BMODE), ctr_ceil_div(N, 32 * nt) * zs);
   if (gx > mtiles) gx = mtiles;
   if (gx < 1) gx = 1;
   const dim3 grid((unsigned)gx, (unsigned)ctr_ceil_div(N, 32 * nt), (unsigned)zs);
@@ -556,10 +543,6 @@ extern "C" int ctr_linear_bwd(const float* x, int64_t ldx, const float* w, int64
       float* ws_b = workspace + splits * slab;
       // orientation: the 128-row side of the tile should be the longer of (n, k).  A funnel layer
       // (n = k/2, n < 128) fills half of a 128 x k tile as gZ^T X but all of a k x n tile as X^T gZ.
-      auto padded = [](int64_t rows, int64_t cols) {
-        const int nt = pick_nt((int)cols);
-        return ctr_ceil_div(rows, kBM) * kBM * ctr_ceil_div(cols, 32 * nt) * 32 * nt;
-      };
       int rc;
       if (padded(k, n) < padded(n, k)) {
         SlabEpiT et{workspace, k, slab};
