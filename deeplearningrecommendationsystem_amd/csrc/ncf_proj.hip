@@ -17,10 +17,13 @@
 //
 // The segment sums are formed without a sort: the forward's id pass counts the samples of every row with returning
 // atomics (rank of a sample within its row), the backward kernel scans the counts (every workgroup for itself, 2625
-// entries) and stores each sample's gz0 row straight into its row's bucket, slot = offset[row] + rank, once for the
-// user and once for the item; a streaming kernel then sums the buckets (balanced over SLOT ranges, so a hot row of a
-// skewed id distribution is shared by many waves).  Same values as the per-sample path up to fp32 summation order;
-// the order inside a bucket follows the atomics, so table gradients are reproducible to rounding, not bitwise.
+// entries) and stores each sample's gz0 row ONCE, at the sample's own row of a (batch + 1, 64) buffer, plus a 16-byte
+// record {gz, partner id, row, sample} into the sample's slot of its user's bucket and of its item's, slot =
+// offset[row] + rank: a bucket is a run of records, and a record names the gz0 row and the partner GMF row of its
+// sample.  A streaming kernel then sums the buckets, fetching both rows through the record (balanced over SLOT ranges,
+// so a hot row of a skewed id distribution is shared by many waves).  Same values as the per-sample path up to fp32
+// summation order; the order inside a bucket follows the atomics, so table gradients are reproducible to rounding, not
+// bitwise.
 //
 // Launches: forward  ncfp_prep (projected tables, head fold) -> ncfp_fwd;   backward  ncfp_bwd -> reduce_segments_fold
 // (tower dW partials, head fold chain rule) -> ncfp_segsum -> ncfp_finish (the table-row products).
@@ -366,7 +369,7 @@ constexpr int64_t bwd_lds_floats(int64_t rows) {
 // 18944 + 16388 floats (138 of the 150 KB); the offsets would fit up to 19455 rows
 static_assert(bwd_lds_floats(CTR_NCF_PROJ_MAX_ROWS) <= kBwdLdsMax, "CTR_NCF_PROJ_MAX_ROWS: the backward's offsets do not fit in LDS");
 constexpr int kBwdDma = 12;                               // row fetches per group
-constexpr int kBwdStores = 10;                            // 8 bucket-row pieces + 2 slot records
+constexpr int kBwdStores = 6;                             // 4 pieces of the gz0 row + 2 slot records
 
 struct Bwd {
   Ids ids;
@@ -377,8 +380,9 @@ struct Bwd {
   int act;
   const int32_t* counts;                       // (nu + ni) from the forward
   const int32_t* ranks;                        // (m + 1, 2)
-  float* gz;                                   // (2m + 1, 64): buckets, user rows' slots first, one spare slot
-  float* aux;                                  // (2m + 1, 4): {gz, partner id, row, -} per slot
+  float* gz;                                   // (m + 1, 64): gz0 rows in sample order, one spare row
+  float* aux;                                  // (2m + 1, 4): {gz, partner id, row, sample} per slot, user rows' slots
+                                               // first, one spare slot
   int32_t* offsets;                            // (nu + ni + 1): written by workgroup 0 for the later launches
   float* slabs;                                // (grid, kSlab)
   float* zero_a; int64_t zero_a_floats;        // cleared first: the segment sums (nu + ni, 128)
@@ -638,23 +642,23 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
         for (int j = 0; j < 2; ++j) dw1[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(tg[0][c], y1t[j][c], dw1[j], 0, 0, 0);
     }
     STAMP(1, stamp++);   // head + layers 2, 1 done
-    // ---- layer 0 (64 -> 32): its input gradient, masked by relu'(z0), IS gz0 -- stored into the sample's two buckets
+    // ---- layer 0 (64 -> 32): its input gradient, masked by relu'(z0), IS gz0 -- stored once, at the sample's own row
     {
       f32x4 tg[2];
       tiles_get<2>(tA, q, lo, tg);
-      // a sample without a slot (bad id, padding lane) writes to the spare slot behind the buckets
-      float* du = B.gz + (int64_t)(su >= 0 ? su : 2 * m) * kN0 + 4 * q;
-      float* di = B.gz + (int64_t)(si >= 0 ? si : 2 * m) * kN0 + 4 * q;
+      // row b of the sample-ordered buffer (a group's sixteen rows are 4 KB in a piece); a padding lane writes the spare row m
+      const int brow = (int)(live ? g * 16 + lo : m);
+      float* dz = B.gz + (int64_t)brow * kN0 + 4 * q;
       dx_layer<0, 2>(s_wt, lane, gz1, w0, w1, [&](int j, const f32x4& d0, const f32x4& d1) {
-        const f32x4 g0 = relu_mask(d0, a0d[j]), g1 = relu_mask(d1, a0d[j + 1]);
-        stg4(du + 16 * j, g0);
-        stg4(du + 16 * (j + 1), g1);
-        stg4(di + 16 * j, g0);
-        stg4(di + 16 * (j + 1), g1);
+        stg4(dz + 16 * j, relu_mask(d0, a0d[j]));
+        stg4(dz + 16 * (j + 1), relu_mask(d1, a0d[j + 1]));
       });
-      // (the four lanes of a sample write the same record: an unconditional, countable store)
-      stg4(B.aux + (int64_t)(su >= 0 ? su : 2 * m) * 4, f32x4{gzs, __int_as_float(ii), __int_as_float(uu), 0.0f});
-      stg4(B.aux + (int64_t)(si >= 0 ? si : 2 * m) * 4, f32x4{gzs, __int_as_float(uu), __int_as_float((int)nu + ii), 0.0f});
+      // the sample's two slot records name its row; a sample without a slot (bad id, padding lane) writes the spare slot
+      // behind the records (the four lanes of a sample write the same record: an unconditional, countable store)
+      stg4(B.aux + (int64_t)(su >= 0 ? su : 2 * m) * 4,
+           f32x4{gzs, __int_as_float(ii), __int_as_float(uu), __int_as_float(brow)});
+      stg4(B.aux + (int64_t)(si >= 0 ? si : 2 * m) * 4,
+           f32x4{gzs, __int_as_float(uu), __int_as_float((int)nu + ii), __int_as_float(brow)});
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -729,7 +733,7 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
 struct Seg {
   const float* gz; const float* aux; const int32_t* offsets;
   const float* gmf_u; const float* gmf_i;
-  int64_t nu, ni;
+  int64_t nu, ni, m;
   float* st;                                   // (nu + ni, 128), zeroed
   int seg_blocks, red_blocks;                  // roles by blockIdx.x: [0, seg) segment sums, [seg, seg + red) slabs, last: fold
   const float* slabs; int parts;
@@ -889,7 +893,10 @@ ncfp_segsum_kernel(const Seg A) {
 #pragma unroll
     for (int k = 0; k < kSegBatch; ++k) {
       const int pid = __float_as_int(ax[k][1]), v = __float_as_int(ax[k][2]);
-      g[k] = ldg4(A.gz + slot(base + k) * kN0 + 4 * lo);
+      // the slot's gz0 row is the row of the sample its record names (clamped: records of a call that broke the
+      // counters' contract give wrong sums, not a read outside the buffer)
+      const uint32_t b = min((uint32_t)__float_as_int(ax[k][3]), (uint32_t)A.m);
+      g[k] = ldg4(A.gz + (int64_t)b * kN0 + 4 * lo);
       p[k] = ldg4((v < A.nu ? A.gmf_i : A.gmf_u) + (int64_t)pid * kP + 4 * lo);
     }
   };
@@ -936,9 +943,19 @@ ncfp_segsum_kernel(const Seg A) {
 }
 
 // ------------------------------------------------------------------ the products over the table rows
-// one wave = sixteen rows of one table:  dMLP[rows] += S . W0half,  dGMF[rows] += wf * T,  and its share of
-// dW0half += S^T . MLP,  db0 += column sums of S (user rows),  g_head_w[:64] += sum_rows GMF * T (user rows); the four
-// waves of a workgroup (same table) meet in LDS, one atomic per element and workgroup goes out.
+// Per sixteen rows of one table:  dMLP[rows] += S . W0half,  dGMF[rows] += wf * T,  and the rows' share of
+// dW0half += S^T . MLP,  db0 += column sums of S (user rows),  g_head_w[:64] += sum_rows GMF * T (user rows).
+// These pieces do not depend on each other, and the launch is as long as the longest chain one wave runs (a few
+// thousand table rows are a fraction of the chip): the grid is kFinParts copies of the row blocks, and a workgroup
+// (four waves = four row blocks of the same table) runs ONE piece for them:
+//   parts 0, 1 (h = part):      dW0half for the units [32h, 32h + 32) -- the four waves meet in LDS, one atomic per element
+//                               and workgroup goes out (splitting by UNITS leaves the number of atomics a line of g_w0
+//                               receives where it was; splitting by rows would multiply it) -- and, h = 0, the small sums
+//   parts 2, 3 (h = part - 2):  dMLP for the inputs [32h, 32h + 32) and dGMF for the columns of blocks 2h, 2h + 1: plain
+//                               read-modify-write of rows nobody else touches, no LDS, no atomics
+// Every operand of a piece is requested before any is consumed: they are independent of each other, and a load-use order
+// was eight dependent round trips (unconditional loads from a clamped row, zeroed afterwards: a load inside a
+// conditional is a round trip of its own).
 struct Fin {
   const float* st;                             // (nu + ni, 128)
   const float* mlp_u; const float* mlp_i; const float* gmf_u; const float* gmf_i;
@@ -949,19 +966,22 @@ struct Fin {
   float* g_w0; int64_t ldgw0; float* g_b0;                           // (+=), nullable
   float* g_head;                                                     // g of linear2.weight[:64] (+=), nullable
   int32_t* counts; int64_t ncounts;                                  // the step's sample counters: left all zero for the next forward
+  int wgs;                                                           // workgroups of one part: gridDim.x = kFinParts * wgs
 };
+constexpr int kFinParts = 4;
 
 __global__ void __launch_bounds__(kThreads)
 ncfp_finish_kernel(const Fin A) {
-  __shared__ __attribute__((aligned(16))) float s_dw[2][16 * 256];
+  __shared__ __attribute__((aligned(16))) float s_dw[2][8 * 256];
   __shared__ float s_sm[kWaves][2][64];
   const int lane = threadIdx.x & 63, q = lane >> 4, n = lane & 15, wave = threadIdx.x >> 6;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < A.ncounts; i += (int64_t)gridDim.x * kThreads)
     A.counts[i] = 0;    // (every reader -- the per-sample backward's scan -- is two launches back)
+  const int part = (int)blockIdx.x / A.wgs, wg = (int)blockIdx.x - part * A.wgs, h = part & 1;
   const int64_t ublocks = (A.nu + 15) / 16, iblocks = (A.ni + 15) / 16;
   const int64_t uwgs = (ublocks + kWaves - 1) / kWaves;
-  const bool user = (int64_t)blockIdx.x < uwgs;
-  const int64_t blk = (user ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - uwgs) * kWaves + wave;
+  const bool user = wg < uwgs;
+  const int64_t blk = (user ? (int64_t)wg : (int64_t)wg - uwgs) * kWaves + wave;
   const int64_t rows = user ? A.nu : A.ni, r0 = blk * 16;
   const bool any = blk < (user ? ublocks : iblocks);
   const float* st = A.st + (user ? 0 : A.nu) * 128;
@@ -973,35 +993,79 @@ ncfp_finish_kernel(const Fin A) {
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const int64_t row = r0 + n;
   const bool live = any && row < rows;
-  f32x4 dw[4][4];
+  const int64_t crow = live ? row : rows - 1;
+  const float keep = live ? 1.0f : 0.0f;
+
+  if (part >= 2) {
+    // ---- the rows' own gradients: inputs / columns of the blocks 2h, 2h + 1
+    if (!any || (!gtab && !ggmf)) return;
+    // sample-major operands: this lane's row n, columns 16j + 4q ..
+    f32x4 sd[4], td[2], og[2], ot[2], wf[2];
+    const float* ogp = ggmf ? ggmf : gmf;      // (a missing gradient buffer: read something valid, the store is skipped)
+    const float* otp = gtab ? gtab : tab;
 #pragma unroll
-  for (int b = 0; b < 4; ++b)
+    for (int j = 0; j < 4; ++j) sd[j] = ldg4(st + crow * 128 + 16 * j + 4 * q);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dw[b][j] = zero4;
+    for (int e = 0; e < 2; ++e) {
+      const int col = 16 * (2 * h + e) + 4 * q;
+      td[e] = ldg4(st + crow * 128 + 64 + col);
+      og[e] = ldg4(ogp + crow * kP + col);
+      ot[e] = ldg4(otp + crow * kH + col);
+      wf[e] = ldg4(A.wfold + col);
+    }
+    // A operands of dMLP, unit-major: W0[16j + 4q + c][coff + 16b + n], b = 2h + e
+    f32x4 wt[4][2];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wt[j][e][c] = A.w0[(int64_t)(16 * j + 4 * q + c) * A.ldw0 + coff + 16 * (2 * h + e) + n];
+    // dGMF[row] += wfold[:64] * T[row]
+    if (ggmf && live) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) stg4(ggmf + row * kP + 16 * (2 * h + e) + 4 * q, og[e] + wf[e] * td[e]);
+    }
+    // dMLP^T (32 inputs x 16 rows) = W0half^T (32 x 64 units) . S^T (64 units x 16 rows)
+    if (gtab) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sd[j] *= keep;
+      f32x4 acc[2] = {ot[0], ot[1]};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[j][e][c], sd[j][c], acc[e], 0, 0, 0);
+      if (live) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) stg4(gtab + row * kH + 16 * (2 * h + e) + 4 * q, acc[e]);
+      }
+    }
+    return;
+  }
+
+  // ---- the sums over the rows: dW0half for the units of blocks 2h, 2h + 1; h = 0: db0 and the head's GMF weights
+  const bool sums = h == 0 && user && (A.g_b0 || A.g_head);
+  if (!A.g_w0 && !sums) return;
+  f32x4 dw[2][4];
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dw[e][j] = zero4;
   f32x4 colsum[4], gw[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) colsum[j] = gw[j] = zero4;
   if (any) {
-    // every operand is requested before any is consumed: they are independent of each other, and a load-use order was
-    // eight dependent round trips on a handful of workgroups (12 us for 40 MFLOP)
-    // ---- sample-major operands: this lane's row n, columns 16j + 4q ..
-    // (unconditional loads from a clamped row, zeroed afterwards: a load inside a conditional is a round trip of its own)
-    f32x4 sd[4], td[4], gd[4], og[4], ot[4], wf[4];
-    const int64_t crow = live ? row : rows - 1;
-    const float* ogp = ggmf ? ggmf : gmf;      // (a missing gradient buffer: read something valid, the store is skipped)
-    const float* otp = gtab ? gtab : tab;
-    const float keep = live ? 1.0f : 0.0f;
+    f32x4 sd[4], td[4], gd[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       sd[j] = ldg4(st + crow * 128 + 16 * j + 4 * q);
       td[j] = ldg4(st + crow * 128 + 64 + 16 * j + 4 * q);
       gd[j] = ldg4(gmf + crow * kP + 16 * j + 4 * q);
-      og[j] = ldg4(ogp + crow * kP + 16 * j + 4 * q);
-      ot[j] = ldg4(otp + crow * kH + 16 * j + 4 * q);
-      wf[j] = ldg4(A.wfold + 16 * j + 4 * q);
     }
-    // ---- unit-major operands: unit / input n of rows 4q + c;  A operands of dMLP: W0[16j + 4q + c][coff + 16b + n]
-    f32x4 stt[4], xt[4], wt[4][4];
+    // unit-major operands: unit 16 (2h + e) + n / input 16j + n of rows 4q + c
+    f32x4 stt[2], xt[4];
     float okc[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -1009,94 +1073,69 @@ ncfp_finish_kernel(const Fin A) {
       const int64_t rr = r < rows ? r : rows - 1;
       okc[c] = r < rows ? 1.0f : 0.0f;
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        stt[b][c] = st[rr * 128 + 16 * b + n];
-        xt[b][c] = tab[rr * kH + 16 * b + n];
+      for (int e = 0; e < 2; ++e) stt[e][c] = st[rr * 128 + 16 * (2 * h + e) + n];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) wt[j][b][c] = A.w0[(int64_t)(16 * j + 4 * q + c) * A.ldw0 + coff + 16 * b + n];
-      }
+      for (int j = 0; j < 4; ++j) xt[j][c] = tab[rr * kH + 16 * j + n];
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      sd[j] *= keep;
-      td[j] *= keep;
+      gw[j] = gd[j] * (td[j] * keep);
+      colsum[j] = sd[j] * keep;
     }
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int e = 0; e < 2; ++e)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) stt[b][c] *= okc[c];
-    // dGMF[row] += wfold[:64] * T[row];   sum_rows GMF * T
-    if (ggmf && live) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) stg4(ggmf + row * kP + 16 * j + 4 * q, og[j] + wf[j] * td[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      gw[j] = gd[j] * td[j];
-      colsum[j] = sd[j];
-    }
-    // ---- dMLP^T (64 inputs x 16 rows) = W0half^T (64 x 64 units) . S^T (64 units x 16 rows)
-    if (gtab) {
-      f32x4 acc[4] = {ot[0], ot[1], ot[2], ot[3]};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[j][b][c], sd[j][c], acc[b], 0, 0, 0);
-      if (live) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) stg4(gtab + row * kH + 16 * b + 4 * q, acc[b]);
-      }
-    }
-    // ---- dW0half (64 units x 64 inputs) += S^T . X
+      for (int c = 0; c < 4; ++c) stt[e][c] *= okc[c];
+    // dW0half (32 units x 64 inputs) += S^T . X
     if (A.g_w0) {
 #pragma unroll
       for (int c = 0; c < 4; ++c)
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
+        for (int e = 0; e < 2; ++e)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) dw[b][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(stt[b][c], xt[j][c], dw[b][j], 0, 0, 0);
+          for (int j = 0; j < 4; ++j) dw[e][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(stt[e][c], xt[j][c], dw[e][j], 0, 0, 0);
     }
   }
   // ---- the workgroup's sums: waves 0 / 1 park their dW blocks, waves 2 / 3 add theirs in place (own lane slots)
   if (wave < 2) {
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int e = 0; e < 2; ++e)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(&s_dw[wave][((b * 4 + j) * 64 + lane) * 4]) = dw[b][j];
+      for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(&s_dw[wave][((e * 4 + j) * 64 + lane) * 4]) = dw[e][j];
   }
   __syncthreads();
   if (wave >= 2) {
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int e = 0; e < 2; ++e)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        f32x4* at = reinterpret_cast<f32x4*>(&s_dw[wave - 2][((b * 4 + j) * 64 + lane) * 4]);
-        *at = *at + dw[b][j];
+        f32x4* at = reinterpret_cast<f32x4*>(&s_dw[wave - 2][((e * 4 + j) * 64 + lane) * 4]);
+        *at = *at + dw[e][j];
       }
   }
+  if (sums) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float cs = row_sum16(colsum[j][r]), gs = row_sum16(gw[j][r]);
-      if (n == 0) {
-        s_sm[wave][0][16 * j + 4 * q + r] = cs;
-        s_sm[wave][1][16 * j + 4 * q + r] = gs;
+      for (int r = 0; r < 4; ++r) {
+        const float cs = row_sum16(colsum[j][r]), gs = row_sum16(gw[j][r]);
+        if (n == 0) {
+          s_sm[wave][0][16 * j + 4 * q + r] = cs;
+          s_sm[wave][1][16 * j + 4 * q + r] = gs;
+        }
       }
-    }
+  }
   __syncthreads();
   if (A.g_w0) {
-    for (int e = threadIdx.x; e < 64 * 64; e += kThreads) {
-      const int unit = e >> 6, k = e & 63;                     // dW0[unit][coff + k]
-      const int b = unit >> 4, qq = (unit >> 2) & 3, r = unit & 3, j = k >> 4, ll = k & 15;
+    for (int e = threadIdx.x; e < 32 * 64; e += kThreads) {
+      const int ul = e >> 6, k = e & 63, unit = 32 * h + ul;     // dW0[unit][coff + k]
+      const int b = ul >> 4, qq = (ul >> 2) & 3, r = ul & 3, j = k >> 4, ll = k & 15;
       const int at = ((b * 4 + j) * 64 + qq * 16 + ll) * 4 + r;
       const float v = s_dw[0][at] + s_dw[1][at];
       ctr_atomic_add_global(A.g_w0 + (int64_t)unit * A.ldgw0 + coff + k, v);
     }
   }
-  if (threadIdx.x < 64 && user) {
+  if (threadIdx.x < 64 && sums) {
     const int t = threadIdx.x;
     if (A.g_b0) ctr_atomic_add_global(A.g_b0 + t, (s_sm[0][0][t] + s_sm[1][0][t]) + (s_sm[2][0][t] + s_sm[3][0][t]));
     if (A.g_head) ctr_atomic_add_global(A.g_head + t, (s_sm[0][1][t] + s_sm[1][1][t]) + (s_sm[2][1][t] + s_sm[3][1][t]));
@@ -1143,9 +1182,10 @@ static int64_t workspace_floats(int64_t batch, int64_t num_users, int64_t num_it
   const int64_t groups = ctr_ceil_div(batch > 0 ? batch : 1, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
   if (grid > kSlabsMax) grid = kSlabsMax;
-  // buckets (2B + 1, 64) | slot records (2B + 1, 4) | segment sums (rows, 128) | offsets (rows + 1) | slabs
-  // (the spare slot 2B takes the stores of samples without a slot: bad ids, the padding lanes of the last group)
-  return (2 * batch + 1) * kN0 + (2 * batch + 1) * 4 + rows * 128 + (rows + 1 + 3) / 4 * 4 + grid * (int64_t)kSlab;
+  // gz0 rows (B + 1, 64) | slot records (2B + 1, 4) | segment sums (rows, 128) | offsets (rows + 1) | slabs
+  // (row B takes the stores of the last group's padding lanes, slot 2B the records of samples without a slot: bad ids,
+  // padding lanes)
+  return (batch + 1) * kN0 + (2 * batch + 1) * 4 + rows * 128 + (rows + 1 + 3) / 4 * 4 + grid * (int64_t)kSlab;
 }
 
 extern "C" int ctr_ncf_proj_workspace_floats(int64_t batch, int64_t num_users, int64_t num_items, int64_t* floats) {
@@ -1214,7 +1254,7 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   CTR_REQUIRE(g->workspace_floats >= workspace_floats(m, nu, ni) && ctr_aligned16(g->workspace), CTR_ELIMIT);
   // carve the workspace
   float* ws = g->workspace;
-  float* gzb = ws;            ws += (2 * m + 1) * kN0;
+  float* gzb = ws;            ws += (m + 1) * kN0;
   float* aux = ws;            ws += (2 * m + 1) * 4;
   float* stt = ws;            ws += rows * 128;
   int32_t* offs = reinterpret_cast<int32_t*>(ws); ws += (rows + 1 + 3) / 4 * 4;
@@ -1236,7 +1276,7 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   if (rc != CTR_OK) return rc;
   // segment sums over the buckets, and beside them (own workgroups) the tower's dW / db partials and the head fold's
   // chain rule (its GMF part arrives from ncfp_finish)
-  Seg S{gzb, aux, offs, d->gmf_user, d->gmf_item, nu, ni, stt, (int)ctr_ceil_div(2 * m, (kThreads / 16) * kSegRange),
+  Seg S{gzb, aux, offs, d->gmf_user, d->gmf_item, nu, ni, m, stt, (int)ctr_ceil_div(2 * m, (kThreads / 16) * kSegRange),
         (kSlabHead + 31) / 32,
         slabs, (int)grid, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, d->head_w, d->proj_w, d->ld_proj_w,
         d->proj_b, g->g_head_w, g->g_proj_w, g->ld_g_proj_w, g->g_proj_b, g->g_head_b};
@@ -1248,10 +1288,10 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
     hipLaunchKernelGGL(ncfp_segsum_kernel, dim3((unsigned)(S.seg_blocks + S.red_blocks + 1)), dim3(kThreads), 0, st, S);
   rc = ctr_launch_status();
   if (rc != CTR_OK) return rc;
+  const int64_t fwgs = ctr_ceil_div(ctr_ceil_div(nu, 16), kWaves) + ctr_ceil_div(ctr_ceil_div(ni, 16), kWaves);
   const Fin N{stt, d->mlp_user, d->mlp_item, d->gmf_user, d->gmf_item, d->layers[0].w, d->layers[0].k, d->wfold, nu, ni,
               g->g_mlp_user, g->g_mlp_item, g->g_gmf_user, g->g_gmf_item, g->layers[0].gw, d->layers[0].k, g->layers[0].gb,
-              g->g_head_w, d->counts, rows * kCountStride};
-  const int64_t fwgs = ctr_ceil_div(ctr_ceil_div(nu, 16), kWaves) + ctr_ceil_div(ctr_ceil_div(ni, 16), kWaves);
-  if (phases & 4) hipLaunchKernelGGL(ncfp_finish_kernel, dim3((unsigned)fwgs), dim3(kThreads), 0, st, N);
+              g->g_head_w, d->counts, rows * kCountStride, (int)fwgs};
+  if (phases & 4) hipLaunchKernelGGL(ncfp_finish_kernel, dim3((unsigned)(kFinParts * fwgs)), dim3(kThreads), 0, st, N);
   return ctr_launch_status();
 }

@@ -739,9 +739,9 @@ class NcfProj:
             # (+ in training, by the rank workgroups of the same launch: ids again, two returning atomics, an 8-byte record)
             "ncfp_fwd": lambda: (m * (16 + 4 * 256 + 4 * (32 + 16 + 8) + 4 + ((16 + 8 + 8) if self.training else 0)),
                                  2 * m * (tower + 72 + 64)),
-            # ids, prob, gprob, ranks, two projected rows, saved activations read; gz0 row stored twice + two records
-            "ncfp_bwd": lambda: (m * (16 + 16 + 2 * 256 + 4 * (32 + 16 + 8) + 2 * 256 + 32), 4 * m * tower + 2 * m * 8),
-            # both buckets (row + record) and one partner row per slot read, (rows, 128) sums added
+            # ids, prob, gprob, ranks, two projected rows, saved activations read; gz0 row stored once + two records
+            "ncfp_bwd": lambda: (m * (16 + 16 + 2 * 256 + 4 * (32 + 16 + 8) + 256 + 32), 4 * m * tower + 2 * m * 8),
+            # per slot: its record, the gz0 row and the partner row the record names read; (rows, 128) sums added
             "ncfp_segsum": lambda: (2 * m * (256 + 16 + 256) + rows * 512, 2 * 2 * m * 64 * 2),
             # sums + tables read, table gradients read-modify-written; three 64 x 64 products per row
             "ncfp_finish": lambda: (rows * (512 + 512 + 4 * 256), 3 * 2 * rows * 64 * 64),

@@ -468,7 +468,10 @@ int ctr_act_mask_bwd(float* g, int64_t ldg, const float* y, int64_t ldy, int64_t
  * is enqueued (its first launch takes every sample's rank with a returning atomic on them); ctr_ncf_proj_bwd's last
  * launch leaves them all zero again, so a caller that pairs every training forward with its backward zero-fills the
  * buffer once.  Parameters must not change between the forward and the backward (the backward re-reads tables and
- * ptab). */
+ * ptab).
+ * The backward's workspace (ctr_ncf_proj_workspace_floats): gz0 rows in sample order (batch + 1, 64) | slot records
+ * (2 batch + 1, 4) = {gz, partner id, row, sample}, the user rows' buckets first | segment sums (rows, 128) | bucket
+ * offsets (rows + 1) | the per-sample kernel's slabs. */
 #define CTR_NCF_PROJ_MAX_ROWS 16384
 #define CTR_NCF_PROJ_COUNT_STRIDE 16   /* int32 between the counters of two table rows: one 64-byte line each */
 typedef struct ctr_ncf_proj {
