@@ -20,7 +20,7 @@ DIN_TRIPLE, DIN_PAIR, DIN_H = 0, 1, 2  # layouts of the DIN attention operand (i
 
 CTR_MAX_FIELDS = 32
 CTR_NCF_PROJ_MAX_ROWS = 16384
-CTR_NCF_PROJ_COUNT_STRIDE = 16
+CTR_NCF_PROJ_COUNT_STRIDE = 72
 CTR_ROWS1_MAX_ROWS = 32768
 CTR_GDCF_MAX_DIM = 256
 FIELD_ID_I64, FIELD_ID_F32, FIELD_BAG, FIELD_DENSE, FIELD_PROD_I64 = range(5)
@@ -82,7 +82,7 @@ class NcfProj(C.Structure):
                 ("proj_w", C.c_void_p), ("ld_proj_w", C.c_int64), ("proj_b", C.c_void_p), ("proj_n", C.c_int32),
                 ("proj_k", C.c_int32), ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("head_act", C.c_int32),
                 ("prob", C.c_void_p), ("ldprob", C.c_int64), ("err_flag", C.c_void_p),
-                ("ptab", C.c_void_p), ("wfold", C.c_void_p), ("counts", C.c_void_p), ("ranks", C.c_void_p),
+                ("ptab", C.c_void_p), ("wfold", C.c_void_p), ("plan", C.c_void_p), ("ranks", C.c_void_p),
                 ("training", C.c_int32), ("phases", C.c_int32)]
 
 

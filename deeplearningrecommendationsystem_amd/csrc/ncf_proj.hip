@@ -15,18 +15,22 @@
 // (gz_b = the head's pre-activation gradient, a scalar per sample).  What is left per sample is the 64-32-16-8 tower,
 // the head's dot product and ONE 64-float row gz0[b] -- which is all the segment sums need.
 //
-// The segment sums are formed without a sort: the forward's id pass counts the samples of every row with returning
-// atomics (rank of a sample within its row), the backward kernel scans the counts (every workgroup for itself, 2625
-// entries) and stores each sample's gz0 row ONCE, at the sample's own row of a (batch + 1, 64) buffer, plus a 16-byte
-// record {gz, partner id, row, sample} into the sample's slot of its user's bucket and of its item's, slot =
-// offset[row] + rank: a bucket is a run of records, and a record names the gz0 row and the partner GMF row of its
-// sample.  A streaming kernel then sums the buckets, fetching both rows through the record (balanced over SLOT ranges,
-// so a hot row of a skewed id distribution is shared by many waves).  Same values as the per-sample path up to fp32
-// summation order; the order inside a bucket follows the atomics, so table gradients are reproducible to rounding, not
-// bitwise.
+// The segment sums are formed without a sort and without a global returning atomic.  The training forward builds a
+// bucket PLAN, once: the batch is cut into at most kChunks contiguous chunks, a workgroup per chunk (beside the
+// projection workgroups of ncfp_prep) counts the chunk's samples per table row in an LDS histogram -- the returning LDS
+// atomic is the sample's rank inside (row, chunk) -- and stores the histogram, zeros included; a few workgroups behind
+// the per-sample ones of ncfp_fwd turn every row's counts into exclusive prefixes over the chunks (base[chunk][row]) and
+// row totals, and the one that draws the last ticket scans the totals into rows + 1 bucket offsets.  The backward kernel
+// loads the offsets into LDS and stores each sample's gz0 row ONCE, at the sample's own row of a (batch + 1, 64) buffer,
+// plus a 16-byte record {gz, partner id, row, sample} into the sample's slot of its user's bucket and of its item's,
+// slot = offset[row] + base[chunk][row] + rank: a bucket is a run of records, and a record names the gz0 row and the
+// partner GMF row of its sample.  A streaming kernel then sums the buckets, fetching both rows through the record
+// (balanced over SLOT ranges, so a hot row of a skewed id distribution is shared by many waves).  Same values as the
+// per-sample path up to fp32 summation order; inside a bucket the chunks follow each other in batch order, the order
+// inside (row, chunk) follows the LDS atomics, so table gradients are reproducible to rounding, not bitwise.
 //
-// Launches: forward  ncfp_prep (projected tables, head fold) -> ncfp_fwd;   backward  ncfp_bwd -> reduce_segments_fold
-// (tower dW partials, head fold chain rule) -> ncfp_segsum -> ncfp_finish (the table-row products).
+// Launches: forward  ncfp_prep (projected tables, head fold, chunk histograms) -> ncfp_fwd (+ prefixes, offsets);
+// backward  ncfp_bwd -> ncfp_segsum (+ tower dW partials, head fold chain rule) -> ncfp_finish (the table-row products).
 #include "ctr_common.h"
 
 #include <stdlib.h>
@@ -54,31 +58,168 @@ __device__ unsigned long long g_stamps[2][64];
 #define STAMP(k, i) do {} while (0)
 #endif
 
-constexpr int kCountStride = CTR_NCF_PROJ_COUNT_STRIDE;   // int32 between two rows' sample counters
-
 struct Ids {
   const int64_t* uidx; int64_t ustride;
   const int64_t* iidx; int64_t istride;
   int64_t nu, ni;
 };
 
-// Ranks of the samples [lo, hi): a returning atomic per sample and id column on the row's counter, an 8-byte record out.
-// Run by workgroups `first` .. gridDim - 1 of a launch that has other work in its first workgroups (see struct Fwd).
+// ------------------------------------------------------------------ the bucket plan of a training forward
+// The caller's plan buffer (rows * CTR_NCF_PROJ_COUNT_STRIDE int32, rows = nu + ni):
+//   [0]                ticket of the prefix workgroups: zero at entry, re-armed by the one that draws the last
+//   base   [chunk][row]  after ncfp_prep: samples of `row` in `chunk`; after ncfp_fwd: the samples of `row` in EARLIER chunks
+//   totals [row]         samples of the row in the batch
+//   offsets[rows + 1]    exclusive scan of the totals (user rows first): where a row's bucket begins; [rows] = all slots
+// A chunk is 2^shift consecutive samples (at least one sample per thread of its workgroup, at most kChunks chunks), so
+// the chunk of a sample is a shift of its index.  Every entry a later launch reads is written by an earlier one, zeros
+// included: nothing but the ticket has to be clear, and nothing is cleared afterwards.
+constexpr int kChunks = 64;
+constexpr int kPlanHead = 4;                   // int32 in front of base (the ticket; keeps base 16-byte aligned)
+static_assert(kPlanHead + 2 * (kChunks + 2) + 1 <= 2 * CTR_NCF_PROJ_COUNT_STRIDE,
+              "CTR_NCF_PROJ_COUNT_STRIDE: the plan of the smallest tables (two rows) does not fit");
+struct Plan {
+  unsigned int* ticket;
+  int32_t* base; int32_t* totals; int32_t* offsets;
+  int64_t rows;
+  int shift, chunks;
+};
+Plan plan_of(int32_t* buf, int64_t rows, int64_t m) {
+  int shift = 8;
+  while (((int64_t)kChunks << shift) < m) ++shift;
+  Plan p;
+  p.ticket = reinterpret_cast<unsigned int*>(buf);
+  p.base = buf + kPlanHead;
+  p.totals = p.base + kChunks * rows;
+  p.offsets = p.totals + rows;
+  p.rows = rows;
+  p.shift = shift;
+  p.chunks = (int)((m + ((int64_t)1 << shift) - 1) >> shift);
+  return p;
+}
+
+// Ranks of one chunk, by workgroup `first` + chunk of a launch that has other work in its first workgroups: an LDS
+// histogram over the rows, a returning LDS atomic per sample and id column, an 8-byte record out, then the histogram.
+// All ids of a pass are requested before the first atomic (id -> atomic -> store, one sample after the other, is a chain
+// of round trips).  Ids sorted by user put a whole wave on one LDS counter: 64 serialised LDS operations, not 64
+// memory-side ones.
 struct RankJob {
   Ids ids;
-  int32_t* counts; int32_t* ranks;
-  int64_t lo, hi;
+  Plan plan; int32_t* ranks;
+  int64_t m;
   int first;
 };
+constexpr int kRankPer = 4;                    // samples of a thread in flight
 __device__ __forceinline__ void rank_role(const RankJob& R) {
-  const int64_t nb = (int64_t)gridDim.x - R.first;
-  for (int64_t s0 = R.lo + ((int64_t)blockIdx.x - R.first) * kThreads + threadIdx.x; s0 < R.hi; s0 += nb * kThreads) {
-    const int64_t u = R.ids.uidx[s0 * R.ids.ustride], i = R.ids.iidx[s0 * R.ids.istride];
-    int ru = -1, ri = -1;                      // an id outside its table has no slot (the per-sample part raises the flag)
-    if ((uint64_t)u < (uint64_t)R.ids.nu) ru = atomicAdd(R.counts + u * kCountStride, 1);
-    if ((uint64_t)i < (uint64_t)R.ids.ni) ri = atomicAdd(R.counts + (R.ids.nu + i) * kCountStride, 1);
-    *reinterpret_cast<int2*>(R.ranks + 2 * s0) = make_int2(ru, ri);
+  extern __shared__ __attribute__((aligned(16))) int s_hist[];   // rows
+  const int chunk = (int)blockIdx.x - R.first;
+  const int rows = (int)R.plan.rows;
+  for (int i = threadIdx.x; i < rows; i += kThreads) s_hist[i] = 0;
+  __syncthreads();
+  const int64_t lo = (int64_t)chunk << R.plan.shift;
+  const int64_t hi = lo + ((int64_t)1 << R.plan.shift) < R.m ? lo + ((int64_t)1 << R.plan.shift) : R.m;   // (lo < m: chunk < chunks)
+  for (int64_t s0 = lo + threadIdx.x; s0 < hi; s0 += kRankPer * kThreads) {
+    int64_t u[kRankPer], i[kRankPer];
+#pragma unroll
+    for (int e = 0; e < kRankPer; ++e) {
+      const int64_t s = s0 + e * kThreads < hi ? s0 + e * kThreads : hi - 1;
+      u[e] = R.ids.uidx[s * R.ids.ustride];
+      i[e] = R.ids.iidx[s * R.ids.istride];
+    }
+#pragma unroll
+    for (int e = 0; e < kRankPer; ++e) {
+      const int64_t s = s0 + e * kThreads;
+      if (s < hi) {
+        int ru = -1, ri = -1;                  // an id outside its table has no slot (the per-sample part raises the flag)
+        if ((uint64_t)u[e] < (uint64_t)R.ids.nu) ru = atomicAdd(s_hist + u[e], 1);
+        if ((uint64_t)i[e] < (uint64_t)R.ids.ni) ri = atomicAdd(s_hist + R.ids.nu + i[e], 1);
+        *reinterpret_cast<int2*>(R.ranks + 2 * s) = make_int2(ru, ri);
+      }
+    }
   }
+  __syncthreads();
+  int32_t* out = R.plan.base + (int64_t)chunk * rows;
+  for (int i = threadIdx.x; i < rows; i += kThreads) out[i] = s_hist[i];
+}
+
+// Prefixes and offsets, by workgroups `first` .. of the launch behind ncfp_prep: a thread per row turns the row's chunk
+// counts into exclusive prefixes, in place, and stores the row's total; the workgroup that draws the last ticket
+// (bce_fwd_kernel's pattern: nobody waits for anybody) scans the totals into the offsets, in `lds` (rows + 1 int32).
+struct PlanJob {
+  Plan plan;
+  int first;
+};
+__device__ __forceinline__ void plan_role(const PlanJob& J, int* lds) {
+  __shared__ int s_scan[kWaves];
+  __shared__ bool s_last;
+  const Plan& P = J.plan;
+  const int64_t rows = P.rows;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  {
+    const int64_t row = ((int64_t)blockIdx.x - J.first) * kThreads + threadIdx.x;
+    const int64_t rr = row < rows ? row : rows - 1;
+    int v[kChunks];
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) v[c] = P.base[(int64_t)(c < P.chunks ? c : P.chunks - 1) * rows + rr];
+    int run = 0;
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c)
+      if (c < P.chunks && row < rows) {
+        P.base[(int64_t)c * rows + row] = run;
+        run += v[c];
+      }
+    if (row < rows) __hip_atomic_store(P.totals + row, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // release this workgroup's totals, acquire everybody else's if it is the last
+    const unsigned int drawn = __hip_atomic_fetch_add(P.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = drawn == gridDim.x - (unsigned int)J.first - 1u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  // the totals into LDS, kCnt coalesced loads in flight per thread (rows past the end re-read the last)
+  constexpr int kCnt = 12;
+  for (int64_t base = 0; base < rows; base += kCnt * kThreads) {
+    int v[kCnt];
+#pragma unroll
+    for (int e = 0; e < kCnt; ++e) {
+      const int64_t i = base + e * kThreads + threadIdx.x;
+      v[e] = __hip_atomic_load(P.totals + (i < rows ? i : rows - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int e = 0; e < kCnt; ++e) {
+      const int64_t i = base + e * kThreads + threadIdx.x;
+      if (i < rows) lds[i] = v[e];
+    }
+  }
+  __syncthreads();
+  // exclusive scan (users, then items), in place
+  const int per = (int)((rows + kThreads - 1) / kThreads);
+  const int64_t i0 = (int64_t)threadIdx.x * per;
+  int sum = 0;
+  for (int e = 0; e < per; ++e)
+    if (i0 + e < rows) sum += lds[i0 + e];
+  int inc = sum;   // inclusive scan of `sum` over the workgroup's threads
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int v = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += v;
+  }
+  if (lane == 63) s_scan[wave] = inc;
+  __syncthreads();
+  int before = 0;
+  for (int w = 0; w < wave; ++w) before += s_scan[w];
+  int run = before + inc - sum;
+  for (int e = 0; e < per; ++e)
+    if (i0 + e < rows) {
+      const int c = lds[i0 + e];
+      lds[i0 + e] = run;
+      run += c;
+    }
+  if (threadIdx.x == kThreads - 1) lds[rows] = before + inc;
+  __syncthreads();
+  for (int64_t i = threadIdx.x; i <= rows; i += kThreads) P.offsets[i] = lds[i];
+  if (threadIdx.x == 0) __hip_atomic_store(P.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ------------------------------------------------------------------ prep: projected tables + head fold
@@ -90,7 +231,7 @@ struct Prep {
   // head fold (ctr_fold_head_fwd's map for p = 64, n = 64, k = 8): wfold[0:72], wfold[72] = cfold
   const float* fold_u; const float* fold_w; int64_t fold_ldw; const float* fold_b; const float* fold_b2;
   float* wfold;
-  RankJob rank;                                // training: the first part of the batch's ranks, by workgroups rank.first ..
+  RankJob rank;                                // training: the batch's ranks and chunk histograms, by workgroups rank.first ..
 };
 
 __global__ void __launch_bounds__(kThreads)
@@ -168,17 +309,13 @@ struct Fwd {
   const float* wfold;                          // 72 weights + the bias
   float* out; int64_t ldout; int act;
   int32_t* err_flag;
-  // training (counts != nullptr): workgroups fwd_blocks .. gridDim - 1 of the SAME launch take every sample's rank
-  // inside its user row and its item row -- a returning atomic on counts (ALL ZERO at entry; the backward's last launch
-  // leaves them zero again) -- and write ranks (m, 2) for the backward's bucketing.  They share the CUs with the
-  // per-sample workgroups (two workgroups' worth of LDS fit a CU) and are done before those are.  Inside the per-sample
-  // loop the same atomics cost 12 of the forward's 25.8 us: same-LINE atomics are served one after the other at the
-  // memory side (~30 ns each) and a wave's memory operations retire in order (profiles/r03_rank_atomics.txt).  The unit
-  // of that serialisation is the line, not the address: with the 2625 counters packed (164 lines, 800 adds each) the
-  // atomics alone took 23 us; every counter therefore has a line to itself (kCountStride int32 apart): 6 us.
-  // The batch's ranks are split over TWO launches: the first part beside the ~40 workgroups of the projection launch, the
-  // rest here -- each about as long as the work it runs beside.
-  RankJob rank;
+  // training: workgroups plan.first .. gridDim - 1 of the SAME launch finish the bucket plan whose chunk histograms the
+  // projection launch left (plan_role).  They share the CUs with the per-sample workgroups (two workgroups' worth of LDS
+  // fit a CU) and are done long before those are.  (Ranks by returning GLOBAL atomics, one per sample and id column,
+  // cost 12 of the forward's 25.8 us inside the per-sample loop and still 2-4 us on workgroups of their own with a
+  // 64-byte line per counter: same-line atomics are served one after the other at the memory side, ~30 ns each,
+  // profiles/r03_rank_atomics.txt.)
+  PlanJob plan;
 };
 
 // How the loops of this file are written (what the first version got wrong, found with cycle stamps, an ablation and
@@ -209,11 +346,11 @@ constexpr int kFwdStores = 5;            // y1 x 2, y2, y3, prob
 
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
-  if ((int)blockIdx.x >= F.rank.first) {
-    rank_role(F.rank);
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  if ((int)blockIdx.x >= F.plan.first) {
+    plan_role(F.plan, reinterpret_cast<int*>(lds));
     return;
   }
-  extern __shared__ __attribute__((aligned(16))) float lds[];
   float* s_w = lds;                                   // kWFloats
   float* s_b = s_w + kWFloats;                        // kBFloats
   float* s_hw = s_b + kBFloats;                       // kHeadW + 4 (+ 4 pad)
@@ -222,7 +359,7 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   float* stage = s_hw + 80 + wave * kFwdStage;        // this wave's rows: [table][row][chunk ^ row] x 16 bytes
   const uint32_t stage_addr = ctr_lds_addr(stage);
   const int64_t groups = (m + 15) / 16;
-  const int64_t wave0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6, nwaves = ((int64_t)F.rank.first * kThreads) >> 6;
+  const int64_t wave0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6, nwaves = ((int64_t)F.plan.first * kThreads) >> 6;
   const uint32_t nu = (uint32_t)F.ids.nu, ni = (uint32_t)F.ids.ni;
   const float* tabs[4] = {F.ptab, F.ptab + F.ids.nu * kN0, F.gmf_u, F.gmf_i};
   // stage 1: the two ids of this lane's sample (sample n of the group, the same in its four lanes)
@@ -378,12 +515,13 @@ struct Bwd {
   const float* prob; int64_t ldp;
   const float* gprob; int64_t ldgp;
   int act;
-  const int32_t* counts;                       // (nu + ni) from the forward
-  const int32_t* ranks;                        // (m + 1, 2)
+  const int32_t* base;                         // the forward's plan: [chunk][row] samples of the row in earlier chunks,
+  const int32_t* offsets;                      // (nu + ni + 1) bucket offsets,
+  int shift;                                   // chunk of sample s = s >> shift
+  const int32_t* ranks;                        // (m + 1, 2): rank of a sample inside (row, chunk)
   float* gz;                                   // (m + 1, 64): gz0 rows in sample order, one spare row
   float* aux;                                  // (2m + 1, 4): {gz, partner id, row, sample} per slot, user rows' slots
                                                // first, one spare slot
-  int32_t* offsets;                            // (nu + ni + 1): written by workgroup 0 for the later launches
   float* slabs;                                // (grid, kSlab)
   float* zero_a; int64_t zero_a_floats;        // cleared first: the segment sums (nu + ni, 128)
   float* zero_b; int64_t zero_b_floats;        // cleared first (nullable): the step's gradient buffer
@@ -397,7 +535,6 @@ __global__ void __launch_bounds__(kThreads)
 ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ __attribute__((aligned(16))) float s_hw[kHeadW + 4];
-  __shared__ int s_scan[kWaves];
   float* s_wt = lds;
   const int lane = threadIdx.x & 63, q = lane >> 4, lo = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -435,7 +572,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   };
   struct Scal {
     float gp, pb;
-    int ru, ri;                       // ranks of this lane's sample in its user / item row
+    int ru, ri;                       // ranks of this lane's sample in its user / item row, inside its chunk,
+    int bu, bi;                       // and the samples of those rows in earlier chunks
     uint32_t u, i;                    // its ids, clamped (bad ids: row 0, no slot)
     bool ubad, ibad;
   };
@@ -483,6 +621,9 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     r.pb = B.prob[rc * B.ldp];
     r.ru = B.ranks[2 * rc];
     r.ri = B.ranks[2 * rc + 1];
+    const int32_t* bc = B.base + (rc >> B.shift) * nrows;
+    r.bu = bc[r.u];
+    r.bi = bc[nu + r.i];
   };
   Scal sc;
   // ---- what a lane sums over every group it walks
@@ -503,20 +644,20 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     int wdst[kStagePer];
     stage_transposed_load(T, wv, wdst);
     const float hw = threadIdx.x <= kHeadW ? B.wfold[threadIdx.x] : 0.0f;
-    // the per-row sample counts into LDS, kCnt coalesced loads in flight per thread (rows past the end re-read the
-    // last): ml-100k's 2625 rows are ONE round trip (four in flight were three)
+    // the bucket offsets into LDS, kCnt coalesced loads in flight per thread (entries past the end re-read the last):
+    // ml-100k's 2626 are ONE round trip (four in flight were three)
     constexpr int kCnt = 12;
-    for (int64_t base = 0; base < nrows; base += kCnt * kThreads) {
+    for (int64_t base = 0; base <= nrows; base += kCnt * kThreads) {
       int v[kCnt];
 #pragma unroll
       for (int e = 0; e < kCnt; ++e) {
         const int64_t i = base + e * kThreads + threadIdx.x;
-        v[e] = B.counts[(i < nrows ? i : nrows - 1) * kCountStride];
+        v[e] = B.offsets[i <= nrows ? i : nrows];
       }
 #pragma unroll
       for (int e = 0; e < kCnt; ++e) {
         const int64_t i = base + e * kThreads + threadIdx.x;
-        if (i < nrows) s_off[i] = v[e];
+        if (i <= nrows) s_off[i] = v[e];
       }
     }
     issue_rows(wave0, sc);
@@ -525,40 +666,10 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     if (threadIdx.x <= kHeadW) s_hw[threadIdx.x] = hw;
   }
   __syncthreads();
-  STAMP(1, stamp++);   // weights staged, counts in LDS, first group requested
-  // ---- exclusive scan of the counts (users, then items), in place: every workgroup for itself
-  {
-    const int per = (int)((nrows + kThreads - 1) / kThreads);
-    const int64_t i0 = (int64_t)threadIdx.x * per;
-    int sum = 0;
-    for (int e = 0; e < per; ++e)
-      if (i0 + e < nrows) sum += s_off[i0 + e];
-    int inc = sum;   // inclusive scan of `sum` over the workgroup's threads
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += v;
-    }
-    if (lane == 63) s_scan[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_scan[w];
-    int run = base + inc - sum;
-    for (int e = 0; e < per; ++e)
-      if (i0 + e < nrows) {
-        const int c = s_off[i0 + e];
-        s_off[i0 + e] = run;
-        run += c;
-      }
-    if (threadIdx.x == kThreads - 1) s_off[nrows] = base + inc;
-    __syncthreads();
-    if (blockIdx.x == 0)
-      for (int64_t i = threadIdx.x; i <= nrows; i += kThreads) B.offsets[i] = s_off[i];
-  }
-  STAMP(1, stamp++);   // scan done
-  // the first group's rows and scalars, the second group's ids (nothing else is in flight but workgroup 0's offsets)
+  STAMP(1, stamp++);   // weights staged, offsets in LDS, first group requested
+  // the first group's rows and scalars, the second group's ids (nothing else is in flight)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("" : "+v"(idu), "+v"(idi), "+v"(sc.gp), "+v"(sc.pb), "+v"(sc.ru), "+v"(sc.ri));
+  asm volatile("" : "+v"(idu), "+v"(idi), "+v"(sc.gp), "+v"(sc.pb), "+v"(sc.ru), "+v"(sc.ri), "+v"(sc.bu), "+v"(sc.bi));
 
   for (int64_t g = wave0; g < groups; g += nwaves) {
     const bool live = g * 16 + lo < m;
@@ -591,8 +702,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
       }
     }
     const int uu = (int)sc.u, ii = (int)sc.i;
-    const int su = (live && !sc.ubad && sc.ru >= 0) ? sc.ru + s_off[uu] : -1;
-    const int si = (live && !sc.ibad && sc.ri >= 0) ? sc.ri + s_off[nu + ii] : -1;
+    const int su = (live && !sc.ubad && sc.ru >= 0) ? sc.ru + sc.bu + s_off[uu] : -1;
+    const int si = (live && !sc.ibad && sc.ri >= 0) ? sc.ri + sc.bi + s_off[nu + ii] : -1;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the stage is read: it may be overwritten
     STAMP(1, stamp++);   // operands read
     issue_rows(g + nwaves, sc);
@@ -670,7 +781,7 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     STAMP(1, stamp++);   // layer 0 done
     // the next group's rows, scalars and its successor's ids are older than this group's kBwdStores stores
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kBwdStores) : "memory");
-    asm volatile("" : "+v"(idu), "+v"(idi), "+v"(sc.gp), "+v"(sc.pb), "+v"(sc.ru), "+v"(sc.ri));
+    asm volatile("" : "+v"(idu), "+v"(idi), "+v"(sc.gp), "+v"(sc.pb), "+v"(sc.ru), "+v"(sc.ri), "+v"(sc.bu), "+v"(sc.bi));
   }
 
   // ---- the workgroup's partial: every wave parks its sums (weights, tiles and stages are dead), the four copies are
@@ -965,7 +1076,6 @@ struct Fin {
   float* g_mlp_u; float* g_mlp_i; float* g_gmf_u; float* g_gmf_i;   // (+=), nullable
   float* g_w0; int64_t ldgw0; float* g_b0;                           // (+=), nullable
   float* g_head;                                                     // g of linear2.weight[:64] (+=), nullable
-  int32_t* counts; int64_t ncounts;                                  // the step's sample counters: left all zero for the next forward
   int wgs;                                                           // workgroups of one part: gridDim.x = kFinParts * wgs
 };
 constexpr int kFinParts = 4;
@@ -975,8 +1085,6 @@ ncfp_finish_kernel(const Fin A) {
   __shared__ __attribute__((aligned(16))) float s_dw[2][8 * 256];
   __shared__ float s_sm[kWaves][2][64];
   const int lane = threadIdx.x & 63, q = lane >> 4, n = lane & 15, wave = threadIdx.x >> 6;
-  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < A.ncounts; i += (int64_t)gridDim.x * kThreads)
-    A.counts[i] = 0;    // (every reader -- the per-sample backward's scan -- is two launches back)
   const int part = (int)blockIdx.x / A.wgs, wg = (int)blockIdx.x - part * A.wgs, h = part & 1;
   const int64_t ublocks = (A.nu + 15) / 16, iblocks = (A.ni + 15) / 16;
   const int64_t uwgs = (ublocks + kWaves - 1) / kWaves;
@@ -1171,7 +1279,6 @@ extern "C" __attribute__((visibility("default"))) int ctr_ncfp_debug_stamps(unsi
 #endif
 
 // launch geometry (the round-3 sweeps that chose these values are in git history)
-constexpr int kRankSplit = 50;      // per cent of a training batch whose ranks the projection launch takes
 constexpr int kFwdWgs = 256;        // per-sample workgroups of the forward, at most
 constexpr int kBwdWgs = 256;        // per-sample workgroups of the backward, at most: one slab each
 constexpr int kSlabsMax = 768;      // workspace_floats() reserves slabs for this many backward workgroups
@@ -1182,10 +1289,10 @@ static int64_t workspace_floats(int64_t batch, int64_t num_users, int64_t num_it
   const int64_t groups = ctr_ceil_div(batch > 0 ? batch : 1, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
   if (grid > kSlabsMax) grid = kSlabsMax;
-  // gz0 rows (B + 1, 64) | slot records (2B + 1, 4) | segment sums (rows, 128) | offsets (rows + 1) | slabs
+  // gz0 rows (B + 1, 64) | slot records (2B + 1, 4) | segment sums (rows, 128) | slabs
   // (row B takes the stores of the last group's padding lanes, slot 2B the records of samples without a slot: bad ids,
-  // padding lanes)
-  return (batch + 1) * kN0 + (2 * batch + 1) * 4 + rows * 128 + (rows + 1 + 3) / 4 * 4 + grid * (int64_t)kSlab;
+  // padding lanes; the bucket offsets are the forward's: they live in its plan buffer)
+  return (batch + 1) * kN0 + (2 * batch + 1) * 4 + rows * 128 + grid * (int64_t)kSlab;
 }
 
 extern "C" int ctr_ncf_proj_workspace_floats(int64_t batch, int64_t num_users, int64_t num_items, int64_t* floats) {
@@ -1195,7 +1302,7 @@ extern "C" int ctr_ncf_proj_workspace_floats(int64_t batch, int64_t num_users, i
 }
 
 // `phases`: 0 = the whole call; else a mask of its launches (a profiler brackets them one by one): forward 1 = projected
-// tables + head fold, 2 = the per-sample kernel; backward 1 = the per-sample kernel, 2 = segment sums + slab reduction +
+// tables + head fold (+ chunk histograms), 2 = the per-sample kernel (+ the plan's prefixes and offsets); backward 1 = the per-sample kernel, 2 = segment sums + slab reduction +
 // head fold, 4 = the table-row products
 extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   CTR_REQUIRE(d && d->batch >= 0, CTR_EINVAL);
@@ -1203,7 +1310,7 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   if (!pattern_ok(d)) return CTR_ELIMIT;
   CTR_REQUIRE(d->prob && d->ldprob >= 1 && d->head_act >= CTR_ACT_NONE && d->head_act <= CTR_ACT_SIGMOID, CTR_EINVAL);
   CTR_REQUIRE(d->ld_proj_w >= d->proj_k, CTR_EINVAL);
-  CTR_REQUIRE(!d->training || (d->counts && d->ranks), CTR_EINVAL);
+  CTR_REQUIRE(!d->training || (d->plan && d->ranks), CTR_EINVAL);
   Tower T;
   int rc = fill_tower(&T, d->layers, true);
   if (rc != CTR_OK) return rc;
@@ -1211,38 +1318,42 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   const int64_t nu = d->num_users, ni = d->num_items;
   const int64_t pwaves = ctr_ceil_div(nu, 16) + ctr_ceil_div(ni, 16);
   const Ids ids{d->user_idx, d->user_stride, d->item_idx, d->item_stride, nu, ni};
-  // training: the samples' ranks, part in this launch, part in the next (RankJob)
-  const int64_t m_first = d->training ? d->batch * kRankSplit / 100 / kThreads * kThreads : 0;
+  // training: the bucket plan -- a rank workgroup per chunk in this launch, the prefix workgroups in the next
+  const bool ranks = d->training && d->batch > 0;
+  const Plan plan = plan_of(d->plan, nu + ni, d->batch);
   const int proj_blocks = (int)ctr_ceil_div(pwaves, kWaves) + 1;
-  int64_t rank_a = ctr_ceil_div(m_first, kThreads);
-  if (rank_a > 256) rank_a = 256;
   const Prep P{d->mlp_user, d->mlp_item, d->layers[0].w, d->layers[0].k, d->layers[0].b, d->ptab, nu, ni,
                d->head_w, d->proj_w, d->ld_proj_w, d->proj_b, d->head_b, d->wfold,
-               RankJob{ids, d->counts, d->ranks, 0, m_first, proj_blocks}};
-  if (phases & 1) hipLaunchKernelGGL(ncfp_prep_kernel, dim3((unsigned)(proj_blocks + rank_a)), dim3(kThreads), 0, st, P);
+               RankJob{ids, plan, d->ranks, d->batch, proj_blocks}};
+  const size_t prep_lds = ranks ? sizeof(int32_t) * (size_t)(nu + ni) : 0;   // a rank workgroup's histogram
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(sizeof(int32_t) * CTR_NCF_PROJ_MAX_ROWS)) != hipSuccess)
+    return CTR_ELAUNCH;
+  if (phases & 1)
+    hipLaunchKernelGGL(ncfp_prep_kernel, dim3((unsigned)(proj_blocks + (ranks ? plan.chunks : 0))), dim3(kThreads), prep_lds, st, P);
   rc = ctr_launch_status();
   if (rc != CTR_OK || d->batch == 0 || !(phases & 2)) return rc;
   const int64_t groups = ctr_ceil_div(d->batch, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
   // one workgroup per CU, every wave walks several groups: 25.6 us at batch 65536 against 28 us with two per CU
   if (grid > kFwdWgs) grid = kFwdWgs;
-  // rank workgroups (training): one sample per thread up to a chip's worth of them, behind the per-sample ones
-  int64_t rank_blocks = d->training ? ctr_ceil_div(d->batch - m_first, kThreads) : 0;
-  if (rank_blocks > 256) rank_blocks = 256;
+  // plan workgroups (training): a thread per table row, behind the per-sample ones
+  const int64_t plan_blocks = ranks ? ctr_ceil_div(nu + ni, kThreads) : 0;
   const Fwd F{ids, d->ptab, d->gmf_user, d->gmf_item, d->wfold, d->prob, d->ldprob, d->head_act, d->err_flag,
-              RankJob{ids, d->counts, d->ranks, m_first, d->training ? d->batch : m_first, (int)grid}};
+              PlanJob{plan, (int)grid}};
   constexpr size_t fwd_lds = sizeof(float) * (kWFloats + kBFloats + 80 + kWaves * kFwdStage);
+  static_assert(fwd_lds >= sizeof(int32_t) * (CTR_NCF_PROJ_MAX_ROWS + 1), "plan_role scans the offsets in the forward's LDS");
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)fwd_lds) != hipSuccess)
     return CTR_ELAUNCH;
-  hipLaunchKernelGGL(ncfp_fwd_kernel, dim3((unsigned)(grid + rank_blocks)), dim3(kThreads), fwd_lds, st, T, d->batch, F);
+  hipLaunchKernelGGL(ncfp_fwd_kernel, dim3((unsigned)(grid + plan_blocks)), dim3(kThreads), fwd_lds, st, T, d->batch, F);
   return ctr_launch_status();
 }
 
 extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad_t* g, void* stream) {
   CTR_REQUIRE(d && g && d->batch >= 0, CTR_EINVAL);
   if (!pattern_ok(d)) return CTR_ELIMIT;
-  CTR_REQUIRE(d->counts && d->ranks && d->prob && g->gprob && g->ldgprob >= 1 && g->workspace, CTR_EINVAL);
+  CTR_REQUIRE(d->plan && d->ranks && d->prob && g->gprob && g->ldgprob >= 1 && g->workspace, CTR_EINVAL);
   CTR_REQUIRE(!g->zero_buf || (ctr_aligned16(g->zero_buf) && g->zero_floats % 4 == 0 && g->zero_floats >= 0), CTR_EALIGN);
   Tower T;
   int rc = fill_tower(&T, d->layers, true);
@@ -1257,14 +1368,15 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   float* gzb = ws;            ws += (m + 1) * kN0;
   float* aux = ws;            ws += (2 * m + 1) * 4;
   float* stt = ws;            ws += rows * 128;
-  int32_t* offs = reinterpret_cast<int32_t*>(ws); ws += (rows + 1 + 3) / 4 * 4;
   float* slabs = ws;
   const int64_t groups = ctr_ceil_div(m, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
   if (grid > kBwdWgs) grid = kBwdWgs;
   const Ids ids{d->user_idx, d->user_stride, d->item_idx, d->item_stride, nu, ni};
-  const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, g->gprob, g->ldgprob, d->head_act, d->counts, d->ranks, gzb, aux,
-              offs, slabs, stt, rows * 128, g->zero_buf, g->zero_buf ? g->zero_floats : 0};
+  const Plan plan = plan_of(d->plan, rows, m);
+  const int32_t* offs = plan.offsets;
+  const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, g->gprob, g->ldgprob, d->head_act, plan.base, offs, plan.shift,
+              d->ranks, gzb, aux, slabs, stt, rows * 128, g->zero_buf, g->zero_buf ? g->zero_floats : 0};
   const size_t lds_bytes = sizeof(float) * (size_t)bwd_lds_floats(rows);
   CTR_REQUIRE(bwd_lds_floats(rows) <= kBwdLdsMax, CTR_ELIMIT);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1291,7 +1403,7 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   const int64_t fwgs = ctr_ceil_div(ctr_ceil_div(nu, 16), kWaves) + ctr_ceil_div(ctr_ceil_div(ni, 16), kWaves);
   const Fin N{stt, d->mlp_user, d->mlp_item, d->gmf_user, d->gmf_item, d->layers[0].w, d->layers[0].k, d->wfold, nu, ni,
               g->g_mlp_user, g->g_mlp_item, g->g_gmf_user, g->g_gmf_item, g->layers[0].gw, d->layers[0].k, g->layers[0].gb,
-              g->g_head_w, d->counts, rows * kCountStride, (int)fwgs};
+              g->g_head_w, (int)fwgs};
   if (phases & 4) hipLaunchKernelGGL(ncfp_finish_kernel, dim3((unsigned)(kFinParts * fwgs)), dim3(kThreads), 0, st, N);
   return ctr_launch_status();
 }

@@ -645,17 +645,18 @@ def act_mask_bwd(g, y, act: int) -> None:
 # NeuralCF with the first tower layer on the table rows (csrc/ncf_proj.hip)
 # ---------------------------------------------------------------------------
 class NcfCounts:
-    """the per-row sample counters of ``ctr_ncf_proj_fwd`` (one holder per model).  The C entry points want them all
-    zero at a training forward and leave them zero after the backward, so in the usual forward -> backward rhythm the
-    buffer is filled once, here.  ``take`` hands it out when it is known to be clean; while a forward's counts still
-    wait for their backward (two graphs alive at once), or after a training forward that never got one, a later
-    forward gets a freshly zeroed buffer of its own instead."""
+    """the bucket plan of ``ctr_ncf_proj_fwd`` (one holder per model): per-row sample counts of the batch's chunks,
+    row totals and bucket offsets, built by every training forward and read by its backward.  The C entry points want
+    its ticket zero at a training forward and leave it zero, so in the usual forward -> backward rhythm the buffer is
+    filled once, here.  ``take`` hands it out when no forward owns it; while a forward's plan still waits for its
+    backward (two graphs alive at once) a later forward gets a freshly zeroed buffer of its own instead, and after a
+    training forward that never got its backward the buffer is cleared before it is handed out again."""
 
     def __init__(self):
         self.buf, self.state = None, "clean"
 
     def take(self, rows: int, device):
-        n = rows * _lib.CTR_NCF_PROJ_COUNT_STRIDE      # a line per counter (ctrhip.h)
+        n = rows * _lib.CTR_NCF_PROJ_COUNT_STRIDE      # chunk counts, total and offset per row (ctrhip.h)
         if self.buf is None or self.buf.numel() < n or self.buf.device != device:
             self.buf, self.state = torch.zeros(n, dtype=torch.int32, device=device), "clean"
         if self.state == "dirty":            # a training forward whose graph was dropped without a backward
@@ -685,15 +686,15 @@ class NcfProj:
         self.prob_buf = torch.empty((m + 1, 1), dtype=torch.float32, device=dev)
         self.prob = self.prob_buf[:m]
         self._holder, self._owns = None, False
-        self.counts = self.ranks = None
+        self.plan = self.ranks = None
         if training:
             self._holder = counts if counts is not None else NcfCounts()
-            self.counts, self._owns = self._holder.take(rows, dev)
+            self.plan, self._owns = self._holder.take(rows, dev)
             self.ranks = torch.empty(2 * (m + 1), dtype=torch.int32, device=dev)
         self.err_flag, self.training = err_flag, training
 
     def __del__(self):
-        # a training forward that never saw its backward leaves the counters dirty
+        # a training forward that never saw its backward: the holder clears the plan before it hands it out again
         if getattr(self, "_owns", False) and self._holder.state == "busy":
             self._holder.state = "dirty"
 
@@ -715,9 +716,15 @@ class NcfProj:
         d.proj_w, d.ld_proj_w, d.proj_b, d.proj_n, d.proj_k = pw.data_ptr(), _ld(pw), _lib.ptr(pb), pw.shape[0], pw.shape[1]
         d.head_w, d.head_b, d.head_act = hw.data_ptr(), _lib.ptr(hb), ACT_SIGMOID
         d.prob, d.ldprob, d.err_flag = self.prob.data_ptr(), 1, _lib.ptr(self.err_flag)
-        d.ptab, d.wfold, d.counts, d.ranks = self.ptab.data_ptr(), self.wfold.data_ptr(), _lib.ptr(self.counts), _lib.ptr(self.ranks)
+        d.ptab, d.wfold, d.plan, d.ranks = self.ptab.data_ptr(), self.wfold.data_ptr(), _lib.ptr(self.plan), _lib.ptr(self.ranks)
         d.training = 1 if self.training else 0
         return d
+
+    def bucket_offsets(self) -> torch.Tensor:
+        """(rows + 1) int32 of the training forward's plan: row v's bucket is the slots [o[v], o[v + 1]), user rows first
+        (the plan's layout, csrc/ncf_proj.hip: 4 int32 of head, 64 chunks x rows prefixes, rows totals, the offsets)"""
+        rows = self.nu + self.ni
+        return self.plan[4 + 65 * rows: 4 + 66 * rows + 1]
 
     @staticmethod
     def supported(tables, hidden, proj, batch) -> bool:
@@ -732,15 +739,25 @@ class NcfProj:
     def _meta(self, which):
         m, rows = self.batch, self.nu + self.ni
         tower = 64 * 32 + 32 * 16 + 16 * 8
+        shift = 8                            # the plan's chunks of the batch (csrc/ncf_proj.hip, plan_of)
+        while (64 << shift) < m:
+            shift += 1
+        chunks = -(-m // (1 << shift))
         return {
             # (rows, 64) tables read, (rows, 64) projected rows written; one 64 x 64 product per row
-            "ncfp_prep": lambda: (rows * 512, 2 * rows * 64 * 64),
+            # (+ in training, by the rank workgroups of the same launch: ids, an 8-byte rank record per sample, a
+            # histogram of the rows per chunk)
+            "ncfp_prep": lambda: (rows * 512 + ((m * (16 + 8) + chunks * rows * 4) if self.training else 0),
+                                  2 * rows * 64 * 64),
             # ids, four 256-byte rows (cache-resident tables), saved activations + prob written; tower + head
-            # (+ in training, by the rank workgroups of the same launch: ids again, two returning atomics, an 8-byte record)
-            "ncfp_fwd": lambda: (m * (16 + 4 * 256 + 4 * (32 + 16 + 8) + 4 + ((16 + 8 + 8) if self.training else 0)),
+            # (+ in training, by the plan workgroups of the same launch: the histograms read and written back as
+            # prefixes, row totals, bucket offsets)
+            "ncfp_fwd": lambda: (m * (16 + 4 * 256 + 4 * (32 + 16 + 8) + 4) +
+                                 ((2 * chunks * rows * 4 + 3 * rows * 4) if self.training else 0),
                                  2 * m * (tower + 72 + 64)),
-            # ids, prob, gprob, ranks, two projected rows, saved activations read; gz0 row stored once + two records
-            "ncfp_bwd": lambda: (m * (16 + 16 + 2 * 256 + 4 * (32 + 16 + 8) + 256 + 32), 4 * m * tower + 2 * m * 8),
+            # ids, prob, gprob, ranks, two chunk prefixes, two projected rows, saved activations read; gz0 row stored
+            # once + two records
+            "ncfp_bwd": lambda: (m * (16 + 16 + 8 + 2 * 256 + 4 * (32 + 16 + 8) + 256 + 32), 4 * m * tower + 2 * m * 8),
             # per slot: its record, the gz0 row and the partner row the record names read; (rows, 128) sums added
             "ncfp_segsum": lambda: (2 * m * (256 + 16 + 256) + rows * 512, 2 * 2 * m * 64 * 2),
             # sums + tables read, table gradients read-modify-written; three 64 x 64 products per row
@@ -766,8 +783,8 @@ class NcfProj:
         """``grads[id(param)]``: where each parameter's gradient accumulates; ``zero``: the flat buffer behind them,
         cleared by the call's first launch"""
         if getattr(self, "_spent", False):
-            # the call's last launch clears the sample counters for the next forward: a second backward over the same
-            # forward would bucket with empty counters
+            # the first backward hands the plan buffer back to its holder: the next forward may have rebuilt it for
+            # other ids by the time a second backward over this forward would read it
             raise RuntimeError("NeuralCF backward consumes what its forward saved: run the forward again before a second "
                                "backward (retain_graph is not supported)")
         self._spent = True
@@ -799,7 +816,7 @@ class NcfProj:
                 rc = rc or _timed(label, self._meta(label), fn, C.byref(d), C.byref(g), _lib.stream_ptr())
         _lib.check(rc, "ctr_ncf_proj_bwd")
         if self._owns:
-            self._holder.state = "clean"     # (the call's last launch zeroed the counters)
+            self._holder.state = "clean"     # (the plan has been read; the forward left its ticket zero)
         self._owns = False
 
 

@@ -463,17 +463,19 @@ int ctr_act_mask_bwd(float* g, int64_t ldg, const float* y, int64_t ldy, int64_t
  * buffer has one spare row behind the batch (prob: m + 1 elements; ranks: 2 (m + 1) int32): lanes without a sample
  * store / read there, so that no store of the per-sample kernels is conditional.
  * Caller-owned buffers the forward fills for the backward: ptab (num_users + num_items, 64), wfold (76 floats), and
- * with training != 0: ranks and counts ((num_users + num_items) * CTR_NCF_PROJ_COUNT_STRIDE int32: a row's counter
- * has a 64-byte line to itself, same-line atomics are served one after the other).  counts must be ALL ZERO when a training forward
- * is enqueued (its first launch takes every sample's rank with a returning atomic on them); ctr_ncf_proj_bwd's last
- * launch leaves them all zero again, so a caller that pairs every training forward with its backward zero-fills the
- * buffer once.  Parameters must not change between the forward and the backward (the backward re-reads tables and
- * ptab).
+ * with training != 0: ranks (a sample's rank among the samples of its chunk of the batch that carry its user id, and
+ * the same for its item id) and plan ((num_users + num_items) * CTR_NCF_PROJ_COUNT_STRIDE int32: the bucket plan the
+ * forward builds from the ids -- per table row the sample counts of up to 64 chunks of the batch as exclusive
+ * prefixes, the row's total, the bucket offsets -- and the backward reads; csrc/ncf_proj.hip has the layout).  The
+ * forward writes every entry of the plan that is read later; only its first word, a ticket of the forward's second
+ * launch, must be ZERO when a training forward is enqueued, and that launch leaves it zero: a caller zero-fills the
+ * buffer once.  The plan belongs to ONE forward until its backward has run: two forwards in flight need a buffer each.
+ * Parameters must not change between the forward and the backward (the backward re-reads tables and ptab).
  * The backward's workspace (ctr_ncf_proj_workspace_floats): gz0 rows in sample order (batch + 1, 64) | slot records
- * (2 batch + 1, 4) = {gz, partner id, row, sample}, the user rows' buckets first | segment sums (rows, 128) | bucket
- * offsets (rows + 1) | the per-sample kernel's slabs. */
+ * (2 batch + 1, 4) = {gz, partner id, row, sample}, the user rows' buckets first | segment sums (rows, 128) | the
+ * per-sample kernel's slabs. */
 #define CTR_NCF_PROJ_MAX_ROWS 16384
-#define CTR_NCF_PROJ_COUNT_STRIDE 16   /* int32 between the counters of two table rows: one 64-byte line each */
+#define CTR_NCF_PROJ_COUNT_STRIDE 72   /* int32 of plan per table row: 64 chunk counts, total, offset, and room for the ticket */
 typedef struct ctr_ncf_proj {
   const int64_t* user_idx; int64_t user_stride;   /* ids of the batch, element strides */
   const int64_t* item_idx; int64_t item_stride;
@@ -486,7 +488,7 @@ typedef struct ctr_ncf_proj {
   const float* head_w; const float* head_b; int32_t head_act;                            /* `linear2` (1, 2 mf_dim) */
   float* prob; int64_t ldprob;                    /* (batch) output */
   int32_t* err_flag;                              /* nullable */
-  float* ptab; float* wfold; int32_t* counts; int32_t* ranks;
+  float* ptab; float* wfold; int32_t* plan; int32_t* ranks;
   int32_t training;
   int32_t phases;                                 /* 0: the whole call; else a mask of its launches (forward: 1 projected tables
                                                      + head fold, 2 per-sample kernel) -- for per-kernel timing */
