@@ -115,6 +115,22 @@ class RowsTable(C.Structure):
                 ("dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LoaderCol(C.Structure):
+    """mirror of ``ctr_loader_col_t``"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("lds", C.c_int64), ("ldd", C.c_int64),
+                ("width", C.c_int32), ("elem_bytes", C.c_int32)]
+
+
+class Loader(C.Structure):
+    """mirror of ``ctr_loader_t``"""
+    _fields_ = [("n", C.c_int64), ("ncols", C.c_int32), ("reserved", C.c_int32), ("cols", LoaderCol * CTR_MAX_FIELDS),
+                ("feat_users", C.c_void_p), ("feat_items", C.c_void_p), ("user_feat", C.c_void_p), ("item_feat", C.c_void_p),
+                ("num_users", C.c_int64), ("num_items", C.c_int64), ("user_width", C.c_int32), ("item_width", C.c_int32),
+                ("feat_out", C.c_void_p), ("feat_ldo", C.c_int64),
+                ("hist_users", C.c_void_p), ("history", C.c_void_p), ("hist_rows", C.c_int64), ("hist_len", C.c_int64),
+                ("ld_history", C.c_int64), ("hist_out", C.c_void_p), ("hist_ldo", C.c_int64), ("err_flag", C.c_void_p)]
+
+
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list every `ctr_*` symbol of include/ctrhip.h
@@ -172,6 +188,8 @@ SIGNATURES = {
     "ctr_mlp_bwd": (_i, [_p, _l, _l, C.POINTER(MlpLayer), _i, _p, _l, _p, _l, _p, _l, _p]),
     "ctr_negative_sample": (_i, [_p, _l, _l, _l, _i, C.c_uint64, _p, _p, _p, _p]),
     "ctr_assemble_features": (_i, [_p, _p, _l, _p, _i, _l, _p, _i, _l, _p, _l, _p, _p]),
+    "ctr_load_batch": (_i, [_p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p: address of a host Loader
+    "ctr_loader_indices": (_i, [_l, C.c_uint64, _l, _l, _l, _i, _p, _p]),
     "ctr_shard_bucket": (_i, [_p, _l, _i, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_bucket_padded": (_i, [_p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_recv_rows": (_i, [_p, _l, _l, _p, _p, _p, _p]),

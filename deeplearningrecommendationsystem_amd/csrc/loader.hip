@@ -1,0 +1,215 @@
+// Mini-batch loader: every tensor of one batch of a shuffled epoch in one launch (ctr_load_batch), and the shuffled
+// index on its own (ctr_loader_indices).  The reference trains full-batch (trainer/trainer.py:23-40: the same tensors
+// every epoch) and leaves data/dataloader.py and data/dataset.py empty; this is the layer a sample set larger than one
+// step needs.
+//
+// The shuffled index.  Position p (0 <= p < N) of epoch e under `seed` reads sample perm(seed, e, p):
+//     bits  = the smallest even number >= 2 with 2^bits >= N;   half = bits / 2;   mask = 2^half - 1
+//     key_r = mix64(seed ^ mix64(e * 0x100000001B3 + r)),  r = 0..3        (uint64, wrapping; mix64 as sampler.hip)
+//     E(x):   (L, R) = (x >> half, x & mask);  for r = 0..3:  (L, R) = (R, L ^ ((mix64(key_r ^ R) >> 32) & mask));
+//             E = (L << half) | R
+//     x = E(p);  while (x >= N) x = E(x);  perm = x
+// E is a balanced Feistel network, so a bijection of [0, 2^bits) whatever the round function is; following a
+// position's cycle until it re-enters [0, N) ("cycle walking") restricts it to a bijection of [0, N), and the walk
+// ends because p itself is below N.  2^bits < 4 N: fewer than 4 evaluations per element on average, for every N.
+// No permutation array, no sort, no state: the index of a position depends on (seed, e, p, N) only, not on the launch
+// geometry or on which batch asks for it.  tests/loader_numpy.py restates it.
+//
+// Integer and copy work only, bit-exact (the one conversion is the feature join's int -> float of the two id columns,
+// as assemble_kernel).  A workgroup takes 64 positions at a time: one wave computes their sample indices (and reads the
+// join ids) into LDS, then all four waves copy -- consecutive lanes take consecutive elements of a row, so a history
+// row (L int64) or a feature row is read and written in whole cache lines, and rows of 16-byte multiples move as
+// 16-byte pieces.
+#include "ctr_common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kTile = 64;  // positions per workgroup pass
+
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+struct LoaderPerm {
+  uint64_t key[4];
+  uint64_t n;
+  int32_t half;
+  int32_t shuffle;
+};
+
+LoaderPerm make_perm(int64_t n, uint64_t seed, int64_t epoch, int shuffle) {
+  LoaderPerm pm;
+  for (int r = 0; r < 4; ++r) pm.key[r] = mix64(seed ^ mix64((uint64_t)epoch * 0x100000001B3ull + (uint64_t)r));
+  int bits = 2;
+  while (bits < 62 && (1ull << bits) < (uint64_t)n) bits += 2;
+  pm.n = (uint64_t)n;
+  pm.half = bits / 2;
+  pm.shuffle = shuffle;
+  return pm;
+}
+
+__device__ __forceinline__ int64_t loader_index(const LoaderPerm& pm, int64_t p) {
+  if (!pm.shuffle) return p;
+  const uint64_t mask = (1ull << pm.half) - 1;
+  uint64_t x = (uint64_t)p;
+  do {
+    uint64_t l = x >> pm.half, r = x & mask;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t t = l ^ ((mix64(pm.key[k] ^ r) >> 32) & mask);
+      l = r;
+      r = t;
+    }
+    x = (l << pm.half) | r;
+  } while (x >= pm.n);
+  return (int64_t)x;
+}
+
+typedef uint32_t ctr_u32x4 __attribute__((ext_vector_type(4)));
+
+// row rows[s] of src -> row base + s of dst, s < cnt, w units of type T per row
+template <typename T>
+__device__ __forceinline__ void copy_rows(const void* src, int64_t lds, void* dst, int64_t ldd, int w, int cnt,
+                                          const int64_t* rows, int64_t base) {
+  const CTR_GLOBAL T* s = (const CTR_GLOBAL T*)src;
+  CTR_GLOBAL T* d = (CTR_GLOBAL T*)dst;
+  if (w == 1) {
+    for (int r = threadIdx.x; r < cnt; r += kBlock) d[(base + r) * ldd] = s[rows[r] * lds];
+    return;
+  }
+  const int total = cnt * w;
+  for (int g = threadIdx.x; g < total; g += kBlock) {
+    const int r = g / w;
+    const int j = g - r * w;
+    d[(base + r) * ldd + j] = s[rows[r] * lds + j];
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+load_batch_kernel(const ctr_loader_t d, const LoaderPerm pm, int64_t first, int64_t count, int hist16) {
+  __shared__ int64_t s_idx[kTile], s_fu[kTile], s_fi[kTile], s_hu[kTile];
+  const int64_t tiles = (count + kTile - 1) / kTile;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t base = tile * kTile;
+    const int cnt = (int)(count - base < kTile ? count - base : kTile);
+    if ((int)threadIdx.x < cnt) {
+      const int64_t idx = loader_index(pm, first + base + threadIdx.x);
+      s_idx[threadIdx.x] = idx;
+      bool bad = false;
+      if (d.feat_out) {
+        const int64_t u = ctr_ldg(d.feat_users + idx), i = ctr_ldg(d.feat_items + idx);
+        bad = u < 0 || u >= d.num_users || i < 0 || i >= d.num_items;
+        s_fu[threadIdx.x] = u;
+        s_fi[threadIdx.x] = i;
+      }
+      if (d.hist_out) {
+        int64_t u = ctr_ldg(d.hist_users + idx);
+        if (u < 0 || u >= d.hist_rows) {
+          bad = true;
+          u = 0;
+        }
+        s_hu[threadIdx.x] = u;
+      }
+      if (bad && d.err_flag) *(CTR_GLOBAL int32_t*)d.err_flag = 1;
+    }
+    __syncthreads();
+    for (int c = 0; c < d.ncols; ++c) {
+      const ctr_loader_col_t& col = d.cols[c];
+      if (col.elem_bytes == 8) copy_rows<uint64_t>(col.src, col.lds, col.dst, col.ldd, col.width, cnt, s_idx, base);
+      else copy_rows<uint32_t>(col.src, col.lds, col.dst, col.ldd, col.width, cnt, s_idx, base);
+    }
+    if (d.feat_out) {
+      const int uw = d.user_width, width = 2 + d.user_width + d.item_width;
+      const int total = cnt * width;
+      for (int g = threadIdx.x; g < total; g += kBlock) {
+        const int r = g / width;
+        const int c = g - r * width;
+        const int64_t u = s_fu[r], i = s_fi[r];
+        float v;
+        if (c == 0) v = (float)u;
+        else if (c == 1) v = (float)i;
+        else if (c < 2 + uw) v = ctr_ldg(d.user_feat + (u < 0 || u >= d.num_users ? 0 : u) * uw + (c - 2));
+        else v = ctr_ldg(d.item_feat + (i < 0 || i >= d.num_items ? 0 : i) * d.item_width + (c - 2 - uw));
+        ctr_stg(d.feat_out + (base + r) * d.feat_ldo + c, v);
+      }
+    }
+    if (d.hist_out) {
+      if (hist16)
+        copy_rows<ctr_u32x4>(d.history, d.ld_history / 2, d.hist_out, d.hist_ldo / 2, (int)(d.hist_len / 2), cnt, s_hu, base);
+      else
+        copy_rows<uint64_t>(d.history, d.ld_history, d.hist_out, d.hist_ldo, (int)d.hist_len, cnt, s_hu, base);
+    }
+    __syncthreads();  // the next pass rewrites the LDS rows
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+loader_indices_kernel(const LoaderPerm pm, int64_t first, int64_t count, int64_t* __restrict__ out) {
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (int64_t)gridDim.x * blockDim.x)
+    out[t] = loader_index(pm, first + t);
+}
+
+constexpr int64_t kMaxRowUnits = 1 << 20;  // cnt * width stays far inside int
+
+bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+int check_range(int64_t n, int64_t epoch, int64_t first, int64_t count) {
+  CTR_REQUIRE(n >= 1 && n <= (1ll << 62) && epoch >= 0 && first >= 0 && first <= n && count <= n - first, CTR_EINVAL);
+  return CTR_OK;
+}
+
+}  // namespace
+
+extern "C" int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t epoch, int64_t first, int64_t count,
+                              int shuffle, void* stream) {
+  CTR_REQUIRE(count >= 0, CTR_EINVAL);
+  if (count == 0) return CTR_OK;
+  CTR_REQUIRE(loader, CTR_EINVAL);
+  const ctr_loader_t& d = *loader;
+  if (int rc = check_range(d.n, epoch, first, count)) return rc;
+  CTR_REQUIRE(d.ncols >= 0 && d.ncols <= CTR_MAX_FIELDS, CTR_EINVAL);
+  for (int c = 0; c < d.ncols; ++c) {
+    const ctr_loader_col_t& col = d.cols[c];
+    CTR_REQUIRE(col.src && col.dst && col.width >= 1 && col.lds >= col.width && col.ldd >= col.width &&
+                    (col.elem_bytes == 4 || col.elem_bytes == 8),
+                CTR_EINVAL);
+    CTR_REQUIRE(col.width <= kMaxRowUnits, CTR_ELIMIT);
+    CTR_REQUIRE(aligned_to(col.src, col.elem_bytes) && aligned_to(col.dst, col.elem_bytes), CTR_EALIGN);
+  }
+  if (d.feat_out) {
+    CTR_REQUIRE(d.feat_users && d.feat_items && d.user_feat && d.item_feat && d.user_width >= 0 && d.item_width >= 0 &&
+                    d.num_users > 0 && d.num_items > 0 && d.feat_ldo >= 2 + (int64_t)d.user_width + d.item_width,
+                CTR_EINVAL);
+    CTR_REQUIRE(2 + (int64_t)d.user_width + d.item_width <= kMaxRowUnits, CTR_ELIMIT);
+  }
+  int hist16 = 0;
+  if (d.hist_out) {
+    CTR_REQUIRE(d.hist_users && d.history && d.hist_rows > 0 && d.hist_len >= 1 && d.ld_history >= d.hist_len &&
+                    d.hist_ldo >= d.hist_len,
+                CTR_EINVAL);
+    CTR_REQUIRE(d.hist_len <= kMaxRowUnits, CTR_ELIMIT);
+    CTR_REQUIRE(aligned_to(d.history, 8) && aligned_to(d.hist_out, 8), CTR_EALIGN);
+    hist16 = d.hist_len % 2 == 0 && d.ld_history % 2 == 0 && d.hist_ldo % 2 == 0 && ctr_aligned16(d.history) &&
+             ctr_aligned16(d.hist_out);
+  }
+  const int grid = ctr_stream_grid(count, kTile);
+  hipLaunchKernelGGL(load_batch_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d,
+                     make_perm(d.n, seed, epoch, shuffle != 0), first, count, hist16);
+  return ctr_launch_status();
+}
+
+extern "C" int ctr_loader_indices(int64_t n, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle,
+                                  int64_t* out, void* stream) {
+  CTR_REQUIRE(count >= 0, CTR_EINVAL);
+  if (count == 0) return CTR_OK;
+  if (int rc = check_range(n, epoch, first, count)) return rc;
+  CTR_REQUIRE(out, CTR_EINVAL);
+  const int grid = ctr_stream_grid(count, kBlock);
+  hipLaunchKernelGGL(loader_indices_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
+                     make_perm(n, seed, epoch, shuffle != 0), first, count, out);
+  return ctr_launch_status();
+}

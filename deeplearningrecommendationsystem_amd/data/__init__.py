@@ -1,3 +1,4 @@
 from .features import FeatureAssembler
+from .loader import DeviceLoader
 
-__all__ = ["FeatureAssembler"]
+__all__ = ["FeatureAssembler", "DeviceLoader"]

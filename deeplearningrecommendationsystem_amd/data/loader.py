@@ -1,0 +1,214 @@
+"""Device-side mini-batch loader: shuffled epochs over sample tensors that live on the device, one
+``ctr_load_batch`` launch per batch (csrc/loader.hip).  The reference trains full-batch and leaves its
+data/dataloader.py and data/dataset.py empty; this fills that slot for sample sets larger than one step.
+
+Position ``p`` of epoch ``e`` reads sample ``perm(seed, e, p)``, a stateless keyed permutation defined in the kernel
+file's header comment: no ``randperm``, no N-sized index tensor, no ``index_select`` per tensor.
+
+Batches and ranks (pure host arithmetic, ``batch_ranges``).  With F = N // batch_size full batches, every rank takes
+F // world of them, rank r the batches r, r + world, ... of the SAME permutation, so all ranks run the same number of
+full steps.  The positions behind those batches, [(F // world) * world * batch_size, N), are dropped with
+``drop_last``; otherwise they are cut into ``world`` contiguous pieces (the first ``rest % world`` one sample longer)
+and piece r is rank r's tail batch.  With world == 1 that is the usual N % batch_size tail.
+
+The loader owns one set of static full-size batch buffers -- what a captured training graph reads, see
+``Trainer.train_epoch`` -- and a separately allocated set for the tail batch.  ``epoch()`` yields views of them: a batch
+is valid until the next one is drawn.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from .. import _lib
+
+
+def batch_ranges(n: int, batch_size: int, drop_last: bool = False, rank: int = 0, world: int = 1):
+    """[(first position, count)] of one rank's batches in an epoch of ``n`` samples (module docstring)"""
+    if n < 1 or batch_size < 1:
+        raise ValueError("batch_ranges(): n and batch_size must be positive")
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("batch_ranges(): need 0 <= rank < world")
+    per_rank = (n // batch_size) // world
+    out = [((k * world + rank) * batch_size, batch_size) for k in range(per_rank)]
+    used = per_rank * world * batch_size
+    rest = n - used
+    if not drop_last and rest > 0:
+        base, extra = divmod(rest, world)
+        count = base + (1 if rank < extra else 0)
+        if count:
+            out.append((used + rank * base + min(rank, extra), count))
+    return out
+
+
+class _Column:
+    """an (N,) or (N, w) int64 / float32 source copied row by row"""
+
+    def __init__(self, name, src):
+        if src.dtype not in (torch.int64, torch.float32) or src.dim() not in (1, 2):
+            raise ValueError(f"DeviceLoader: {name} must be an (N,) or (N, w) int64 or float32 tensor")
+        self.src = src.contiguous()
+        self.width = 1 if src.dim() == 1 else src.shape[1]
+        if self.width < 1:
+            raise ValueError(f"DeviceLoader: {name} has no columns")
+
+    def buffer(self, rows):
+        return torch.empty((rows,) + tuple(self.src.shape[1:]), dtype=self.src.dtype, device=self.src.device)
+
+    def describe(self, col, dst):
+        col.src, col.dst = self.src.data_ptr(), dst.data_ptr()
+        col.lds = col.ldd = col.width = self.width
+        col.elem_bytes = self.src.element_size()
+
+
+class _Buffers:
+    """one set of batch outputs and the descriptor that fills them"""
+
+    def __init__(self, loader, rows):
+        self.desc = d = _lib.Loader()
+        d.n = loader.num_samples
+        d.ncols = len(loader._columns)
+        self.cols = []
+        for k, c in enumerate(loader._columns):
+            self.cols.append(c.buffer(rows))
+            c.describe(d.cols[k], self.cols[k])
+        self.feat = self.hist = None
+        dev = loader.device
+        if loader._feature is not None:
+            asm, users, items = loader._feature
+            self.feat = torch.empty((rows, asm.width), dtype=torch.float32, device=dev)
+            d.feat_users, d.feat_items = users.data_ptr(), items.data_ptr()
+            d.user_feat, d.item_feat = asm.user_features.data_ptr(), asm.item_features.data_ptr()
+            d.num_users, d.user_width = asm.user_features.shape
+            d.num_items, d.item_width = asm.item_features.shape
+            d.feat_out, d.feat_ldo = self.feat.data_ptr(), self.feat.stride(0)
+        if loader._history is not None:
+            history, users = loader._history
+            self.hist = torch.empty((rows, history.shape[1]), dtype=torch.int64, device=dev)
+            d.hist_users, d.history = users.data_ptr(), history.data_ptr()
+            d.hist_rows, d.hist_len = history.shape
+            d.ld_history = history.stride(0)
+            d.hist_out, d.hist_ldo = self.hist.data_ptr(), self.hist.stride(0)
+        d.err_flag = loader._err.data_ptr()
+
+    def batch(self, family):
+        rating = self.cols[-1]
+        if family == "pairs":
+            return (self.cols[0], self.cols[1]), rating
+        if family == "features":
+            return (self.feat,), rating
+        return (self.hist, self.cols[0]), rating
+
+
+class DeviceLoader:
+    """Shuffled mini-batches of device-resident samples; build one with ``pairs``, ``features`` or ``sequences``.
+
+    ``for args, rating in loader.epoch(e)`` draws this rank's batches of epoch ``e``: ``model(*args)`` against
+    ``rating``.  ``len(loader)`` batches; the full-size ones are views of ``static_batch()``."""
+
+    def __init__(self, family, columns, ids, feature, history, batch_size, seed, shuffle, drop_last, rank, world):
+        if int(batch_size) < 1:
+            raise ValueError("DeviceLoader: batch_size must be positive")
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError("DeviceLoader: need 0 <= rank < world")
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("DeviceLoader: seed must fit an unsigned 64-bit integer")
+        samples = [t for _, t in columns] + list(ids)
+        tables = [feature.user_features, feature.item_features] if feature is not None else []
+        _lib.require_device(*samples, *tables, history)
+        if any(t.dtype != torch.int64 or t.dim() != 1 for t in ids):
+            raise ValueError("DeviceLoader: the id columns must be 1-D int64 tensors")
+        self._columns = [_Column(name, t) for name, t in columns]
+        n = samples[0].shape[0]
+        if n < 1 or any(t.shape[0] != n for t in samples):
+            raise ValueError("DeviceLoader: the sample tensors must have one length, at least 1")
+        if history is not None and (history.dtype != torch.int64 or history.dim() != 2 or 0 in history.shape):
+            raise ValueError("DeviceLoader: history must be a (U, L) int64 matrix")
+        self.family, self.num_samples, self.device = family, n, samples[0].device
+        self.batch_size, self.seed, self.shuffle = int(batch_size), int(seed), bool(shuffle)
+        self.drop_last, self.rank, self.world = bool(drop_last), int(rank), int(world)
+        ids = [t.contiguous() for t in ids]
+        self._feature = None if feature is None else (feature, ids[0], ids[1])
+        self._history = None if history is None else (history.contiguous(), ids[0])
+        self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._ranges = batch_ranges(n, self.batch_size, self.drop_last, self.rank, self.world)
+        # a tail piece that happens to hold batch_size samples is still the tail: it has its own buffers
+        self._num_full = (n // self.batch_size) // self.world
+        tail = self._ranges[-1][1] if len(self._ranges) > self._num_full else 0
+        self._full = _Buffers(self, self.batch_size) if self._num_full else None
+        self._tail = _Buffers(self, tail) if tail else None
+
+    # -- constructors ------------------------------------------------------------------------------------------
+    @classmethod
+    def pairs(cls, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0, world=1):
+        """MF / NeuralCF: batches ``(user_idx (B,), item_idx (B,)), rating`` -- rating (N,) or (N, 1) float32"""
+        cols = [("users", users), ("items", items), ("ratings", ratings)]
+        return cls("pairs", cols, [users, items], None, None, batch_size, seed, shuffle, drop_last, rank, world)
+
+    @classmethod
+    def features(cls, assembler, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
+                 world=1):
+        """feature models: batches ``(x (B, assembler.width),), rating`` -- x as ``assembler.feature`` builds it"""
+        return cls("features", [("ratings", ratings)], [users, items], assembler, None, batch_size, seed, shuffle,
+                   drop_last, rank, world)
+
+    @classmethod
+    def sequences(cls, history, users, targets, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
+                  world=1):
+        """DIN / DIEN: batches ``(hist (B, L), target (B,)), rating`` -- hist row = ``history[users[sample]]``,
+        ``history`` one (U, L) int64 row per USER"""
+        cols = [("targets", targets), ("ratings", ratings)]
+        return cls("sequences", cols, [users, targets], None, history, batch_size, seed, shuffle, drop_last, rank, world)
+
+    # -- batches -----------------------------------------------------------------------------------------------
+    def __len__(self):
+        return len(self._ranges)
+
+    @property
+    def ranges(self):
+        """[(first position, count)] of this rank's batches"""
+        return list(self._ranges)
+
+    @property
+    def num_rank_samples(self):
+        return sum(count for _, count in self._ranges)
+
+    def static_batch(self):
+        """``(args, rating)`` over the static full-size buffers (what every full batch is written to), or None when
+        this rank has no full batch"""
+        return None if self._full is None else self._full.batch(self.family)
+
+    def _launch(self, buffers, epoch, first, count, shuffle):
+        rc = _lib.load().ctr_load_batch(C.addressof(buffers.desc), self.seed, epoch, first, count, int(shuffle),
+                                        _lib.stream_ptr())
+        _lib.check(rc, "ctr_load_batch")
+
+    def epoch(self, epoch: int, shuffle=None):
+        """yield ``(args, rating)`` for every batch of this rank; ``shuffle`` overrides the loader's setting (an
+        evaluation pass asks for the identity order)"""
+        if int(epoch) < 0:
+            raise ValueError("DeviceLoader.epoch(): epoch must be non-negative")
+        shuffle = self.shuffle if shuffle is None else bool(shuffle)
+        for k, (first, count) in enumerate(self._ranges):
+            buffers = self._full if k < self._num_full else self._tail
+            self._launch(buffers, int(epoch), first, count, shuffle)
+            yield buffers.batch(self.family)
+
+    def indices(self, epoch: int, first: int = 0, count=None, shuffle=None) -> torch.Tensor:
+        """sample indices of positions [first, first + count) of epoch ``epoch`` (int64, on the device)"""
+        count = self.num_samples - first if count is None else count
+        if epoch < 0 or first < 0 or count < 0 or first + count > self.num_samples:
+            raise ValueError("DeviceLoader.indices(): position range outside the epoch")
+        shuffle = self.shuffle if shuffle is None else bool(shuffle)
+        out = torch.empty(count, dtype=torch.int64, device=self.device)
+        rc = _lib.load().ctr_loader_indices(self.num_samples, self.seed, int(epoch), int(first), int(count), int(shuffle),
+                                            out.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "ctr_loader_indices")
+        return out
+
+    def check_bad_index(self):
+        """raise the IndexError of an id outside its join table seen by any batch since the last call"""
+        if int(self._err.item()):
+            self._err.zero_()
+            raise IndexError("index out of range in self")

@@ -88,6 +88,78 @@ class Trainer:
             self.test_rating = test_matrix[mask]
             self.test_loss = self.loss_fn(self.predictions_test, self.test_rating)
 
+    # mini-batch epochs over a data.DeviceLoader (no counterpart in the reference, which trains full-batch)
+    def _eager_batch(self, args, rating):
+        """one eager step that leaves the captured graph usable: the graph's replays write the .grad tensors made at
+        capture, and zero_grad(set_to_none=True) would put fresh ones in their place, so they are set aside"""
+        params = [p for group in self.optimizer.param_groups for p in group["params"]]
+        kept = [p.grad for p in params] if self._graphed is not None else None
+        self.optimizer.zero_grad()
+        pred = self._forward(args)
+        loss = self.loss_fn(pred, rating)
+        loss.backward()
+        self.optimizer.step()
+        if kept is not None:
+            for p, g in zip(params, kept):
+                p.grad = g
+        return pred, loss
+
+    def train_epoch(self, loader, epoch):
+        """one optimizer step per batch of ``loader.epoch(epoch)``.  With ``graph=True`` the full-size batches replay
+        ONE graph captured over the loader's static buffers (the loader launch runs eagerly in front of each replay);
+        the tail batch has buffers of its own and runs eagerly, so it never replaces the captured graph.
+        ``train_loss``: sample-weighted mean of the batch losses; predictions / rating: those of the last batch."""
+        self.model.train()
+        static = loader.static_batch()
+        total = torch.zeros((), dtype=torch.float64, device=loader.device)
+        samples = 0
+        pred = rating = None
+        for args, rating in loader.epoch(epoch):
+            if self._graph and static is not None and rating is static[1]:
+                key = tuple(t.data_ptr() for t in args) + (rating.data_ptr(),)
+                if self._graphed is None or key != self._graph_key:
+                    from ..graph import GraphedStep
+                    self._graphed = GraphedStep(self.model, self.loss_fn, args, rating)
+                    self._graph_key = key
+                loss, pred = self._graphed(), self._graphed.prob
+                self.optimizer.step()
+            else:
+                pred, loss = self._eager_batch(args, rating)
+            total.add_(loss.detach(), alpha=rating.shape[0])
+            samples += rating.shape[0]
+        if samples == 0:
+            raise ValueError("train_epoch: the loader has no batch for this rank")
+        self.train_loss = (total / samples).float()
+        self.predictions_train, self.train_rating = pred, rating
+
+    def _eval_epoch(self, loader):
+        """unshuffled pass under no_grad -> (predictions (N, ...), ratings (N, ...), sample-weighted mean loss)"""
+        self.model.eval()
+        n = loader.num_rank_samples
+        if n == 0:
+            raise ValueError("the loader has no batch for this rank")
+        total = torch.zeros((), dtype=torch.float64, device=loader.device)
+        preds = ratings = None
+        done = 0
+        with torch.no_grad():
+            for args, rating in loader.epoch(0, shuffle=False):
+                pred = self._forward(args)
+                if preds is None:
+                    preds = torch.empty((n,) + tuple(pred.shape[1:]), dtype=pred.dtype, device=pred.device)
+                    ratings = torch.empty((n,) + tuple(rating.shape[1:]), dtype=rating.dtype, device=rating.device)
+                count = rating.shape[0]
+                preds[done:done + count] = pred
+                ratings[done:done + count] = rating
+                total.add_(self.loss_fn(pred, rating), alpha=count)
+                done += count
+        return preds, ratings, (total / n).float()
+
+    def valid_epoch(self, loader):
+        self.predictions_valid, self.valid_rating, self.valid_loss = self._eval_epoch(loader)
+
+    def test_epoch(self, loader):
+        self.predictions_test, self.test_rating, self.test_loss = self._eval_epoch(loader)
+
     def model_eval(self, epoch):
         """prints the reference's per-epoch report (trainer/trainer.py:116-146)"""
         # the report syncs on loss.item() anyway: the place to surface a bad id seen by any step since the

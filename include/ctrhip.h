@@ -688,6 +688,61 @@ int ctr_assemble_features(const int64_t* users, const int64_t* items, int64_t n,
                           int64_t num_items, float* out, int64_t ldo, int32_t* err_flag, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Mini-batch loader: one launch builds every tensor of one batch of a shuffled epoch.  (The reference trains
+ * full-batch, trainer/trainer.py:23-40; its data/dataloader.py and data/dataset.py are empty.)
+ * Position p of epoch e reads sample perm(seed, e, p): a keyed 4-round Feistel network with cycle walking,
+ * defined in the header comment of csrc/loader.hip -- stateless, no permutation array, independent of the launch
+ * geometry.  shuffle == 0 makes the index the identity.
+ * The descriptor is a host struct, copied by value into the launch:
+ *   cols      each (n, width) source of 4- or 8-byte elements (float32 / int64), row idx copied to row b of dst;
+ *   feature   (feat_out non-null)  feat_out[b, :] = what ctr_assemble_features writes for
+ *             (feat_users[idx], feat_items[idx]), the id columns as floats included;
+ *   history   (hist_out non-null)  hist_out[b, :hist_len] = history[hist_users[idx], :hist_len].
+ * An id of a join outside its table raises *err_flag (nullable) and reads row 0.
+ * ctr_load_batch writes the batch of positions [first, first + count), first + count <= n.
+ * ctr_loader_indices writes their sample indices to out (count int64): the permutation alone, for inspection.
+ * count == 0 is a no-op; n < 1, a negative epoch or first, or a range beyond n is CTR_EINVAL.
+ * ---------------------------------------------------------------------- */
+typedef struct ctr_loader_col {
+  const void* src;      /* (n, width) elements, leading dimension lds */
+  void* dst;            /* (count, width) elements, leading dimension ldd */
+  int64_t lds;
+  int64_t ldd;
+  int32_t width;        /* >= 1 */
+  int32_t elem_bytes;   /* 4 or 8 */
+} ctr_loader_col_t;
+
+typedef struct ctr_loader {
+  int64_t n;                    /* samples */
+  int32_t ncols;                /* <= CTR_MAX_FIELDS */
+  int32_t reserved;
+  ctr_loader_col_t cols[CTR_MAX_FIELDS];
+  const int64_t* feat_users;    /* (n,) */
+  const int64_t* feat_items;    /* (n,) */
+  const float* user_feat;       /* (num_users, user_width) */
+  const float* item_feat;       /* (num_items, item_width) */
+  int64_t num_users;
+  int64_t num_items;
+  int32_t user_width;
+  int32_t item_width;
+  float* feat_out;              /* (count, 2 + user_width + item_width), NULL = no feature join */
+  int64_t feat_ldo;
+  const int64_t* hist_users;    /* (n,) */
+  const int64_t* history;       /* (hist_rows, hist_len), leading dimension ld_history */
+  int64_t hist_rows;
+  int64_t hist_len;
+  int64_t ld_history;
+  int64_t* hist_out;            /* (count, hist_len), NULL = no history join */
+  int64_t hist_ldo;
+  int32_t* err_flag;            /* device int32, nullable */
+} ctr_loader_t;
+
+int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle,
+                   void* stream);
+int ctr_loader_indices(int64_t n, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle, int64_t* out,
+                       void* stream);
+
+/* ------------------------------------------------------------------------
  * Head folding: a linear layer W (n x k, bias b) whose output feeds ONLY a single-unit layer u is the
  * k-wide dot product  (h W^T + b).u + b2 == h.v + c,  v = W^T u,  c = b.u + b2.  NeuralCF ends like
  * that (model/neuralcf.py:27 linear, :50-56 cat + linear2): folding per step keeps the 8 -> mf_dim
