@@ -830,12 +830,14 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
 // ------------------------------------------------------------------ segment sums over the buckets
 // ST[v] = [ S[v] (64) | T[v] (64) ],  S[v] = sum of the gz0 rows in row v's bucket,  T[v] = sum gz_b * partner row.
 // A lane group of sixteen owns sixteen consecutive SLOTS, whatever rows they belong to: equal work per wave under any
-// id distribution.  Every load of the group is requested before any is consumed -- the slot records first (one round
-// trip), then the sixteen bucket rows and the sixteen partner rows they name (a second one): a load-use loop over the
-// slots was eight dependent round trips, 15 us for a kernel that moves 50 MB.  The group keeps running sums for the row
-// it is in and adds them to ST when the row changes (and at its end): one 64-byte atomic segment per sixteen lanes and
-// quarter row, after a transposition through LDS (lane lo of the loads holds columns 4lo .. 4lo+3; an atomic
-// instruction wants sixteen consecutive floats from sixteen lanes).
+// id distribution.  Every load of the group is requested before any is consumed -- the slot records, one per lane,
+// beside the number of slots in use (one round trip), then the sixteen bucket rows and the sixteen partner rows they
+// name (a second one): a load-use loop over the slots was eight dependent round trips, 15 us for a kernel that moves
+// 50 MB.  The group keeps running sums for the row it is in; a run that begins and ends inside the group is a whole
+// bucket and is stored, a run that continues in a neighbouring group is parked in LDS, where the workgroup sums the
+// chains of such runs: a chain inside the workgroup's 256 slots is stored as well, one that reaches its first or last
+// slot is added to ST atomically, a thread per column (sixteen consecutive floats from sixteen lanes are one 64-byte
+// atomic segment).  ncfp_bwd zeroes ST, so a row without a sample stays zero.
 //
 // The same launch carries, on workgroups of their own, the second pass over ncfp_bwd's slabs (tower dW / db: 32
 // outputs x 8 part-lanes per workgroup, fixed order) and the head fold's chain rule from the slabs' head sums
@@ -881,7 +883,13 @@ __device__ __forceinline__ void slab_reduce_role(const Seg& A, int blk) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) acc[u] += src[(int64_t)(p + 8 * u) * kSlab];
     }
-    for (; p < A.parts; p += 8) acc[0] += src[(int64_t)p * kSlab];
+    // the at most seven partials left: requested together from clamped indices, the ones past the end masked out (a load
+    // inside the loop's condition was a round trip each)
+    float tail[7];
+#pragma unroll
+    for (int u = 0; u < 7; ++u) tail[u] = src[(int64_t)(p + 8 * u < A.parts ? p + 8 * u : A.parts - 1) * kSlab];
+#pragma unroll
+    for (int u = 0; u < 7; ++u) acc[0] += (p + 8 * u < A.parts ? 1.0f : 0.0f) * tail[u];
   }
   float t = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
   t += __shfl_xor(t, 32, 64);
@@ -911,9 +919,12 @@ __device__ __forceinline__ void head_fold_role(const Seg& A) {
 #pragma unroll
     for (int u = 0; u < 10; ++u) v[u] = 0.0f;
     for (int p0 = pl; p0 < A.parts; p0 += 28 * 10) {
+      // unconditional loads from clamped indices, masked afterwards: a load inside the condition is a round trip each
+      float x[10];
 #pragma unroll
-      for (int u = 0; u < 10; ++u)
-        if (p0 + 28 * u < A.parts) v[u] += src[(int64_t)(p0 + 28 * u) * kSlab];
+      for (int u = 0; u < 10; ++u) x[u] = src[(int64_t)(p0 + 28 * u < A.parts ? p0 + 28 * u : A.parts - 1) * kSlab];
+#pragma unroll
+      for (int u = 0; u < 10; ++u) v[u] += (p0 + 28 * u < A.parts ? 1.0f : 0.0f) * x[u];
     }
 #pragma unroll
     for (int u = 0; u < 10; ++u) acc += v[u];
@@ -945,112 +956,152 @@ __device__ __forceinline__ void head_fold_role(const Seg& A) {
   if (threadIdx.x == 64 && A.g_b2) A.g_b2[0] += gc;
 }
 
-constexpr int kSegRange = 32;   // consecutive slots a lane group of sixteen owns
-constexpr int kSegBatch = 8;    // slots whose loads are in flight together
+constexpr int kSegSlots = 16;                        // consecutive slots a lane group of sixteen owns: all in flight at once
+constexpr int kSegGroups = kThreads / 16;            // lane groups of a workgroup
+constexpr int kSegWgSlots = kSegGroups * kSegSlots;  // consecutive slots of a workgroup
+constexpr int kSegOpenL = 1, kSegOpenR = 2;          // a parked run continues in the group before / behind
 
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kThreads, 3)
 ncfp_segsum_kernel(const Seg A) {
   if ((int)blockIdx.x >= A.seg_blocks) {
     if ((int)blockIdx.x < A.seg_blocks + A.red_blocks) slab_reduce_role(A, (int)blockIdx.x - A.seg_blocks);
     else head_fold_role(A);
     return;
   }
-  // A lane group owns kSegRange consecutive slots and walks them kSegBatch at a time, software-pipelined: while batch k
-  // is summed, the rows of batch k + 1 (bucket row + the partner row its record names) and the records of batch k + 2
-  // are in flight.  A row whose whole bucket lies inside the range is STORED (nobody else adds to it); only the first and
-  // the last row of a range can continue in a neighbour's and are added atomically -- 2 per 64 slots instead of one per
-  // 12: the first version flushed every run with atomics and ran at the memory side's atomic rate (240 K 64-byte
-  // requests, TCC_EA0_ATOMIC), not at the rate the buckets can be read.
-  __shared__ __attribute__((aligned(16))) float s_t[kThreads / 16][2][68];
+  // The chain of a wave is {total || records} -> rows -> sums: lane lo of a group loads the record of slot s0 + lo (the
+  // group's records are 256 contiguous bytes) beside the number of slots in use, the fields of slot k reach the other
+  // lanes by a shuffle inside the sixteen, and the 32 row loads (gz0 row + partner row of every slot) are requested back
+  // to back before any is consumed.  (The version before walked 32 slots 8 at a time behind offsets[rows] -- six
+  // dependent round trips at one wave per SIMD, every lane of a group holding a copy of every record.)
+  //
+  // A run that begins and ends inside the group is the whole bucket of its row: plain stores.  A run that continues in a
+  // neighbouring group -- the first when the slot before the range has its row, the last when the slot behind has -- is
+  // OPEN: the group parks it in LDS (two entries a group: an open first run that ends inside, and the last run), and
+  // after one barrier a thread per column walks the workgroup's entries in slot order, sums the chains of entries that
+  // continue each other, stores a chain that lies inside the workgroup and adds one that is open at the workgroup's
+  // first or last slot to ST atomically (64-byte segments from sixteen lanes): at most two atomic flushes per 256 slots.
+  // (Two per 32-slot range went out at the end of the waves with nothing else in flight: 4.2 MB at the memory side's
+  // atomic rate.)
+  __shared__ __attribute__((aligned(16))) float s_run[2 * kSegGroups][128];
+  __shared__ int s_meta[2 * kSegGroups];             // row << 2 | open flags; -1: no entry
   const int lane = threadIdx.x & 63, lo = lane & 15, grp = threadIdx.x >> 4;
+  const int64_t s0 = ((int64_t)blockIdx.x * kSegGroups + grp) * kSegSlots, sme = s0 + lo;
+  const int64_t spare = 2 * A.m;                     // the last slot of the record array: every index is clamped to it
+  // ---- requests: the slots in use, this lane's record, the rows of the slots just outside the range
   const int64_t total = A.offsets[A.nu + A.ni];
-  const int64_t s0 = ((int64_t)blockIdx.x * (kThreads / 16) + grp) * kSegRange;
-  const int64_t s1 = s0 + kSegRange < total ? s0 + kSegRange : total;   // (may be <= s0: nothing to do, but stay for the shuffles)
+  const f32x4 rec = ldg4(A.aux + (sme < spare ? sme : spare) * 4);
+  const int64_t sb = s0 > 0 ? s0 - 1 : 0, sa = s0 + kSegSlots;
+  const int row_before = __float_as_int(A.aux[(sb < spare ? sb : spare) * 4 + 2]);
+  const int row_after = __float_as_int(A.aux[(sa < spare ? sa : spare) * 4 + 2]);
+  // a slot at or behind `total` holds stale bytes of an earlier step: nothing is addressed through it, it joins no sum
+  const bool used = sme < total;
+  const float gzv = used ? rec[0] : 0.0f;
+  const int v = used && (uint32_t)__float_as_int(rec[2]) < (uint32_t)(A.nu + A.ni) ? __float_as_int(rec[2]) : -1;
+  const bool urow = v < A.nu;                        // a user row: its partners are items
+  // (clamped: records of a call that broke the counters' contract give wrong sums, not a read outside a buffer)
+  const uint32_t pid = used ? min((uint32_t)__float_as_int(rec[1]), (uint32_t)((urow ? A.ni : A.nu) - 1)) : 0u;
+  const int pk = (int)(2u * pid + (urow ? 1u : 0u));
+  const uint32_t b = used ? min((uint32_t)__float_as_int(rec[3]), (uint32_t)A.m) : (uint32_t)A.m;
+  const int v_before = (s0 > 0 && s0 - 1 < total) ? row_before : -1;
+  const int v_after = sa < total ? row_after : -1;
+  // ---- the 32 rows of the range, 16 bytes per lane each
+  f32x4 g[kSegSlots], p[kSegSlots];
+#pragma unroll
+  for (int k = 0; k < kSegSlots; ++k) {
+    const int src = (lane & 48) | k;
+    const uint32_t bk = (uint32_t)__shfl((int)b, src, 64);
+    const int pkk = __shfl(pk, src, 64);
+    g[k] = ldg4(A.gz + (int64_t)bk * kN0 + 4 * lo);
+    p[k] = ldg4(((pkk & 1) ? A.gmf_i : A.gmf_u) + (int64_t)(pkk >> 1) * kP + 4 * lo);
+  }
+  // ---- the runs, in slot order (every lane of the group takes the same turns: it holds columns 4 lo .. 4 lo + 3)
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 accs = zero4, acct = zero4;
   int cur = -1;
-  bool cur_inside = false;   // the run being summed began inside this range (its row's bucket does not start earlier)
-  auto flush = [&](int v, bool complete) {
-    // a row whose whole bucket lies inside [s0, s1): plain stores; else atomics (transposed through LDS to 64-byte segments)
-    float* dst = A.st + (int64_t)v * 128;
-    if (complete) {
-      stg4(dst + 4 * lo, accs);
-      stg4(dst + 64 + 4 * lo, acct);
-    } else {
-      float* t = &s_t[grp][0][0];
-      *reinterpret_cast<f32x4*>(t + 4 * lo) = accs;
-      *reinterpret_cast<f32x4*>(t + 68 + 4 * lo) = acct;
-      asm volatile("" ::: "memory");   // (same lane group, same wave: the LDS pipe is in order)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        ctr_atomic_add_global(dst + 16 * r + lo, t[16 * r + lo]);
-        ctr_atomic_add_global(dst + 64 + 16 * r + lo, t[68 + 16 * r + lo]);
-      }
-      asm volatile("" ::: "memory");
-    }
+  bool inside = false;   // the run being summed began inside this range (its row's bucket does not start earlier)
+  int meta0 = -1, meta1 = -1;
+  auto store_run = [&](int r) {
+    float* dst = A.st + (int64_t)r * 128;
+    stg4(dst + 4 * lo, accs);
+    stg4(dst + 64 + 4 * lo, acct);
   };
-  const int64_t last = total > 0 ? total - 1 : 0;
-  // the rows of the slots just outside the range (requested with the first records): does the first / last run continue?
-  const f32x4 rec_before = ldg4(A.aux + (s0 > 0 ? (s0 - 1 < total ? s0 - 1 : last) : 0) * 4);
-  const f32x4 rec_after = ldg4(A.aux + (s1 < total ? s1 : last) * 4);
-  const int v_before = s0 > 0 ? __float_as_int(rec_before[2]) : -1;
-  const int v_after = s1 < total ? __float_as_int(rec_after[2]) : -1;
-  auto slot = [&](int64_t s) { return s < s1 ? s : (s1 > s0 ? s1 - 1 : last); };   // clamped: always a written slot
-  auto load_aux = [&](int64_t base, f32x4 (&ax)[kSegBatch]) {
-#pragma unroll
-    for (int k = 0; k < kSegBatch; ++k) ax[k] = ldg4(A.aux + slot(base + k) * 4);
+  auto park = [&](int e) {
+    *reinterpret_cast<f32x4*>(&s_run[2 * grp + e][4 * lo]) = accs;
+    *reinterpret_cast<f32x4*>(&s_run[2 * grp + e][64 + 4 * lo]) = acct;
   };
-  auto load_rows = [&](int64_t base, const f32x4 (&ax)[kSegBatch], f32x4 (&g)[kSegBatch], f32x4 (&p)[kSegBatch]) {
 #pragma unroll
-    for (int k = 0; k < kSegBatch; ++k) {
-      const int pid = __float_as_int(ax[k][1]), v = __float_as_int(ax[k][2]);
-      // the slot's gz0 row is the row of the sample its record names (clamped: records of a call that broke the
-      // counters' contract give wrong sums, not a read outside the buffer)
-      const uint32_t b = min((uint32_t)__float_as_int(ax[k][3]), (uint32_t)A.m);
-      g[k] = ldg4(A.gz + (int64_t)b * kN0 + 4 * lo);
-      p[k] = ldg4((v < A.nu ? A.gmf_i : A.gmf_u) + (int64_t)pid * kP + 4 * lo);
-    }
-  };
-  auto sum = [&](int64_t base, const f32x4 (&ax)[kSegBatch], const f32x4 (&g)[kSegBatch], const f32x4 (&p)[kSegBatch]) {
-#pragma unroll
-    for (int k = 0; k < kSegBatch; ++k) {
-      if (base + k < s1) {
-        const int v = __float_as_int(ax[k][2]);
-        if (v != cur) {
-          if (cur >= 0) flush(cur, cur_inside);       // it ended here, inside the range
-          cur_inside = base + k > s0 || v != v_before;
-          cur = v;
-          accs = acct = zero4;
+  for (int k = 0; k < kSegSlots; ++k) {
+    const int src = (lane & 48) | k;
+    const int vk = __shfl(v, src, 64);
+    const float gk = __shfl(gzv, src, 64);
+    if (vk != cur) {
+      if (cur >= 0) {                                // it ended here, inside the range
+        if (inside) store_run(cur);
+        else {
+          park(0);
+          meta0 = (cur << 2) | kSegOpenL;
         }
-        accs += g[k];
-        acct += ax[k][0] * p[k];
       }
+      inside = k > 0 || vk != v_before;
+      cur = vk;
+      accs = acct = zero4;
     }
-  };
-  if (total <= 0) return;
-  // batch k: records axA, rows (gA, pA); batch k + 1: records axB
-  f32x4 axA[kSegBatch], axB[kSegBatch], axC[kSegBatch], gA[kSegBatch], pA[kSegBatch], gB[kSegBatch], pB[kSegBatch];
-  load_aux(s0, axA);
-  load_rows(s0, axA, gA, pA);
-  load_aux(s0 + kSegBatch, axB);
-  constexpr int kPairs = kSegRange / (2 * kSegBatch);
-#pragma unroll 1
-  for (int it = 0; it < kPairs; ++it) {
-    const int64_t base = s0 + (int64_t)it * 2 * kSegBatch;
-    load_rows(base + kSegBatch, axB, gB, pB);          // rows of k + 1 (waits for its records)
-    load_aux(base + 2 * kSegBatch, axC);               // records of k + 2
-    sum(base, axA, gA, pA);                            // k (its rows were requested a batch ago)
-    load_rows(base + 2 * kSegBatch, axC, gA, pA);      // rows of k + 2
-    load_aux(base + 3 * kSegBatch, axA);               // records of k + 3
-    sum(base + kSegBatch, axB, gB, pB);                // k + 1
-#pragma unroll
-    for (int k = 0; k < kSegBatch; ++k) {              // next pair: k + 2 in (axA, gA, pA), records of k + 3 in axB
-      const f32x4 t = axA[k];
-      axA[k] = axC[k];
-      axB[k] = t;
+    accs += g[k];
+    acct += gk * p[k];
+  }
+  if (cur >= 0) {
+    const bool open_r = cur == v_after;
+    if (inside && !open_r) store_run(cur);
+    else {
+      park(1);
+      meta1 = (cur << 2) | (inside ? 0 : kSegOpenL) | (open_r ? kSegOpenR : 0);
     }
   }
-  if (cur >= 0) flush(cur, cur_inside && cur != v_after);
+  if (lo == 0) {
+    s_meta[2 * grp] = meta0;
+    s_meta[2 * grp + 1] = meta1;
+  }
+  __syncthreads();
+  // ---- the open runs of the workgroup, a thread per column.  An entry open to the right is continued by the first
+  // entry of the next group (same row, open to the left); a chain that reaches the workgroup's first or last slot open
+  // may go on in another workgroup
+  if (threadIdx.x >= 128) return;
+  const int c = threadIdx.x;
+  float sum = 0.0f;
+  int row = -1;
+  bool shared = false;
+  auto emit = [&](bool atomic) {
+    float* dst = A.st + (int64_t)row * 128 + c;
+    if (atomic) ctr_atomic_add_global(dst, sum);
+    else dst[0] = sum;
+    row = -1;
+  };
+  // (every entry is read before the first is looked at, empty ones included: one LDS round trip, not one per entry)
+  int meta[2 * kSegGroups];
+  float val[2 * kSegGroups];
+#pragma unroll
+  for (int e = 0; e < 2 * kSegGroups; ++e) {
+    meta[e] = s_meta[e];
+    val[e] = s_run[e][c];
+  }
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int e = 0; e < 2 * kSegGroups; ++e) {
+    const int mt = __builtin_amdgcn_readfirstlane(meta[e]);
+    const float x = val[e];
+    if (mt >= 0) {
+      const int r = mt >> 2;
+      if (row >= 0 && r != row) emit(true);          // (never, for records that keep the contract)
+      if (row < 0) {
+        row = r;
+        sum = 0.0f;
+        shared = (mt & kSegOpenL) != 0;              // open to the left with nothing before it here: the workgroup's edge
+      }
+      sum += x;
+      if (!(mt & kSegOpenR)) emit(shared);
+    }
+  }
+  if (row >= 0) emit(true);                          // still open at the workgroup's last slot
 }
 
 // ------------------------------------------------------------------ the products over the table rows
@@ -1388,7 +1439,7 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   if (rc != CTR_OK) return rc;
   // segment sums over the buckets, and beside them (own workgroups) the tower's dW / db partials and the head fold's
   // chain rule (its GMF part arrives from ncfp_finish)
-  Seg S{gzb, aux, offs, d->gmf_user, d->gmf_item, nu, ni, m, stt, (int)ctr_ceil_div(2 * m, (kThreads / 16) * kSegRange),
+  Seg S{gzb, aux, offs, d->gmf_user, d->gmf_item, nu, ni, m, stt, (int)ctr_ceil_div(2 * m, kSegWgSlots),
         (kSlabHead + 31) / 32,
         slabs, (int)grid, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, d->head_w, d->proj_w, d->ld_proj_w,
         d->proj_b, g->g_head_w, g->g_proj_w, g->ld_g_proj_w, g->g_proj_b, g->g_head_b};
