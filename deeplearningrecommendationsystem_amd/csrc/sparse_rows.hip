@@ -83,7 +83,8 @@ struct AdamConsts {
 
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamConsts& c) {
   const float gr = fmaf(c.weight_decay, p, g);   // grad.add(param, alpha=wd), on touched rows only
-  m = fmaf(c.omb1, gr - m, m);                   // exp_avg.lerp_(grad, 1 - beta1)
+  // exp_avg.lerp_(grad, 1 - beta1), from the nearer end as ATen forms it (see adam_kernel)
+  m = c.omb1 >= 0.5f ? fmaf(m - gr, 1.0f - c.omb1, gr) : fmaf(c.omb1, gr - m, m);
   v = v * c.beta2 + (c.omb2 * gr) * gr;          // mul_(beta2).addcmul_(grad, grad, 1 - beta2)
   p -= c.step_size * (m / (sqrtf(v) / c.bc2_sqrt + c.eps));
 }

@@ -75,6 +75,10 @@ adam_kernel(const AdamPack P, float lr, float beta2, float omb1, float omb2, flo
             float bc2_sqrt) {  // omb = 1 - beta, formed in double on the host as torch does
   const ctr_adam_tensor_t t = P.t[blockIdx.y];
   const float step_size = lr / bc1;
+  // lerp as ATen forms it: from the nearer end.  With weight >= 0.5 the first form loses gr below ulp(m) in gr - m
+  // (beta1 = 0: exp_avg would not be the gradient), and Adam's m / sqrt(v) carries that into a visible step.
+  const bool near_end = omb1 >= 0.5f;
+  const float b1 = 1.0f - omb1;
   for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < t.numel; i += (int64_t)gridDim.x * blockDim.x * 4) {
     if (i + 3 < t.numel) {
       float4 g = *reinterpret_cast<const float4*>(t.grad + i);
@@ -85,7 +89,7 @@ adam_kernel(const AdamPack P, float lr, float beta2, float omb1, float omb2, flo
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float gr = fmaf(weight_decay, pp[e], gg[e]);     // grad.add(param, alpha=wd)
-        mm[e] = fmaf(omb1, gr - mm[e], mm[e]);           // exp_avg.lerp_(grad, 1 - beta1)
+        mm[e] = near_end ? fmaf(mm[e] - gr, b1, gr) : fmaf(omb1, gr - mm[e], mm[e]);  // exp_avg.lerp_(grad, 1 - beta1)
         vv[e] = vv[e] * beta2 + (omb2 * gr) * gr;      // mul_(beta2).addcmul_(grad, grad, 1 - beta2)
         const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
         pp[e] -= step_size * (mm[e] / denom);
@@ -96,7 +100,7 @@ adam_kernel(const AdamPack P, float lr, float beta2, float omb1, float omb2, flo
     } else {
       for (int64_t j = i; j < t.numel; ++j) {
         const float gr = fmaf(weight_decay, t.param[j], t.grad[j]);
-        const float m = fmaf(omb1, gr - t.exp_avg[j], t.exp_avg[j]);
+        const float m = near_end ? fmaf(t.exp_avg[j] - gr, b1, gr) : fmaf(omb1, gr - t.exp_avg[j], t.exp_avg[j]);
         const float v = t.exp_avg_sq[j] * beta2 + (omb2 * gr) * gr;
         t.exp_avg[j] = m;
         t.exp_avg_sq[j] = v;

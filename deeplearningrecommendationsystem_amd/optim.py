@@ -55,6 +55,8 @@ class Adam(torch.optim.Optimizer):
                 step = st["step"] if step is None else step
                 if st["step"] != step:
                     raise RuntimeError("parameters of one group must share a step count")
+                if p.numel() == 0:
+                    continue   # nothing to update, and no address to hand over: an empty tensor's pointer is null
                 todo.append((p, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"]))
             if rows:
                 sparse.adam_rows(rows, group["lr"], group["betas"], group["eps"], group["weight_decay"], step)
