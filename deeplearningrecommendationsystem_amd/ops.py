@@ -378,6 +378,16 @@ FUSED_MLP = True  # narrow stacks run as one launch (ctr_mlp_fwd/bwd) when their
 _REFUSED = (-2, -4)  # CTR_ELIMIT / CTR_EALIGN: nothing was enqueued, take the per-layer path
 
 
+def _refused(rc, label) -> bool:
+    """whether the library refused the ``_timed`` call that returned ``rc``; nothing ran then, so the profiler's record
+    of it goes and what the caller issues instead is what gets timed"""
+    if rc not in _REFUSED:
+        return False
+    if _profiler is not None and _profiler.records and _profiler.records[-1][0] == label:
+        _profiler.records.pop()
+    return True
+
+
 def _mlp_layer_array(layers, ys, grads=None):
     arr = (_lib.MlpLayer * len(layers))()
     for k, (layer, y) in enumerate(zip(layers, ys)):
@@ -432,21 +442,17 @@ def mlp_fwd(x: torch.Tensor, layers: Sequence[Layer], last_out: Optional[torch.T
             rc = _timed("mlp_fused_fwd", lambda: (4 * m * (dims[0][1] + p + 1 + sum(n for n, _ in dims)),
                                                   2 * m * (sum(n * k for n, k in dims) + p + dims[-1][0])),
                         lib.ctr_mlp_head_fwd, x.data_ptr(), _ld(x), m, arr, len(layers), C.byref(hd), _lib.stream_ptr())
-            if rc not in _REFUSED:
+            if not _refused(rc, "mlp_fused_fwd"):
                 _lib.check(rc, "ctr_mlp_head_fwd")
                 head.out = out
                 return [x] + ys
-            if _profiler is not None and _profiler.records and _profiler.records[-1][0] == "mlp_fused_fwd":
-                _profiler.records.pop()  # refused: nothing ran
         rc = _timed("mlp_fused_fwd", lambda: (4 * m * (dims[0][1] + sum(n for n, _ in dims)),
                                               2 * m * sum(n * k for n, k in dims)),
                     lib.ctr_mlp_fwd, x.data_ptr(), _ld(x), m, arr, len(layers), _lib.stream_ptr())
-        if rc not in _REFUSED:
+        if not _refused(rc, "mlp_fused_fwd"):
             _lib.check(rc, "ctr_mlp_fwd")
             _head_unfused(head, ys[-1])
             return [x] + ys
-        if _profiler is not None and _profiler.records and _profiler.records[-1][0] == "mlp_fused_fwd":
-            _profiler.records.pop()  # refused: nothing ran
     acts = [x]
     for k, layer in enumerate(layers):
         out = last_out if (k == len(layers) - 1) else None
@@ -489,9 +495,7 @@ def embed_mlp_head_fwd(specs: Sequence[FieldSpec], batch: int, buf: torch.Tensor
                 _lib.load().ctr_embed_mlp_head_fwd, farr, len(specs), batch, buf.data_ptr(), _ld(buf), _lib.ptr(err_flag),
                 1 if write_x else 0, arr, len(layers), C.byref(hd), C.byref(fd) if fd is not None else None,
                 _lib.stream_ptr())
-    if rc in _REFUSED:
-        if _profiler is not None and _profiler.records and _profiler.records[-1][0] == "embed_mlp_fused_fwd":
-            _profiler.records.pop()  # refused: nothing ran
+    if _refused(rc, "embed_mlp_fused_fwd"):
         return None
     _lib.check(rc, "ctr_embed_mlp_head_fwd")
     head.out = out
@@ -554,9 +558,7 @@ def mlp_head_bwd(acts: Sequence[torch.Tensor], layers: Sequence[Layer], head: He
         return grads
     rc = _timed("mlp_fused_bwd", meta, _lib.load().ctr_mlp_head_bwd, x0.data_ptr(), _ld(x0), m, arr, len(layers),
                 C.byref(hg), gx_first.data_ptr(), _ld(gx_first), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
-    if rc in _REFUSED:
-        if _profiler is not None and _profiler.records and _profiler.records[-1][0] == "mlp_fused_bwd":
-            _profiler.records.pop()
+    if _refused(rc, "mlp_fused_bwd"):
         return None
     _lib.check(rc, "ctr_mlp_head_bwd")
     return grads
@@ -592,11 +594,9 @@ def mlp_bwd(acts: Sequence[torch.Tensor], layers: Sequence[Layer], gy: torch.Ten
                                               4 * m * sum(n * k for n, k in dims)),
                     _lib.load().ctr_mlp_bwd, x0.data_ptr(), _ld(x0), m, arr, len(layers), gy.data_ptr(), _ld(gy),
                     _lib.ptr(gx), _ld(gx) if gx is not None else 0, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
-        if rc not in _REFUSED:
+        if not _refused(rc, "mlp_fused_bwd"):
             _lib.check(rc, "ctr_mlp_bwd")
             return grads, gx
-        if _profiler is not None and _profiler.records and _profiler.records[-1][0] == "mlp_fused_bwd":
-            _profiler.records.pop()  # refused: nothing ran, the per-layer path below is what gets timed
     g = gy
     for k in range(len(layers) - 1, -1, -1):
         layer = layers[k]
@@ -644,6 +644,12 @@ def act_mask_bwd(g, y, act: int) -> None:
 # ---------------------------------------------------------------------------
 # NeuralCF with the first tower layer on the table rows (csrc/ncf_proj.hip)
 # ---------------------------------------------------------------------------
+def few_table_rows(rows: int, batch: int) -> bool:
+    """the admission both of NeuralCF's table-row paths share: a batch worth a launch over the tables' ``rows`` (both
+    tables together), with every row met by four samples on average"""
+    return batch >= 4096 and batch >= 4 * rows
+
+
 class NcfCounts:
     """the bucket plan of ``ctr_ncf_proj_fwd`` (one holder per model): per-row sample counts of the batch's chunks,
     row totals and bucket offsets, built by every training forward and read by its backward.  The C entry points want
@@ -733,7 +739,7 @@ class NcfProj:
         dims = [tuple(layer.weight.shape) for layer in hidden]
         return (dims == [(64, 128), (32, 64), (16, 32), (8, 16)] and gmf_u.shape[1] == 64 and mlp_u.shape[1] == 64 and
                 tuple(proj[0].shape) == (64, 8) and all(layer.bias is not None for layer in hidden) and
-                rows <= _lib.CTR_NCF_PROJ_MAX_ROWS and batch >= 4096 and batch >= 4 * rows and 2 * batch < 2 ** 31)
+                rows <= _lib.CTR_NCF_PROJ_MAX_ROWS and few_table_rows(rows, batch) and 2 * batch < 2 ** 31)
 
     # algorithmic bytes / flops of the launches: per sample unless said otherwise
     def _meta(self, which):
@@ -1261,9 +1267,7 @@ def gru_fused_fwd(x, w_ih, b_ih, w_hh, b_hh, batch, length, dim, hbuf, last) -> 
                 _lib.load().ctr_gru_fused_fwd, x.data_ptr(), _ld(x), w_ih.data_ptr(), b_ih.data_ptr(), w_hh.data_ptr(),
                 b_hh.data_ptr(), batch, length, dim, hbuf.data_ptr(), _lib.ptr(last),
                 _ld(last) if last is not None else 0, _lib.stream_ptr())
-    if rc in _REFUSED:
-        if _profiler is not None and _profiler.records and _profiler.records[-1][0] == "gru_fused_fwd":
-            _profiler.records.pop()
+    if _refused(rc, "gru_fused_fwd"):
         return False
     _lib.check(rc, "ctr_gru_fused_fwd")
     return True

@@ -7,6 +7,7 @@ checked against the CPU oracle on seeded synthetic batches.
 Tolerance (north_star): logits/loss within 1e-5 relative; gradients are sums of
 up to B terms accumulated with fp32 atomics in no fixed order, so they get
 rtol 1e-4 with an absolute floor scaled to the fixture's gradient magnitude."""
+import contextlib
 import os
 
 import numpy as np
@@ -504,6 +505,22 @@ def _ncf_step(module, u, i, y, project):
     return out
 
 
+@contextlib.contextmanager
+def _ncf_paths_watched(*names):
+    """wraps the ``forward`` of the named NeuralCF path objects (model/neuralcf.py: _PATHS); yields the list that the
+    name of every path that runs is appended to"""
+    from deeplearningrecommendationsystem_amd.model import neuralcf as ncf_mod
+    ran = []
+    real = {name: ncf_mod._PATHS[name].forward for name in names}
+    try:
+        for name, fwd in real.items():
+            ncf_mod._PATHS[name].forward = staticmethod(lambda *a, name=name, fwd=fwd: (ran.append(name), fwd(*a))[1])
+        yield ran
+    finally:
+        for name, fwd in real.items():
+            ncf_mod._PATHS[name].forward = staticmethod(fwd)
+
+
 @pytest.mark.parametrize("nu,ni,batch,dist", [(943, 1682, 16384, "uniform"), (943, 1682, 65536 + 37, "uniform"),
                                               (943, 1682, 20000, "zipf"), (5, 7, 4099, "uniform"),
                                               (3000, 5000, 40000, "uniform")])
@@ -537,11 +554,10 @@ def test_neuralcf_table_row_path_against_oracle_and_per_sample_path(nu, ni, batc
                                          ((943, 1682, 32, [64, 32, 16]), 12000), ((50, 70, 16, [96, 24, 8]), 5003)])
 def test_neuralcf_any_tower_table_row_path_against_oracle_and_per_sample_path(shape, batch):
     """the reference script's own shape (scripts/neuralcf.py:60: NeuralCF(943, 1682, 256, [512, 256, 128, 64, 32])) at batch
-    65536, and two other towers: the composed table-row path (_NeuralCFRowsFunction: projected tables, row sums, products
+    65536, and two other towers: the composed table-row path (_RowsPath: projected tables, row sums, products
     over the table rows) against the CPU oracle and against the per-sample kernels"""
     from deeplearningrecommendationsystem_amd import synth
     from deeplearningrecommendationsystem_amd.model import NeuralCF
-    from deeplearningrecommendationsystem_amd.model import neuralcf as ncf_mod
     nu, ni, mf, layers = shape
     torch.manual_seed(17)
     module = NeuralCF(nu, ni, mf, layers)
@@ -552,14 +568,9 @@ def test_neuralcf_any_tower_table_row_path_against_oracle_and_per_sample_path(sh
     params = {k: v.detach().clone() for k, v in module.state_dict().items()}
     prob_ref, loss_ref, grads_ref = orc.step("neuralcf", params, [u, i], y)
     module = module.to(DEV)
-    calls = []
-    real = ncf_mod._NeuralCFRowsFunction.forward
-    try:
-        ncf_mod._NeuralCFRowsFunction.forward = staticmethod(lambda *a: (calls.append(1), real(*a))[1])
+    with _ncf_paths_watched("rows") as ran:
         prob, loss, grads = _run(module, [u, i], y)
-    finally:
-        ncf_mod._NeuralCFRowsFunction.forward = staticmethod(real)
-    assert calls, "the composed table-row path did not run"
+    assert ran, "the composed table-row path did not run"
     torch.testing.assert_close(prob, prob_ref, rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(loss, loss_ref, rtol=1e-5, atol=1e-6)
     _check_grads(grads, grads_ref)
@@ -576,7 +587,6 @@ def test_neuralcf_table_row_path_at_the_edge_of_the_admitted_table_rows(nu, ni):
     four-layer tower kernel): forward, BCELoss, backward and every gradient against the CPU oracle, with the first and
     last row of both tables in the batch"""
     from deeplearningrecommendationsystem_amd import _lib, synth
-    from deeplearningrecommendationsystem_amd.model import neuralcf as ncf_mod
     rows = nu + ni
     batch = max(4 * rows, 65536)
     projected = rows <= _lib.CTR_NCF_PROJ_MAX_ROWS
@@ -588,20 +598,41 @@ def test_neuralcf_table_row_path_at_the_edge_of_the_admitted_table_rows(nu, ni):
     params = {k: v.detach().clone() for k, v in module.state_dict().items()}
     prob_ref, loss_ref, grads_ref = orc.step("neuralcf", params, [u, i], y)
     module = module.to(DEV)
-    ran = []
-    fns = (ncf_mod._NeuralCFProjFunction, ncf_mod._NeuralCFRowsFunction)
-    real = [fn.forward for fn in fns]
-    try:
-        for fn, r in zip(fns, real):
-            fn.forward = staticmethod(lambda *a, fn=fn, r=r: (ran.append(fn.__name__), r(*a))[1])
+    with _ncf_paths_watched("proj", "rows") as ran:
         prob, loss, grads = _run(module, [u, i], y)
-    finally:
-        for fn, r in zip(fns, real):
-            fn.forward = staticmethod(r)
-    assert ran == ["_NeuralCFProjFunction" if projected else "_NeuralCFRowsFunction"], ran
+    assert ran == ["proj" if projected else "rows"], ran
     torch.testing.assert_close(prob, prob_ref, rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(loss, loss_ref, rtol=1e-5, atol=1e-6)
     _check_grads(grads, grads_ref)
+
+
+def test_neuralcf_three_paths_side_by_side_on_the_smallest_shape_all_admit():
+    """the cfg2 tower over a 5 x 7 vocabulary at batch 4099 (ragged against every tile, every row shared by hundreds of
+    samples, first and last row of both tables present): one training step forced through the pinned table-row kernels,
+    the composed table-row path and the per-sample kernels in turn, each against the CPU oracle"""
+    from deeplearningrecommendationsystem_amd import synth
+    from deeplearningrecommendationsystem_amd.model import neuralcf as ncf_mod
+    nu, ni, batch = 5, 7, 4099
+    module = _ncf(nu, ni, 29)
+    gen = synth.generator(batch + 1)
+    u, i = synth.id_batch(batch, nu, ni, gen)
+    u[0], i[0], u[1], i[1] = 0, 0, nu - 1, ni - 1
+    y = synth.labels(batch, True, gen)
+    params = {k: v.detach().clone() for k, v in module.state_dict().items()}
+    prob_ref, loss_ref, grads_ref = orc.step("neuralcf", params, [u, i], y)
+    module = module.to(DEV)
+    choose = ncf_mod.choose_path
+    try:
+        for path in ("proj", "rows", "samples"):
+            ncf_mod.choose_path = lambda *a, path=path: path
+            with _ncf_paths_watched("proj", "rows", "samples") as ran:
+                prob, loss, grads = _run(module, [u, i], y)
+            assert ran == [path], ran
+            torch.testing.assert_close(prob, prob_ref, rtol=1e-5, atol=1e-6, msg=lambda m, path=path: f"{path}: {m}")
+            torch.testing.assert_close(loss, loss_ref, rtol=1e-5, atol=1e-6, msg=lambda m, path=path: f"{path}: {m}")
+            _check_grads(grads, grads_ref)
+    finally:
+        ncf_mod.choose_path = choose
 
 
 def test_neuralcf_table_row_path_counters_survive_unusual_call_orders():

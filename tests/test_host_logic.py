@@ -147,3 +147,51 @@ def test_ncf_counts_holder_hands_out_a_clean_buffer_or_a_private_one():
     h.state = "clean"
     e, _ = h.take(20, cpu)                           # more table rows: a new buffer
     assert e.numel() == 20 * _lib.CTR_NCF_PROJ_COUNT_STRIDE and int(e.abs().sum()) == 0
+
+
+_CFG2 = [128, 64, 32, 16, 8]
+_NCF_PATHS = [  # users, items, mf_dim, layers, batch, ids 1-D, the path
+    (943, 1682, 64, _CFG2, 65536, True, "proj"),
+    (943, 1682, 64, _CFG2, 10500, True, "proj"),                        # = 4 x rows
+    (943, 1682, 64, _CFG2, 10499, True, "samples"),
+    (5, 7, 64, _CFG2, 4096, True, "proj"),
+    (5, 7, 64, _CFG2, 4095, True, "samples"),
+    (6000, 10384, 64, _CFG2, 65536, True, "proj"),                      # 16384 rows
+    (6001, 10384, 64, _CFG2, 65540, True, "rows"),
+    (6001, 10384, 64, _CFG2, 65539, True, "samples"),
+    (943, 1682, 64, _CFG2, 65536, False, "samples"),                    # (B, 1) ids
+    (943, 1682, 32, _CFG2, 65536, True, "rows"),
+    (943, 1682, 256, [512, 256, 128, 64, 32], 65536, True, "rows"),     # n0 = 256
+    (943, 1682, 256, [1024, 512, 256], 65536, True, "samples"),         # n0 > 256
+    (50, 70, 16, [96, 24, 8], 5003, True, "rows"),
+    (50, 70, 16, [96, 24], 5003, True, "samples"),                      # one tower layer
+    (50, 70, 6, [96, 24, 8], 5003, True, "samples"),                    # mf % 4
+    (50, 70, 16, [12, 8, 4], 5003, True, "samples"),                    # half % 4
+    (50, 70, 16, [96, 6, 4], 5003, True, "samples"),                    # n0 % 4
+]
+
+
+def _ncf_choice(model, batch, ids_1d):
+    from deeplearningrecommendationsystem_amd.model import neuralcf
+    p = model._params()
+    return neuralcf.choose_path(p.tables, p.hidden, p.proj, batch, ids_1d)
+
+
+@pytest.mark.parametrize("nu,ni,mf,layers,batch,ids_1d,want", _NCF_PATHS)
+def test_neuralcf_choose_path_is_a_function_of_shapes(nu, ni, mf, layers, batch, ids_1d, want):
+    """which of NeuralCF's three paths a shape takes, asked of a model on the CPU: the edges of the shared admission
+    (4096 samples, four per table row), of the pinned kernels (cfg2's widths, 16384 rows) and of the composed path
+    (widths in fours, first layer up to 256 wide, a second tower layer)"""
+    from deeplearningrecommendationsystem_amd.model import NeuralCF
+    assert _ncf_choice(NeuralCF(nu, ni, mf, layers), batch, ids_1d) == want
+
+
+def test_neuralcf_choose_path_switch_and_sparse_tables_keep_the_per_sample_path(monkeypatch):
+    from deeplearningrecommendationsystem_amd.model import NeuralCF, neuralcf
+    model = NeuralCF(943, 1682, 64, _CFG2)
+    assert _ncf_choice(model, 65536, True) == "proj"
+    monkeypatch.setattr(neuralcf, "PROJECT_TABLES", False)
+    assert _ncf_choice(model, 65536, True) == "samples"
+    monkeypatch.setattr(neuralcf, "PROJECT_TABLES", True)
+    model.MLP_Embedding_Item.weight._ctr_sparse = object()
+    assert _ncf_choice(model, 65536, True) == "samples"
