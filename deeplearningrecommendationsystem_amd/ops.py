@@ -832,7 +832,20 @@ class NcfProj:
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112
 
 
+ALLPAIRS_MAX_VECTORS = 32  # ctr_allpairs_bwd's limit: the backward every shape but the pinned 26 x 16 takes
+
+
+def _allpairs_admit(nvec: int) -> None:
+    if not 2 <= nvec <= ALLPAIRS_MAX_VECTORS:
+        raise ValueError(f"allpairs: 2..{ALLPAIRS_MAX_VECTORS} vectors per sample, got {nvec}")
+
+
 def allpairs_fwd(emb: torch.Tensor, nvec: int, dim: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """inner products of all pairs of a sample's ``nvec`` vectors, i < j lexicographic.  Admits what ``allpairs_bwd``
+    can differentiate and nothing else: the lane-group forward (csrc/fields.hip) would take up to 64 vectors, but the
+    backward of such a shape is refused by ctr_fields_pairs_bwd and then by ctr_allpairs_bwd (at most 32 vectors), so
+    both raise ``ValueError`` above 32 vectors instead of a forward that succeeds and a backward that cannot."""
+    _allpairs_admit(nvec)
     emb = _mat(emb, "emb")
     batch = emb.shape[0]
     npairs = nvec * (nvec - 1) // 2
@@ -850,6 +863,8 @@ def allpairs_fwd(emb: torch.Tensor, nvec: int, dim: int, out: Optional[torch.Ten
 
 
 def allpairs_bwd(emb, nvec, dim, gp, gemb, accumulate: bool) -> None:
+    """backward of ``allpairs_fwd``; the same admission (``ValueError`` outside 2..32 vectors)"""
+    _allpairs_admit(nvec)
     emb, gp, gemb = _mat(emb, "emb"), _mat(gp, "gp"), _mat(gemb, "gemb")
     batch = emb.shape[0]
     npairs = nvec * (nvec - 1) // 2
