@@ -131,6 +131,13 @@ class Loader(C.Structure):
                 ("ld_history", C.c_int64), ("hist_out", C.c_void_p), ("hist_ldo", C.c_int64), ("err_flag", C.c_void_p)]
 
 
+class LoaderNeg(C.Structure):
+    """mirror of ``ctr_loader_neg_t``"""
+    _fields_ = [("negatives", C.c_int32), ("item_col", C.c_int32), ("rating_col", C.c_int32), ("reserved", C.c_int32),
+                ("users", C.c_void_p), ("num_users", C.c_int64), ("num_items", C.c_int64), ("indptr", C.c_void_p),
+                ("indices", C.c_void_p), ("fail_flag", C.c_void_p)]
+
+
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list every `ctr_*` symbol of include/ctrhip.h
@@ -190,6 +197,7 @@ SIGNATURES = {
     "ctr_assemble_features": (_i, [_p, _p, _l, _p, _i, _l, _p, _i, _l, _p, _l, _p, _p]),
     "ctr_load_batch": (_i, [_p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p: address of a host Loader
     "ctr_loader_indices": (_i, [_l, C.c_uint64, _l, _l, _l, _i, _p, _p]),
+    "ctr_load_batch_neg": (_i, [_p, _p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p, _p: host Loader, host LoaderNeg
     "ctr_shard_bucket": (_i, [_p, _l, _i, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_bucket_padded": (_i, [_p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_recv_rows": (_i, [_p, _l, _l, _p, _p, _p, _p]),

@@ -20,6 +20,30 @@
 // join ids) into LDS, then all four waves copy -- consecutive lanes take consecutive elements of a row, so a history
 // row (L int64) or a feature row is read and written in whole cache lines, and rows of 16-byte multiples move as
 // 16-byte pieces.
+//
+// Drawn negatives (ctr_load_batch_neg).  N positives, k = negatives >= 1; an epoch has M = N * (1 + k) positions and
+// position p of epoch e holds
+//     v = perm_M(seed, e, p)             the permutation above over M instead of N;  v = p when shuffle == 0
+//     s = v / (1 + k);  j = v % (1 + k)
+//     j == 0:  the positive s, every output exactly as ctr_load_batch writes sample s
+//     j >= 1:  a negative of user u = users[s]:
+//         nkey    = mix64(seed ^ mix64(e * 0x100000001B3 + 4))             (round index 4: the permutation uses 0..3)
+//         draw_t  = ((mix64(nkey ^ mix64(v * 0x100000001B3 + t)) >> 32) * num_items) >> 32,    t = 0, 1, ...
+//         item    = draw_t for the first t < 2^14 with (u, draw_t) not observed
+//         outputs = those of sample s, with the item id replaced by `item` and the rating by 0.0f (the replaced id is
+//                   what the feature join reads; the history row stays user u's)
+// uint64 arithmetic, wrapping.  Slots draw independently, so one positive's negatives may repeat.  Unshuffled, every
+// positive is followed by its k negatives.  If all 2^14 draws are observed the last one is written and *fail_flag is
+// raised; a user id outside [0, num_users) makes no draw, writes item 0 and raises *err_flag.  The observed set is a
+// CSR over users (indptr int64, item ids int32 ascending and distinct within a row), membership a binary search: 4 B
+// per observed pair whatever num_items is, where the sampler's bitmap is num_users * num_items / 8 B.
+// tests/loader_neg_numpy.py restates this.
+//
+// The draw is a chain of dependent loads per position: users[s] -> indptr[u], indptr[u + 1] -> about log2(row length)
+// probes per try.  Spreading a tile's 64 chains over the four waves would not shorten any of them, and a batch of
+// 65536 positions is 1024 workgroups of 2 KiB LDS and few registers, all resident at once (4 per CU), so every chain of
+// the batch is in flight from the start either way: the draw stays in the index stage's one wave, and the other
+// workgroups on the CU cover its latency.  The output does not depend on that choice.
 #include "ctr_common.h"
 
 namespace {
@@ -89,6 +113,32 @@ __device__ __forceinline__ void copy_rows(const void* src, int64_t lds, void* ds
   }
 }
 
+// the feature join and the history join of one tile, from the ids the index stage left in LDS
+__device__ __forceinline__ void write_joins(const ctr_loader_t& d, int cnt, int64_t base, int hist16, const int64_t* s_fu,
+                                            const int64_t* s_fi, const int64_t* s_hu) {
+  if (d.feat_out) {
+    const int uw = d.user_width, width = 2 + d.user_width + d.item_width;
+    const int total = cnt * width;
+    for (int g = threadIdx.x; g < total; g += kBlock) {
+      const int r = g / width;
+      const int c = g - r * width;
+      const int64_t u = s_fu[r], i = s_fi[r];
+      float v;
+      if (c == 0) v = (float)u;
+      else if (c == 1) v = (float)i;
+      else if (c < 2 + uw) v = ctr_ldg(d.user_feat + (u < 0 || u >= d.num_users ? 0 : u) * uw + (c - 2));
+      else v = ctr_ldg(d.item_feat + (i < 0 || i >= d.num_items ? 0 : i) * d.item_width + (c - 2 - uw));
+      ctr_stg(d.feat_out + (base + r) * d.feat_ldo + c, v);
+    }
+  }
+  if (d.hist_out) {
+    if (hist16)
+      copy_rows<ctr_u32x4>(d.history, d.ld_history / 2, d.hist_out, d.hist_ldo / 2, (int)(d.hist_len / 2), cnt, s_hu, base);
+    else
+      copy_rows<uint64_t>(d.history, d.ld_history, d.hist_out, d.hist_ldo, (int)d.hist_len, cnt, s_hu, base);
+  }
+}
+
 __global__ void __launch_bounds__(kBlock)
 load_batch_kernel(const ctr_loader_t d, const LoaderPerm pm, int64_t first, int64_t count, int hist16) {
   __shared__ int64_t s_idx[kTile], s_fu[kTile], s_fi[kTile], s_hu[kTile];
@@ -122,27 +172,106 @@ load_batch_kernel(const ctr_loader_t d, const LoaderPerm pm, int64_t first, int6
       if (col.elem_bytes == 8) copy_rows<uint64_t>(col.src, col.lds, col.dst, col.ldd, col.width, cnt, s_idx, base);
       else copy_rows<uint32_t>(col.src, col.lds, col.dst, col.ldd, col.width, cnt, s_idx, base);
     }
-    if (d.feat_out) {
-      const int uw = d.user_width, width = 2 + d.user_width + d.item_width;
-      const int total = cnt * width;
-      for (int g = threadIdx.x; g < total; g += kBlock) {
-        const int r = g / width;
-        const int c = g - r * width;
-        const int64_t u = s_fu[r], i = s_fi[r];
-        float v;
-        if (c == 0) v = (float)u;
-        else if (c == 1) v = (float)i;
-        else if (c < 2 + uw) v = ctr_ldg(d.user_feat + (u < 0 || u >= d.num_users ? 0 : u) * uw + (c - 2));
-        else v = ctr_ldg(d.item_feat + (i < 0 || i >= d.num_items ? 0 : i) * d.item_width + (c - 2 - uw));
-        ctr_stg(d.feat_out + (base + r) * d.feat_ldo + c, v);
+    write_joins(d, cnt, base, hist16, s_fu, s_fi, s_hu);
+    __syncthreads();  // the next pass rewrites the LDS rows
+  }
+}
+
+constexpr int kMaxTries = 1 << 14;
+
+struct LoaderDraw {
+  uint64_t nkey;
+  uint64_t per;  // 1 + negatives
+  const int64_t* users;
+  const int64_t* indptr;
+  const int32_t* indices;
+  int64_t num_users;
+  uint64_t num_items;
+  int32_t* fail_flag;
+  int32_t item_col, rating_col;
+};
+
+// the item of negative slot v of user u (header comment); u inside [0, num_users)
+__device__ __forceinline__ int64_t draw_negative(const LoaderDraw& nd, uint64_t v, int64_t u) {
+  const int64_t lo = ctr_ldg(nd.indptr + u), hi = ctr_ldg(nd.indptr + u + 1);
+  const CTR_GLOBAL int32_t* ind = (const CTR_GLOBAL int32_t*)nd.indices;
+  const uint64_t slot = v * 0x100000001B3ull;
+  uint64_t item = 0;
+  for (int t = 0; t < kMaxTries; ++t) {
+    item = ((mix64(nd.nkey ^ mix64(slot + (uint64_t)t)) >> 32) * nd.num_items) >> 32;
+    int64_t a = lo, b = hi;
+    while (a < b) {  // first entry of the row that is >= item
+      const int64_t mid = a + ((b - a) >> 1);
+      if (ind[mid] < (int32_t)item) a = mid + 1;
+      else b = mid;
+    }
+    if (a == hi || ind[a] != (int32_t)item) return (int64_t)item;
+  }
+  if (nd.fail_flag) *(CTR_GLOBAL int32_t*)nd.fail_flag = 1;
+  return (int64_t)item;
+}
+
+// ctr_load_batch_neg: load_batch_kernel over the virtual epoch.  The index stage also decides positive or negative
+// and draws; s_neg holds the drawn item, -1 for a positive.  A kernel of its own, so that the plain loader keeps its
+// registers.
+__global__ void __launch_bounds__(kBlock)
+load_batch_neg_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, int64_t first, int64_t count,
+                      int hist16) {
+  __shared__ int64_t s_idx[kTile], s_fu[kTile], s_fi[kTile], s_hu[kTile], s_neg[kTile];
+  const int64_t tiles = (count + kTile - 1) / kTile;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t base = tile * kTile;
+    const int cnt = (int)(count - base < kTile ? count - base : kTile);
+    if ((int)threadIdx.x < cnt) {
+      const uint64_t v = (uint64_t)loader_index(pm, first + base + threadIdx.x);
+      const int64_t idx = (int64_t)(v / nd.per);
+      s_idx[threadIdx.x] = idx;
+      bool bad = false;
+      int64_t item = -1;
+      if (v - (uint64_t)idx * nd.per != 0) {
+        const int64_t u = ctr_ldg(nd.users + idx);
+        if (u < 0 || u >= nd.num_users) {
+          bad = true;
+          item = 0;
+        } else {
+          item = draw_negative(nd, v, u);
+        }
+      }
+      s_neg[threadIdx.x] = item;
+      if (d.feat_out) {
+        const int64_t u = ctr_ldg(d.feat_users + idx), i = item >= 0 ? item : ctr_ldg(d.feat_items + idx);
+        bad = bad || u < 0 || u >= d.num_users || i < 0 || i >= d.num_items;
+        s_fu[threadIdx.x] = u;
+        s_fi[threadIdx.x] = i;
+      }
+      if (d.hist_out) {
+        int64_t u = ctr_ldg(d.hist_users + idx);
+        if (u < 0 || u >= d.hist_rows) {
+          bad = true;
+          u = 0;
+        }
+        s_hu[threadIdx.x] = u;
+      }
+      if (bad && d.err_flag) *(CTR_GLOBAL int32_t*)d.err_flag = 1;
+    }
+    __syncthreads();
+    for (int c = 0; c < d.ncols; ++c) {
+      const ctr_loader_col_t& col = d.cols[c];
+      if (c == nd.item_col) {  // int64, width 1 (checked by the entry point)
+        const CTR_GLOBAL int64_t* s = (const CTR_GLOBAL int64_t*)col.src;
+        CTR_GLOBAL int64_t* o = (CTR_GLOBAL int64_t*)col.dst;
+        for (int r = threadIdx.x; r < cnt; r += kBlock) o[(base + r) * col.ldd] = s_neg[r] >= 0 ? s_neg[r] : s[s_idx[r] * col.lds];
+      } else if (c == nd.rating_col) {  // float32, width 1
+        const CTR_GLOBAL float* s = (const CTR_GLOBAL float*)col.src;
+        CTR_GLOBAL float* o = (CTR_GLOBAL float*)col.dst;
+        for (int r = threadIdx.x; r < cnt; r += kBlock) o[(base + r) * col.ldd] = s_neg[r] >= 0 ? 0.0f : s[s_idx[r] * col.lds];
+      } else if (col.elem_bytes == 8) {
+        copy_rows<uint64_t>(col.src, col.lds, col.dst, col.ldd, col.width, cnt, s_idx, base);
+      } else {
+        copy_rows<uint32_t>(col.src, col.lds, col.dst, col.ldd, col.width, cnt, s_idx, base);
       }
     }
-    if (d.hist_out) {
-      if (hist16)
-        copy_rows<ctr_u32x4>(d.history, d.ld_history / 2, d.hist_out, d.hist_ldo / 2, (int)(d.hist_len / 2), cnt, s_hu, base);
-      else
-        copy_rows<uint64_t>(d.history, d.ld_history, d.hist_out, d.hist_ldo, (int)d.hist_len, cnt, s_hu, base);
-    }
+    write_joins(d, cnt, base, hist16, s_fu, s_fi, s_hu);
     __syncthreads();  // the next pass rewrites the LDS rows
   }
 }
@@ -162,15 +291,8 @@ int check_range(int64_t n, int64_t epoch, int64_t first, int64_t count) {
   return CTR_OK;
 }
 
-}  // namespace
-
-extern "C" int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t epoch, int64_t first, int64_t count,
-                              int shuffle, void* stream) {
-  CTR_REQUIRE(count >= 0, CTR_EINVAL);
-  if (count == 0) return CTR_OK;
-  CTR_REQUIRE(loader, CTR_EINVAL);
-  const ctr_loader_t& d = *loader;
-  if (int rc = check_range(d.n, epoch, first, count)) return rc;
+// the descriptor's own checks, shared by both entry points; *hist16: history rows move as 16-byte pieces
+int check_loader(const ctr_loader_t& d, int* hist16) {
   CTR_REQUIRE(d.ncols >= 0 && d.ncols <= CTR_MAX_FIELDS, CTR_EINVAL);
   for (int c = 0; c < d.ncols; ++c) {
     const ctr_loader_col_t& col = d.cols[c];
@@ -186,19 +308,69 @@ extern "C" int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t
                 CTR_EINVAL);
     CTR_REQUIRE(2 + (int64_t)d.user_width + d.item_width <= kMaxRowUnits, CTR_ELIMIT);
   }
-  int hist16 = 0;
+  *hist16 = 0;
   if (d.hist_out) {
     CTR_REQUIRE(d.hist_users && d.history && d.hist_rows > 0 && d.hist_len >= 1 && d.ld_history >= d.hist_len &&
                     d.hist_ldo >= d.hist_len,
                 CTR_EINVAL);
     CTR_REQUIRE(d.hist_len <= kMaxRowUnits, CTR_ELIMIT);
     CTR_REQUIRE(aligned_to(d.history, 8) && aligned_to(d.hist_out, 8), CTR_EALIGN);
-    hist16 = d.hist_len % 2 == 0 && d.ld_history % 2 == 0 && d.hist_ldo % 2 == 0 && ctr_aligned16(d.history) &&
-             ctr_aligned16(d.hist_out);
+    *hist16 = d.hist_len % 2 == 0 && d.ld_history % 2 == 0 && d.hist_ldo % 2 == 0 && ctr_aligned16(d.history) &&
+              ctr_aligned16(d.hist_out);
   }
+  return CTR_OK;
+}
+
+}  // namespace
+
+extern "C" int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t epoch, int64_t first, int64_t count,
+                              int shuffle, void* stream) {
+  CTR_REQUIRE(count >= 0, CTR_EINVAL);
+  if (count == 0) return CTR_OK;
+  CTR_REQUIRE(loader, CTR_EINVAL);
+  const ctr_loader_t& d = *loader;
+  if (int rc = check_range(d.n, epoch, first, count)) return rc;
+  int hist16 = 0;
+  if (int rc = check_loader(d, &hist16)) return rc;
   const int grid = ctr_stream_grid(count, kTile);
   hipLaunchKernelGGL(load_batch_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d,
                      make_perm(d.n, seed, epoch, shuffle != 0), first, count, hist16);
+  return ctr_launch_status();
+}
+
+extern "C" int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
+                                  int64_t first, int64_t count, int shuffle, void* stream) {
+  CTR_REQUIRE(count >= 0, CTR_EINVAL);
+  if (count == 0) return CTR_OK;
+  CTR_REQUIRE(loader && neg, CTR_EINVAL);
+  const ctr_loader_t& d = *loader;
+  const ctr_loader_neg_t& g = *neg;
+  CTR_REQUIRE(g.negatives >= 1 && d.n >= 1 && d.n <= (1ll << 62) / (1 + (int64_t)g.negatives), CTR_EINVAL);
+  const int64_t m = d.n * (1 + (int64_t)g.negatives);
+  if (int rc = check_range(m, epoch, first, count)) return rc;
+  int hist16 = 0;
+  if (int rc = check_loader(d, &hist16)) return rc;
+  CTR_REQUIRE(g.users && g.indptr && g.indices && g.num_users >= 1 && g.num_items >= 1 && g.num_items < (1ll << 31),
+              CTR_EINVAL);
+  CTR_REQUIRE(g.rating_col >= 0 && g.rating_col < d.ncols && g.item_col >= -1 && g.item_col < d.ncols &&
+                  g.item_col != g.rating_col,
+              CTR_EINVAL);
+  CTR_REQUIRE(d.cols[g.rating_col].width == 1 && d.cols[g.rating_col].elem_bytes == 4, CTR_EINVAL);
+  CTR_REQUIRE(g.item_col < 0 || (d.cols[g.item_col].width == 1 && d.cols[g.item_col].elem_bytes == 8), CTR_EINVAL);
+  LoaderDraw nd;
+  nd.nkey = mix64(seed ^ mix64((uint64_t)epoch * 0x100000001B3ull + 4));
+  nd.per = 1 + (uint64_t)g.negatives;
+  nd.users = g.users;
+  nd.indptr = g.indptr;
+  nd.indices = g.indices;
+  nd.num_users = g.num_users;
+  nd.num_items = (uint64_t)g.num_items;
+  nd.fail_flag = g.fail_flag;
+  nd.item_col = g.item_col;
+  nd.rating_col = g.rating_col;
+  const int grid = ctr_stream_grid(count, kTile);
+  hipLaunchKernelGGL(load_batch_neg_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d,
+                     make_perm(m, seed, epoch, shuffle != 0), nd, first, count, hist16);
   return ctr_launch_status();
 }
 

@@ -1,4 +1,4 @@
 from .features import FeatureAssembler
-from .loader import DeviceLoader
+from .loader import DeviceLoader, ObservedPairs
 
-__all__ = ["FeatureAssembler", "DeviceLoader"]
+__all__ = ["FeatureAssembler", "DeviceLoader", "ObservedPairs"]

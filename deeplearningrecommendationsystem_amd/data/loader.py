@@ -14,6 +14,13 @@ and piece r is rank r's tail batch.  With world == 1 that is the usual N % batch
 The loader owns one set of static full-size batch buffers -- what a captured training graph reads, see
 ``Trainer.train_epoch`` -- and a separately allocated set for the tail batch.  ``epoch()`` yields views of them: a batch
 is valid until the next one is drawn.  There is no CPU fallback.
+
+Drawn negatives.  A loader built with ``negatives=k`` and ``observed=ObservedPairs(...)`` is given the positives only
+and emits, per epoch, every positive once and k negatives per positive, drawn inside the same launch and shuffled in
+with the positives (``ctr_load_batch_neg``; the definition stands in the kernel file's header comment).  Everything
+above then speaks of the virtual epoch of ``num_samples = num_positives * (1 + k)`` positions.  An unshuffled pass --
+what ``valid_epoch`` / ``test_epoch`` ask for -- shows each positive followed by its k negatives, the same ones every
+time.
 """
 from __future__ import annotations
 
@@ -42,6 +49,45 @@ def batch_ranges(n: int, batch_size: int, drop_last: bool = False, rank: int = 0
     return out
 
 
+class ObservedPairs:
+    """The (user, item) pairs no negative may repeat, as a CSR over users: ``indptr`` (num_users + 1) int64, ``indices``
+    int32 item ids, ascending and distinct within a row -- 4 B per pair whatever ``num_items`` is.  ``users`` / ``items``
+    are 1-D int64 tensors, or sequences of them to union (train | valid | test).  Built once with torch ops on the
+    device the ids live on."""
+
+    def __init__(self, users, items, num_users, num_items):
+        users = torch.cat([t.reshape(-1) for t in users]) if isinstance(users, (list, tuple)) else users
+        items = torch.cat([t.reshape(-1) for t in items]) if isinstance(items, (list, tuple)) else items
+        self.num_users, self.num_items = int(num_users), int(num_items)
+        if self.num_users < 1 or self.num_items < 1:
+            raise ValueError("ObservedPairs: num_users and num_items must be positive")
+        if self.num_items >= 1 << 31:
+            raise ValueError("ObservedPairs: num_items must be below 2^31 (item ids are stored as int32)")
+        if self.num_users >= 1 << 31:
+            raise ValueError("ObservedPairs: num_users must be below 2^31")
+        if users.dtype != torch.int64 or items.dtype != torch.int64 or users.dim() != 1 or users.shape != items.shape:
+            raise ValueError("ObservedPairs: users and items must be 1-D int64 tensors of one length")
+        if users.numel() and bool(((users < 0) | (users >= self.num_users) | (items < 0) | (items >= self.num_items)).any()):
+            raise IndexError("index out of range in self")
+        keys = torch.unique(users * self.num_items + items)          # sorted: by user, then by item
+        rows = torch.div(keys, self.num_items, rounding_mode="floor")
+        self.indices = (keys - rows * self.num_items).to(torch.int32)
+        self.indptr = torch.zeros(self.num_users + 1, dtype=torch.int64, device=users.device)
+        torch.cumsum(torch.bincount(rows, minlength=self.num_users), 0, out=self.indptr[1:])
+
+    def __len__(self):
+        return self.indices.shape[0]
+
+    def contains(self, users, items) -> torch.Tensor:
+        """bool tensor: is (users[b], items[b]) observed; ids outside the tables are not"""
+        inside = (users >= 0) & (users < self.num_users) & (items >= 0) & (items < self.num_items)
+        rows = torch.repeat_interleave(torch.arange(self.num_users, device=self.indptr.device), self.indptr.diff())
+        keys = rows * self.num_items + self.indices
+        query = torch.where(inside, users * self.num_items + items, torch.full_like(users, -1))
+        at = torch.searchsorted(keys, query).clamp_(max=max(len(self) - 1, 0))
+        return inside & (keys[at] == query) if len(self) else torch.zeros_like(inside)
+
+
 class _Column:
     """an (N,) or (N, w) int64 / float32 source copied row by row"""
 
@@ -67,7 +113,7 @@ class _Buffers:
 
     def __init__(self, loader, rows):
         self.desc = d = _lib.Loader()
-        d.n = loader.num_samples
+        d.n = loader.num_positives
         d.ncols = len(loader._columns)
         self.cols = []
         for k, c in enumerate(loader._columns):
@@ -107,13 +153,17 @@ class DeviceLoader:
     ``for args, rating in loader.epoch(e)`` draws this rank's batches of epoch ``e``: ``model(*args)`` against
     ``rating``.  ``len(loader)`` batches; the full-size ones are views of ``static_batch()``."""
 
-    def __init__(self, family, columns, ids, feature, history, batch_size, seed, shuffle, drop_last, rank, world):
+    def __init__(self, family, columns, ids, feature, history, batch_size, seed, shuffle, drop_last, rank, world,
+                 negatives=0, observed=None):
         if int(batch_size) < 1:
             raise ValueError("DeviceLoader: batch_size must be positive")
         if int(world) < 1 or not 0 <= int(rank) < int(world):
             raise ValueError("DeviceLoader: need 0 <= rank < world")
         if not 0 <= int(seed) < 1 << 64:
             raise ValueError("DeviceLoader: seed must fit an unsigned 64-bit integer")
+        self.negatives = int(negatives)
+        if self.negatives < 0 or (self.negatives > 0) != (observed is not None):
+            raise ValueError("DeviceLoader: negatives > 0 and observed=ObservedPairs(...) go together")
         samples = [t for _, t in columns] + list(ids)
         tables = [feature.user_features, feature.item_features] if feature is not None else []
         _lib.require_device(*samples, *tables, history)
@@ -125,13 +175,18 @@ class DeviceLoader:
             raise ValueError("DeviceLoader: the sample tensors must have one length, at least 1")
         if history is not None and (history.dtype != torch.int64 or history.dim() != 2 or 0 in history.shape):
             raise ValueError("DeviceLoader: history must be a (U, L) int64 matrix")
-        self.family, self.num_samples, self.device = family, n, samples[0].device
+        # the epoch: every positive, and `negatives` drawn samples per positive
+        self.family, self.num_positives, self.device = family, n, samples[0].device
+        self.num_samples = n = n * (1 + self.negatives)
         self.batch_size, self.seed, self.shuffle = int(batch_size), int(seed), bool(shuffle)
         self.drop_last, self.rank, self.world = bool(drop_last), int(rank), int(world)
         ids = [t.contiguous() for t in ids]
         self._feature = None if feature is None else (feature, ids[0], ids[1])
         self._history = None if history is None else (history.contiguous(), ids[0])
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._neg = self._fail = None
+        if self.negatives:
+            self._describe_negatives(observed, ids[0])
         self._ranges = batch_ranges(n, self.batch_size, self.drop_last, self.rank, self.world)
         # a tail piece that happens to hold batch_size samples is still the tail: it has its own buffers
         self._num_full = (n // self.batch_size) // self.world
@@ -139,27 +194,50 @@ class DeviceLoader:
         self._full = _Buffers(self, self.batch_size) if self._num_full else None
         self._tail = _Buffers(self, tail) if tail else None
 
+    def _describe_negatives(self, observed, users):
+        """the ``ctr_loader_neg_t`` both buffer sets share"""
+        _lib.require_device(observed.indptr, observed.indices)
+        rating = self._columns[-1]                         # every family: the ratings come last
+        if rating.width != 1 or rating.src.dtype != torch.float32:
+            raise ValueError("DeviceLoader: with negatives the ratings must be (N,) or (N, 1) float32")
+        self._fail = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._neg_keep = (observed, users)                 # what the descriptor points into
+        self._neg = g = _lib.LoaderNeg()
+        g.negatives = self.negatives
+        g.item_col = {"pairs": 1, "features": -1, "sequences": 0}[self.family]    # items / (in the join) / targets
+        g.rating_col = len(self._columns) - 1
+        g.users = users.data_ptr()
+        g.num_users, g.num_items = observed.num_users, observed.num_items
+        g.indptr, g.indices = observed.indptr.data_ptr(), observed.indices.data_ptr()
+        g.fail_flag = self._fail.data_ptr()
+
     # -- constructors ------------------------------------------------------------------------------------------
     @classmethod
-    def pairs(cls, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0, world=1):
-        """MF / NeuralCF: batches ``(user_idx (B,), item_idx (B,)), rating`` -- rating (N,) or (N, 1) float32"""
+    def pairs(cls, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0, world=1,
+              negatives=0, observed=None):
+        """MF / NeuralCF: batches ``(user_idx (B,), item_idx (B,)), rating`` -- rating (N,) or (N, 1) float32.
+        ``negatives=k, observed=ObservedPairs(...)`` (every constructor): the samples are positives, and each epoch adds
+        k drawn negatives per positive, rating 0"""
         cols = [("users", users), ("items", items), ("ratings", ratings)]
-        return cls("pairs", cols, [users, items], None, None, batch_size, seed, shuffle, drop_last, rank, world)
+        return cls("pairs", cols, [users, items], None, None, batch_size, seed, shuffle, drop_last, rank, world,
+                   negatives, observed)
 
     @classmethod
     def features(cls, assembler, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
-                 world=1):
-        """feature models: batches ``(x (B, assembler.width),), rating`` -- x as ``assembler.feature`` builds it"""
+                 world=1, negatives=0, observed=None):
+        """feature models: batches ``(x (B, assembler.width),), rating`` -- x as ``assembler.feature`` builds it (for a
+        negative: from the drawn item's row)"""
         return cls("features", [("ratings", ratings)], [users, items], assembler, None, batch_size, seed, shuffle,
-                   drop_last, rank, world)
+                   drop_last, rank, world, negatives, observed)
 
     @classmethod
     def sequences(cls, history, users, targets, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
-                  world=1):
+                  world=1, negatives=0, observed=None):
         """DIN / DIEN: batches ``(hist (B, L), target (B,)), rating`` -- hist row = ``history[users[sample]]``,
-        ``history`` one (U, L) int64 row per USER"""
+        ``history`` one (U, L) int64 row per USER (a negative replaces the target and keeps the row)"""
         cols = [("targets", targets), ("ratings", ratings)]
-        return cls("sequences", cols, [users, targets], None, history, batch_size, seed, shuffle, drop_last, rank, world)
+        return cls("sequences", cols, [users, targets], None, history, batch_size, seed, shuffle, drop_last, rank, world,
+                   negatives, observed)
 
     # -- batches -----------------------------------------------------------------------------------------------
     def __len__(self):
@@ -180,6 +258,11 @@ class DeviceLoader:
         return None if self._full is None else self._full.batch(self.family)
 
     def _launch(self, buffers, epoch, first, count, shuffle):
+        if self._neg is not None:
+            rc = _lib.load().ctr_load_batch_neg(C.addressof(buffers.desc), C.addressof(self._neg), self.seed, epoch, first,
+                                                count, int(shuffle), _lib.stream_ptr())
+            _lib.check(rc, "ctr_load_batch_neg")
+            return
         rc = _lib.load().ctr_load_batch(C.addressof(buffers.desc), self.seed, epoch, first, count, int(shuffle),
                                         _lib.stream_ptr())
         _lib.check(rc, "ctr_load_batch")
@@ -196,7 +279,8 @@ class DeviceLoader:
             yield buffers.batch(self.family)
 
     def indices(self, epoch: int, first: int = 0, count=None, shuffle=None) -> torch.Tensor:
-        """sample indices of positions [first, first + count) of epoch ``epoch`` (int64, on the device)"""
+        """sample indices of positions [first, first + count) of epoch ``epoch`` (int64, on the device); with negatives
+        the index v over the virtual epoch: positive ``v // (1 + k)``, slot ``v % (1 + k)``"""
         count = self.num_samples - first if count is None else count
         if epoch < 0 or first < 0 or count < 0 or first + count > self.num_samples:
             raise ValueError("DeviceLoader.indices(): position range outside the epoch")
@@ -208,7 +292,11 @@ class DeviceLoader:
         return out
 
     def check_bad_index(self):
-        """raise the IndexError of an id outside its join table seen by any batch since the last call"""
+        """raise the IndexError of an id outside its join table seen by any batch since the last call, or the
+        RuntimeError of a negative that could not be drawn"""
         if int(self._err.item()):
             self._err.zero_()
             raise IndexError("index out of range in self")
+        if self._fail is not None and int(self._fail.item()):
+            self._fail.zero_()
+            raise RuntimeError("negative sampling: a user has (practically) no item outside the observed pairs")

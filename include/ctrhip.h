@@ -702,6 +702,12 @@ int ctr_assemble_features(const int64_t* users, const int64_t* items, int64_t n,
  * ctr_load_batch writes the batch of positions [first, first + count), first + count <= n.
  * ctr_loader_indices writes their sample indices to out (count int64): the permutation alone, for inspection.
  * count == 0 is a no-op; n < 1, a negative epoch or first, or a range beyond n is CTR_EINVAL.
+ * ctr_load_batch_neg draws negatives inside the same launch: the epoch has n * (1 + negatives) positions, every
+ * positive once and `negatives` drawn items per positive, none of them in the observed set (a CSR over users); the
+ * definition stands in the header comment of csrc/loader.hip.  A negative is sample s with the drawn item in cols[item_col]
+ * (and in the feature join) and 0.0f in cols[rating_col].  The position range is checked against n * (1 + negatives);
+ * negatives < 1, a column index out of range or of the wrong width or element size, num_items < 1 or >= 2^31, or
+ * n * (1 + negatives) > 2^62 is CTR_EINVAL.  *fail_flag is raised when 2^14 draws of one slot were all observed.
  * ---------------------------------------------------------------------- */
 typedef struct ctr_loader_col {
   const void* src;      /* (n, width) elements, leading dimension lds */
@@ -741,6 +747,22 @@ int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t epoch, int
                    void* stream);
 int ctr_loader_indices(int64_t n, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle, int64_t* out,
                        void* stream);
+
+typedef struct ctr_loader_neg {
+  int32_t negatives;            /* k >= 1 */
+  int32_t item_col;             /* index into cols[] of the int64 width-1 item column, or -1 (features family) */
+  int32_t rating_col;           /* index into cols[] of the float32 width-1 rating column */
+  int32_t reserved;
+  const int64_t* users;         /* (n,) user id of every positive */
+  int64_t num_users;
+  int64_t num_items;
+  const int64_t* indptr;        /* (num_users + 1) */
+  const int32_t* indices;       /* sorted, distinct per row */
+  int32_t* fail_flag;           /* device int32, nullable */
+} ctr_loader_neg_t;
+
+int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
+                       int64_t first, int64_t count, int shuffle, void* stream);
 
 /* ------------------------------------------------------------------------
  * Head folding: a linear layer W (n x k, bias b) whose output feeds ONLY a single-unit layer u is the
