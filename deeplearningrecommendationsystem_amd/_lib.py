@@ -23,6 +23,7 @@ CTR_NCF_PROJ_MAX_ROWS = 16384
 CTR_NCF_PROJ_COUNT_STRIDE = 72
 CTR_ROWS1_MAX_ROWS = 32768
 CTR_GDCF_MAX_DIM = 256
+CTR_GROUP_MAX_K = 4095
 FIELD_ID_I64, FIELD_ID_F32, FIELD_BAG, FIELD_DENSE, FIELD_PROD_I64 = range(5)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = range(3)
 
@@ -198,6 +199,8 @@ SIGNATURES = {
     "ctr_load_batch": (_i, [_p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p: address of a host Loader
     "ctr_loader_indices": (_i, [_l, C.c_uint64, _l, _l, _l, _i, _p, _p]),
     "ctr_load_batch_neg": (_i, [_p, _p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p, _p: host Loader, host LoaderNeg
+    "ctr_eval_candidates": (_i, [_p, _p, _l, _p, _p, _l, _l, _l, _i, C.c_uint64, _p, _l, _p, _p, _p]),
+    "ctr_group_rank": (_i, [_p, _l, _l, _i, _p, _p, _p]),
     "ctr_shard_bucket": (_i, [_p, _l, _i, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_bucket_padded": (_i, [_p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_recv_rows": (_i, [_p, _l, _l, _p, _p, _p, _p]),

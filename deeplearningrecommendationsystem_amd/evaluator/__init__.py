@@ -1,4 +1,6 @@
 from .evaluator import Evaluator
 from .ranking import Ranking, RankingMetrics, itemid_matrix, ranking_metrics, ranking_partials, remove_itemid
+from .sampled import GroupRankingMetrics, group_histogram, group_ranking_metrics, group_ranks
 
-__all__ = ["Evaluator", "Ranking", "RankingMetrics", "itemid_matrix", "ranking_metrics", "ranking_partials", "remove_itemid"]
+__all__ = ["Evaluator", "Ranking", "RankingMetrics", "itemid_matrix", "ranking_metrics", "ranking_partials", "remove_itemid",
+           "GroupRankingMetrics", "group_histogram", "group_ranking_metrics", "group_ranks"]

@@ -1541,3 +1541,61 @@ def rank_metrics_scores(scores: torch.Tensor, top: torch.Tensor, k: int, act_off
                 alen.data_ptr(), n_real.data_ptr(), pad.data_ptr(), parts.data_ptr(), err.data_ptr(),
                 _lib.stream_ptr())
     _lib.check(rc, "ctr_rank_metrics_scores")
+
+
+# ---------------------------------------------------------------------------
+# sampled leave-one-out evaluation (csrc/group_eval.hip)
+# ---------------------------------------------------------------------------
+GROUP_MAX_K = _lib.CTR_GROUP_MAX_K
+
+
+def eval_candidates(users: torch.Tensor, items: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor,
+                    num_users: int, num_items: int, k: int, seed: int, err: torch.Tensor, fail: torch.Tensor,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(N, 1 + k) int64 candidates: column 0 the held-out item, then k distinct items that are neither it nor observed
+    for the user (``ctr_eval_candidates``).  ``out``: an (N, >= 1 + k) int64 tensor with unit inner stride to write
+    into (columns past 1 + k are left alone); ``err`` / ``fail``: device int32 flags, raised and never cleared."""
+    _i64(users, items, indptr)
+    _lib.require_device(indices, err, fail, out)
+    if users.dim() != 1 or users.shape != items.shape:
+        raise ValueError("eval_candidates: users and items must be 1-D tensors of one length")
+    if indices.dtype != torch.int32 or not indices.is_contiguous() or indptr.numel() != num_users + 1:
+        raise ValueError("eval_candidates: indptr (num_users + 1) int64, indices contiguous int32")
+    if not 1 <= int(k) <= GROUP_MAX_K:
+        raise ValueError(f"eval_candidates: negatives = {k} outside [1, {GROUP_MAX_K}]")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("eval_candidates: seed must fit an unsigned 64-bit integer")
+    n = users.shape[0]
+    if out is None:
+        out = torch.empty((n, 1 + k), dtype=torch.int64, device=users.device)
+    elif out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != n or out.shape[1] < 1 + k or \
+            (n > 0 and out.stride(1) != 1) or (n > 1 and out.stride(0) < 1 + k):
+        raise ValueError("eval_candidates: out must be an (N, >= 1 + k) int64 tensor with unit inner stride")
+    ld = out.stride(0) if n > 1 else max(out.shape[1], 1 + k)
+    rc = _timed("eval_candidates", lambda: (16 * n + 8 * n * (1 + k), 0), _lib.load().ctr_eval_candidates,
+                _lib.ptr(users) if n else None, _lib.ptr(items) if n else None, n, indptr.data_ptr(),
+                _lib.ptr(indices) if indices.numel() else None, indices.numel(), int(num_users), int(num_items), int(k),
+                int(seed), _lib.ptr(out) if n else None, ld, err.data_ptr(), fail.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_eval_candidates")
+    return out
+
+
+def group_rank(scores: torch.Tensor, k: int, hist: torch.Tensor, ranks: Optional[torch.Tensor] = None) -> None:
+    """``ctr_group_rank``: scores (N, >= 1 + k) float32 with unit inner stride, slot 0 of a row the positive;
+    ``hist`` (k + 1,) int64 is added to, ``ranks`` (N,) int32 (optional) receives every group's rank"""
+    _lib.require_device(scores, hist, ranks)
+    if not 1 <= int(k) <= GROUP_MAX_K:
+        raise ValueError(f"group_rank: negatives = {k} outside [1, {GROUP_MAX_K}]")
+    n = scores.shape[0] if scores.dim() == 2 else -1
+    if scores.dtype != torch.float32 or n < 0 or scores.shape[1] < 1 + k or (n > 0 and scores.stride(1) != 1) or \
+            (n > 1 and scores.stride(0) < 1 + k):
+        raise ValueError("group_rank: scores must be an (N, >= 1 + k) float32 tensor with unit inner stride")
+    if hist.dtype != torch.int64 or hist.shape != (k + 1,) or not hist.is_contiguous():
+        raise ValueError("group_rank: hist must be a contiguous (k + 1,) int64 tensor")
+    if ranks is not None and (ranks.dtype != torch.int32 or ranks.shape != (n,) or not ranks.is_contiguous()):
+        raise ValueError("group_rank: ranks must be a contiguous (N,) int32 tensor")
+    ld = scores.stride(0) if n > 1 else max(scores.shape[1], 1 + k)
+    rc = _timed("group_rank", lambda: (4 * n * (1 + k) + (4 * n if ranks is not None else 0), 0),
+                _lib.load().ctr_group_rank, _lib.ptr(scores) if n else None, ld, n, int(k), _lib.ptr(ranks),
+                hist.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_group_rank")

@@ -17,6 +17,7 @@ class Trainer:
         self.train_loss = self.valid_loss = self.test_loss = None
         self.predictions_train = self.predictions_valid = self.predictions_test = None
         self.train_rating = self.valid_rating = self.test_rating = None
+        self.rank_metrics = self.predictions_rank = self.rank_rating = self.rank_loss = None
         self._graph = graph
         self._graphed = None
         self._graph_key = None
@@ -159,6 +160,29 @@ class Trainer:
 
     def test_epoch(self, loader):
         self.predictions_test, self.test_rating, self.test_loss = self._eval_epoch(loader)
+
+    def rank_epoch(self, loader, negatives=None, cutoffs=(10,)):
+        """sampled leave-one-out evaluation: an unshuffled pass over a loader whose samples lie in groups of
+        1 + ``negatives``, the positive first (``data.LeaveOneOut``'s loaders, or a ``DeviceLoader`` that draws its own
+        negatives, whose count is the default), then HR@c / NDCG@c / MRR@c for every c of ``cutoffs`` and MRR from
+        the gathered predictions (``evaluator.sampled``).  Keeps and returns ``rank_metrics``; the predictions, ratings
+        and loss of the pass are kept as ``predictions_rank`` / ``rank_rating`` / ``rank_loss``."""
+        from ..evaluator.sampled import group_ranking_metrics
+        if negatives is None:
+            negatives = getattr(loader, "negatives", 0)
+            if negatives < 1:
+                raise ValueError("rank_epoch: the loader draws no negatives of its own; pass negatives=k")
+        negatives = int(negatives)
+        if negatives < 1:
+            raise ValueError("rank_epoch: negatives must be positive")
+        if loader.world != 1:
+            raise ValueError("rank_epoch: the batches of a loader with world > 1 interleave across ranks and break the "
+                             "groups; evaluate with a world=1 loader")
+        if loader.num_samples % (1 + negatives):
+            raise ValueError(f"rank_epoch: {loader.num_samples} samples are not groups of 1 + {negatives}")
+        self.predictions_rank, self.rank_rating, self.rank_loss = self._eval_epoch(loader)
+        self.rank_metrics = group_ranking_metrics(self.predictions_rank, negatives, cutoffs)
+        return self.rank_metrics
 
     def model_eval(self, epoch):
         """prints the reference's per-epoch report (trainer/trainer.py:116-146)"""

@@ -765,6 +765,37 @@ int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, 
                        int64_t first, int64_t count, int shuffle, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Sampled leave-one-out evaluation (csrc/group_eval.hip): every held-out positive is ranked against k sampled
+ * negatives, "1 positive + 99 negatives, HR@10 / NDCG@10".
+ * ctr_eval_candidates draws the candidates.  n positives (users[s], items[s]); the observed set is the loader's CSR
+ * (indptr (num_users + 1) int64, indices (nnz) int32 ascending and distinct within a row).  cand is (n, 1 + k) int64
+ * with leading dimension ld >= 1 + k; columns past 1 + k are not touched.  Row s:
+ *   cand[s, 0]    = items[s]
+ *   gseed_s       = mix64(seed ^ mix64(s * 0x100000001B3 + 5))
+ *   q_t           = perm_{num_items}(gseed_s, 0, t),  t = 0 .. num_items - 1      (csrc/loader_perm.h)
+ *   cand[s, 1..k] = the first k of q_0, q_1, .. that are neither items[s] nor observed for users[s], in that order
+ * so the k negatives are distinct and the draw with k' < k is a prefix of the draw with k.  Fewer than k eligible
+ * items: the remaining slots are written -1 and *fail_flag is raised.  users[s] outside [0, num_users): the k slots
+ * are written 0 and *err_flag is raised.  A CSR row with indptr[u] < 0, indptr[u + 1] < indptr[u] or
+ * indptr[u + 1] > nnz is read as empty and raises *err_flag.  Both flags are device int32, nullable.
+ * 1 <= k <= CTR_GROUP_MAX_K, 1 <= num_items < 2^31, num_users >= 1, nnz >= 0 (CTR_EINVAL otherwise); n == 0 is a
+ * no-op.
+ * ctr_group_rank ranks the positive of every group.  scores: n groups of 1 + k float32, slot 0 the positive,
+ * leading dimension ld >= 1 + k (ld == 1 + k: the flat prediction vector of an evaluation pass).
+ *   rank[g]  = #{ j in 1..k : !(scores[g, j] < scores[g, 0]) }
+ *   hist[r] += #{ g : rank[g] == r },  r = 0..k
+ * The one comparison makes ties and NaN count against the positive.  ranks_out (n) int32 is nullable; hist (k + 1)
+ * int64 is ADDED to (integer atomics: exact, independent of the launch geometry), the caller zeroes it.
+ * 1 <= k <= CTR_GROUP_MAX_K (CTR_EINVAL otherwise), n <= 2^40 (CTR_ELIMIT beyond); n == 0 is a no-op.
+ * ---------------------------------------------------------------------- */
+#define CTR_GROUP_MAX_K 4095
+int ctr_eval_candidates(const int64_t* users, const int64_t* items, int64_t n, const int64_t* indptr,
+                        const int32_t* indices, int64_t nnz, int64_t num_users, int64_t num_items, int k,
+                        uint64_t seed, int64_t* cand, int64_t ld, int32_t* err_flag, int32_t* fail_flag, void* stream);
+int ctr_group_rank(const float* scores, int64_t ld, int64_t n, int k, int32_t* ranks_out, int64_t* hist,
+                   void* stream);
+
+/* ------------------------------------------------------------------------
  * Head folding: a linear layer W (n x k, bias b) whose output feeds ONLY a single-unit layer u is the
  * k-wide dot product  (h W^T + b).u + b2 == h.v + c,  v = W^T u,  c = b.u + b2.  NeuralCF ends like
  * that (model/neuralcf.py:27 linear, :50-56 cat + linear2): folding per step keeps the 8 -> mf_dim
