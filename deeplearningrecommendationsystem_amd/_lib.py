@@ -199,6 +199,7 @@ SIGNATURES = {
     "ctr_load_batch": (_i, [_p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p: address of a host Loader
     "ctr_loader_indices": (_i, [_l, C.c_uint64, _l, _l, _l, _i, _p, _p]),
     "ctr_load_batch_neg": (_i, [_p, _p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p, _p: host Loader, host LoaderNeg
+    "ctr_load_batch_groups": (_i, [_p, _p, C.c_uint64, _l, _l, _l, _i, _p]),   # as ctr_load_batch_neg
     "ctr_eval_candidates": (_i, [_p, _p, _l, _p, _p, _l, _l, _l, _i, C.c_uint64, _p, _l, _p, _p, _p]),
     "ctr_group_rank": (_i, [_p, _l, _l, _i, _p, _p, _p]),
     "ctr_shard_bucket": (_i, [_p, _l, _i, _l, _p, _p, _p, _p, _p, _p]),
@@ -222,6 +223,8 @@ SIGNATURES = {
     "ctr_fold_head_bwd": (_i, [_p, _i, _p, _l, _p, _i, _i, _p, _p, _p, _p, _l, _p, _p, _p]),
     "ctr_bce_fwd": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p, _p, _p]),
     "ctr_bce_bwd": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p]),
+    "ctr_group_loss_fwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _l, _p, _p, _p]),
+    "ctr_group_loss_bwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _l, _p]),
     "ctr_din_scatter_bwd": (_i, [_p, _l, _l, _i, _i, _p, _l, _p, _p, _l, _i, _p, _p]),
     "ctr_linear_group_fwd": (_i, [_p, _l, _p, _l, _p, _p, _l, _i, _p, _l, _p, _l, _l, _i, _i, _i, _p]),
     "ctr_linear_dx_masked": (_i, [_p, _l, _p, _l, _p, _l, _i, _p, _l, _i, _p, _l, _p, _l, _p, _l, _i, _l, _i, _i, _p]),

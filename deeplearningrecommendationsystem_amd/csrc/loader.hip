@@ -39,6 +39,21 @@
 // per observed pair whatever num_items is, where the sampler's bitmap is num_users * num_items / 8 B.
 // tests/loader_neg_numpy.py restates this.
 //
+// Grouped epochs (ctr_load_batch_groups).  The shuffle above scatters a positive and its negatives over the epoch; a
+// loss over the group (group_loss.hip) needs them side by side.  With N positives and k = negatives, position p of
+// epoch e holds
+//     g = p / (1 + k);  j = p % (1 + k)
+//     s = perm_N(seed, e, g)             the permutation over N, not over M;  s = g when shuffle == 0
+//     v = s * (1 + k) + j
+//     outputs = exactly what ctr_load_batch_neg defines for virtual index v
+//               (j == 0: positive s;  j >= 1: the draw keyed by (seed, e, v))
+// Every batch whose first position and count are multiples of 1 + k is a run of whole groups, positive first.
+// Unshuffled the output equals ctr_load_batch_neg's bit for bit; shuffled, the epoch emits the same multiset of
+// samples as ctr_load_batch_neg does for the same (seed, e), because the draws depend on (seed, e, v) only and
+// (g, j) -> v is a bijection of [0, M); the order of groups is a bijection of [0, N).  A 64-position tile usually
+// cuts a group (1 + k seldom divides 64), so every position derives its own g and j.
+// tests/loader_group_numpy.py restates this.
+//
 // The draw is a chain of dependent loads per position: users[s] -> indptr[u], indptr[u + 1] -> about log2(row length)
 // probes per try.  Spreading a tile's 64 chains over the four waves would not shorten any of them, and a batch of
 // 65536 positions is 1024 workgroups of 2 KiB LDS and few registers, all resident at once (4 per CU), so every chain of
@@ -170,20 +185,30 @@ __device__ __forceinline__ int64_t draw_negative(const LoaderDraw& nd, uint64_t 
   return (int64_t)item;
 }
 
-// ctr_load_batch_neg: load_batch_kernel over the virtual epoch.  The index stage also decides positive or negative
-// and draws; s_neg holds the drawn item, -1 for a positive.  A kernel of its own, so that the plain loader keeps its
-// registers.
-__global__ void __launch_bounds__(kBlock)
-load_batch_neg_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, int64_t first, int64_t count,
-                      int hist16) {
+// ctr_load_batch_neg / ctr_load_batch_groups: load_batch_kernel over the virtual epoch.  The index stage also decides
+// positive or negative and draws; s_neg holds the drawn item, -1 for a positive.  kGrouped: pm permutes the N groups
+// and the position keeps its slot (header comment); otherwise pm permutes the M positions.  One body, a kernel per
+// arm, so that the plain loader and the ungrouped arm keep their registers.
+template <bool kGrouped>
+__device__ __forceinline__ void load_neg_tiles(const ctr_loader_t& d, const LoaderPerm& pm, const LoaderDraw& nd,
+                                               int64_t first, int64_t count, int hist16) {
   __shared__ int64_t s_idx[kTile], s_fu[kTile], s_fi[kTile], s_hu[kTile], s_neg[kTile];
   const int64_t tiles = (count + kTile - 1) / kTile;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t base = tile * kTile;
     const int cnt = (int)(count - base < kTile ? count - base : kTile);
     if ((int)threadIdx.x < cnt) {
-      const uint64_t v = (uint64_t)loader_index(pm, first + base + threadIdx.x);
-      const int64_t idx = (int64_t)(v / nd.per);
+      uint64_t v;
+      int64_t idx;
+      if constexpr (kGrouped) {
+        const uint64_t p = (uint64_t)(first + base + threadIdx.x);
+        const uint64_t g = p / nd.per;
+        idx = loader_index(pm, (int64_t)g);
+        v = (uint64_t)idx * nd.per + (p - g * nd.per);
+      } else {
+        v = (uint64_t)loader_index(pm, first + base + threadIdx.x);
+        idx = (int64_t)(v / nd.per);
+      }
       s_idx[threadIdx.x] = idx;
       bool bad = false;
       int64_t item = -1;
@@ -233,6 +258,18 @@ load_batch_neg_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDra
     write_joins(d, cnt, base, hist16, s_fu, s_fi, s_hu);
     __syncthreads();  // the next pass rewrites the LDS rows
   }
+}
+
+__global__ void __launch_bounds__(kBlock)
+load_batch_neg_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, int64_t first, int64_t count,
+                      int hist16) {
+  load_neg_tiles<false>(d, pm, nd, first, count, hist16);
+}
+
+__global__ void __launch_bounds__(kBlock)
+load_batch_groups_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, int64_t first, int64_t count,
+                         int hist16) {
+  load_neg_tiles<true>(d, pm, nd, first, count, hist16);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -297,8 +334,11 @@ extern "C" int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t
   return ctr_launch_status();
 }
 
-extern "C" int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
-                                  int64_t first, int64_t count, int shuffle, void* stream) {
+namespace {
+
+// both arms over the virtual epoch: the checks, the draw descriptor and the launch
+int launch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch, int64_t first,
+               int64_t count, int shuffle, bool grouped, hipStream_t st) {
   CTR_REQUIRE(count >= 0, CTR_EINVAL);
   if (count == 0) return CTR_OK;
   CTR_REQUIRE(loader && neg, CTR_EINVAL);
@@ -328,9 +368,25 @@ extern "C" int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_n
   nd.item_col = g.item_col;
   nd.rating_col = g.rating_col;
   const int grid = ctr_stream_grid(count, kTile);
-  hipLaunchKernelGGL(load_batch_neg_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d,
-                     make_perm(m, seed, epoch, shuffle != 0), nd, first, count, hist16);
+  if (grouped)
+    hipLaunchKernelGGL(load_batch_groups_kernel, dim3(grid), dim3(kBlock), 0, st, d,
+                       make_perm(d.n, seed, epoch, shuffle != 0), nd, first, count, hist16);
+  else
+    hipLaunchKernelGGL(load_batch_neg_kernel, dim3(grid), dim3(kBlock), 0, st, d,
+                       make_perm(m, seed, epoch, shuffle != 0), nd, first, count, hist16);
   return ctr_launch_status();
+}
+
+}  // namespace
+
+extern "C" int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
+                                  int64_t first, int64_t count, int shuffle, void* stream) {
+  return launch_neg(loader, neg, seed, epoch, first, count, shuffle, false, (hipStream_t)stream);
+}
+
+extern "C" int ctr_load_batch_groups(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed,
+                                     int64_t epoch, int64_t first, int64_t count, int shuffle, void* stream) {
+  return launch_neg(loader, neg, seed, epoch, first, count, shuffle, true, (hipStream_t)stream);
 }
 
 extern "C" int ctr_loader_indices(int64_t n, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle,

@@ -21,6 +21,14 @@ with the positives (``ctr_load_batch_neg``; the definition stands in the kernel 
 above then speaks of the virtual epoch of ``num_samples = num_positives * (1 + k)`` positions.  An unshuffled pass --
 what ``valid_epoch`` / ``test_epoch`` ask for -- shows each positive followed by its k negatives, the same ones every
 time.
+
+Grouped epochs.  The shuffle of the virtual epoch scatters a positive and its negatives over the batches.  A loader built
+with ``grouped=True`` shuffles the positives instead and keeps each one's k negatives behind it
+(``ctr_load_batch_groups``; the definition stands in the kernel file's header comment): every batch is a run of whole
+groups of ``1 + k`` samples, the positive first -- what ``loss.BPRLoss`` / ``loss.SampledSoftmaxLoss`` read.  The
+samples of an epoch are the ungrouped loader's, in another order.  ``batch_size`` must be a multiple of ``1 + k``; the
+batch ranges are those of ``num_positives`` groups in batches of ``batch_size // (1 + k)``, scaled by ``1 + k``, so
+neither a tail piece nor the ``world > 1`` split cuts a group.
 """
 from __future__ import annotations
 
@@ -154,7 +162,7 @@ class DeviceLoader:
     ``rating``.  ``len(loader)`` batches; the full-size ones are views of ``static_batch()``."""
 
     def __init__(self, family, columns, ids, feature, history, batch_size, seed, shuffle, drop_last, rank, world,
-                 negatives=0, observed=None):
+                 negatives=0, observed=None, grouped=False):
         if int(batch_size) < 1:
             raise ValueError("DeviceLoader: batch_size must be positive")
         if int(world) < 1 or not 0 <= int(rank) < int(world):
@@ -164,6 +172,10 @@ class DeviceLoader:
         self.negatives = int(negatives)
         if self.negatives < 0 or (self.negatives > 0) != (observed is not None):
             raise ValueError("DeviceLoader: negatives > 0 and observed=ObservedPairs(...) go together")
+        self.grouped = bool(grouped)
+        if self.grouped and (self.negatives < 1 or int(batch_size) % (1 + self.negatives)):
+            raise ValueError("DeviceLoader: grouped=True needs negatives >= 1 and a batch_size that is a multiple of "
+                             "1 + negatives")
         samples = [t for _, t in columns] + list(ids)
         tables = [feature.user_features, feature.item_features] if feature is not None else []
         _lib.require_device(*samples, *tables, history)
@@ -187,7 +199,12 @@ class DeviceLoader:
         self._neg = self._fail = None
         if self.negatives:
             self._describe_negatives(observed, ids[0])
-        self._ranges = batch_ranges(n, self.batch_size, self.drop_last, self.rank, self.world)
+        if self.grouped:    # the ranges of the groups, scaled: no batch, tail piece or rank boundary cuts a group
+            per = 1 + self.negatives
+            groups = batch_ranges(self.num_positives, self.batch_size // per, self.drop_last, self.rank, self.world)
+            self._ranges = [(first * per, count * per) for first, count in groups]
+        else:
+            self._ranges = batch_ranges(n, self.batch_size, self.drop_last, self.rank, self.world)
         # a tail piece that happens to hold batch_size samples is still the tail: it has its own buffers
         self._num_full = (n // self.batch_size) // self.world
         tail = self._ranges[-1][1] if len(self._ranges) > self._num_full else 0
@@ -214,30 +231,31 @@ class DeviceLoader:
     # -- constructors ------------------------------------------------------------------------------------------
     @classmethod
     def pairs(cls, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0, world=1,
-              negatives=0, observed=None):
+              negatives=0, observed=None, grouped=False):
         """MF / NeuralCF: batches ``(user_idx (B,), item_idx (B,)), rating`` -- rating (N,) or (N, 1) float32.
         ``negatives=k, observed=ObservedPairs(...)`` (every constructor): the samples are positives, and each epoch adds
-        k drawn negatives per positive, rating 0"""
+        k drawn negatives per positive, rating 0; ``grouped=True`` (every constructor) keeps each positive's negatives
+        behind it (module docstring)"""
         cols = [("users", users), ("items", items), ("ratings", ratings)]
         return cls("pairs", cols, [users, items], None, None, batch_size, seed, shuffle, drop_last, rank, world,
-                   negatives, observed)
+                   negatives, observed, grouped)
 
     @classmethod
     def features(cls, assembler, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
-                 world=1, negatives=0, observed=None):
+                 world=1, negatives=0, observed=None, grouped=False):
         """feature models: batches ``(x (B, assembler.width),), rating`` -- x as ``assembler.feature`` builds it (for a
         negative: from the drawn item's row)"""
         return cls("features", [("ratings", ratings)], [users, items], assembler, None, batch_size, seed, shuffle,
-                   drop_last, rank, world, negatives, observed)
+                   drop_last, rank, world, negatives, observed, grouped)
 
     @classmethod
     def sequences(cls, history, users, targets, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
-                  world=1, negatives=0, observed=None):
+                  world=1, negatives=0, observed=None, grouped=False):
         """DIN / DIEN: batches ``(hist (B, L), target (B,)), rating`` -- hist row = ``history[users[sample]]``,
         ``history`` one (U, L) int64 row per USER (a negative replaces the target and keeps the row)"""
         cols = [("targets", targets), ("ratings", ratings)]
         return cls("sequences", cols, [users, targets], None, history, batch_size, seed, shuffle, drop_last, rank, world,
-                   negatives, observed)
+                   negatives, observed, grouped)
 
     # -- batches -----------------------------------------------------------------------------------------------
     def __len__(self):
@@ -259,9 +277,10 @@ class DeviceLoader:
 
     def _launch(self, buffers, epoch, first, count, shuffle):
         if self._neg is not None:
-            rc = _lib.load().ctr_load_batch_neg(C.addressof(buffers.desc), C.addressof(self._neg), self.seed, epoch, first,
-                                                count, int(shuffle), _lib.stream_ptr())
-            _lib.check(rc, "ctr_load_batch_neg")
+            name = "ctr_load_batch_groups" if self.grouped else "ctr_load_batch_neg"
+            rc = getattr(_lib.load(), name)(C.addressof(buffers.desc), C.addressof(self._neg), self.seed, epoch, first,
+                                            count, int(shuffle), _lib.stream_ptr())
+            _lib.check(rc, name)
             return
         rc = _lib.load().ctr_load_batch(C.addressof(buffers.desc), self.seed, epoch, first, count, int(shuffle),
                                         _lib.stream_ptr())
@@ -280,16 +299,34 @@ class DeviceLoader:
 
     def indices(self, epoch: int, first: int = 0, count=None, shuffle=None) -> torch.Tensor:
         """sample indices of positions [first, first + count) of epoch ``epoch`` (int64, on the device); with negatives
-        the index v over the virtual epoch: positive ``v // (1 + k)``, slot ``v % (1 + k)``"""
+        the index v over the virtual epoch: positive ``v // (1 + k)``, slot ``v % (1 + k)`` (grouped: the slot is the
+        position's, the positive its group's)"""
         count = self.num_samples - first if count is None else count
         if epoch < 0 or first < 0 or count < 0 or first + count > self.num_samples:
             raise ValueError("DeviceLoader.indices(): position range outside the epoch")
         shuffle = self.shuffle if shuffle is None else bool(shuffle)
+        if self.grouped:
+            return self._group_indices(int(epoch), int(first), int(count), shuffle)
         out = torch.empty(count, dtype=torch.int64, device=self.device)
         rc = _lib.load().ctr_loader_indices(self.num_samples, self.seed, int(epoch), int(first), int(count), int(shuffle),
                                             out.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, "ctr_loader_indices")
         return out
+
+    def _group_indices(self, epoch, first, count, shuffle):
+        """v = perm_N(group) * (1 + k) + slot of positions [first, first + count): the permutation of the groups that
+        the range touches by ``ctr_loader_indices`` over N, the rest by torch ops"""
+        per = 1 + self.negatives
+        pos = torch.arange(first, first + count, dtype=torch.int64, device=self.device)
+        if count == 0:
+            return pos
+        g0, g1 = first // per, (first + count - 1) // per + 1
+        order = torch.empty(g1 - g0, dtype=torch.int64, device=self.device)
+        rc = _lib.load().ctr_loader_indices(self.num_positives, self.seed, epoch, g0, g1 - g0, int(shuffle),
+                                            order.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "ctr_loader_indices")
+        group = torch.div(pos, per, rounding_mode="floor")
+        return order[group - g0] * per + (pos - group * per)
 
     def check_bad_index(self):
         """raise the IndexError of an id outside its join table seen by any batch since the last call, or the

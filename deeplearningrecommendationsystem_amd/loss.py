@@ -1,7 +1,14 @@
 """``BCELoss`` -- drop-in for the ``torch.nn.BCELoss()`` every reference script builds
 (e.g. scripts/pnn.py:54): mean reduction, log terms clamped at -100.  Forward is ONE launch: a pass
 over the samples whose last workgroup sums the <= 256 partials in a fixed order (torch: elementwise
-kernel + a single-workgroup mean), backward one pass."""
+kernel + a single-workgroup mean), backward one pass.
+
+``BPRLoss(negatives)`` / ``SampledSoftmaxLoss(negatives)`` -- ranking losses over groups of ``1 + negatives``
+contiguous samples, the positive first: the batches of a ``data.DeviceLoader(..., grouped=True)``.  They take the
+model's probabilities like ``BCELoss`` (every model of the package ends in a sigmoid) and go back to the logit; the
+definitions stand in the header comment of csrc/group_loss.hip.  Same launch structure as ``BCELoss``: one forward
+launch that also writes the gradient for an upstream of exactly 1, one backward pass otherwise.  The reference has
+no loss over a group."""
 from __future__ import annotations
 
 import torch
@@ -80,3 +87,66 @@ class BCELoss(torch.nn.Module):
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return _BCEFunction.apply(input, target)
+
+
+class _GroupLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prob, negatives, kind):
+        _lib.require_device(prob)
+        p = prob.reshape(-1)
+        if p.dtype != torch.float32 or p.numel() == 0 or p.numel() % (1 + negatives):
+            raise ValueError(f"the group loss expects float32 input of whole groups of 1 + {negatives} samples")
+        groups = p.numel() // (1 + negatives)
+        loss = torch.empty((), dtype=torch.float32, device=prob.device)
+        ws = torch.empty(256, dtype=torch.float32, device=prob.device)
+        # d loss / d prob for an upstream gradient of exactly 1, written by the same launch
+        gp1 = torch.empty(p.numel(), dtype=torch.float32, device=prob.device) if ctx.needs_input_grad[0] else None
+        rc = _lib.load().ctr_group_loss_fwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1, groups, negatives, kind,
+                                            loss.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            _ticket(prob.device).data_ptr(), _lib.ptr(gp1), _lib.stream_ptr())
+        _lib.check(rc, "ctr_group_loss_fwd")
+        ctx.save_for_backward(p)
+        ctx.shape, ctx.negatives, ctx.kind, ctx.gp1 = prob.shape, negatives, kind, gp1
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        p, = ctx.saved_tensors
+        unit = _units.get(p.device.index)
+        if ctx.gp1 is not None and unit is not None and gloss.data_ptr() == unit.data_ptr():
+            return ctx.gp1.view(ctx.shape), None, None  # upstream gradient is THE 1.0: forward wrote this already
+        gp = torch.empty(p.numel(), dtype=torch.float32, device=p.device)
+        g = gloss.contiguous()
+        rc = _lib.load().ctr_group_loss_bwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1,
+                                            p.numel() // (1 + ctx.negatives), ctx.negatives, ctx.kind, g.data_ptr(),
+                                            gp.data_ptr(), 1, _lib.stream_ptr())
+        _lib.check(rc, "ctr_group_loss_bwd")
+        return gp.view(ctx.shape), None, None
+
+
+class _GroupLoss(torch.nn.Module):
+    """``loss_fn(input, target)`` over groups of ``group_size`` contiguous samples, slot 0 the positive; ``target`` is
+    accepted, so that ``Trainer`` and ``GraphedStep`` drive the loss like ``BCELoss``, and not read: the position
+    inside the group says which sample is the positive"""
+    kind = None
+
+    def __init__(self, negatives: int):
+        super().__init__()
+        self.negatives = int(negatives)
+        if not 1 <= self.negatives <= _lib.CTR_GROUP_MAX_K:
+            raise ValueError(f"negatives must be in [1, {_lib.CTR_GROUP_MAX_K}]")
+        self.group_size = 1 + self.negatives
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor = None) -> torch.Tensor:
+        return _GroupLossFunction.apply(input, self.negatives, self.kind)
+
+
+class BPRLoss(_GroupLoss):
+    """Bayesian personalised ranking: mean over the (positive, negative) pairs of ``softplus(z_neg - z_pos)``, i.e.
+    ``-logsigmoid(z_pos - z_neg)``, z the logit of the model's probability"""
+    kind = 0
+
+
+class SampledSoftmaxLoss(_GroupLoss):
+    """sampled softmax: mean over the groups of the cross entropy of the group's logits against slot 0"""
+    kind = 1

@@ -105,11 +105,27 @@ class Trainer:
                 p.grad = g
         return pred, loss
 
+    def _check_groups(self, loader):
+        size = getattr(self.loss_fn, "group_size", None)
+        if size is None:
+            return
+        if not (getattr(loader, "grouped", False) or not loader.shuffle):
+            raise ValueError("train_epoch: a group loss needs a loader built with grouped=True (or shuffle=False): a "
+                             "shuffled epoch scatters a positive and its negatives over the batches")
+        if getattr(loader, "negatives", 0) + 1 != size:
+            raise ValueError(f"train_epoch: the loss reads groups of {size}, the loader draws "
+                             f"{getattr(loader, 'negatives', 0)} negatives per positive")
+        if loader.batch_size % size:
+            raise ValueError(f"train_epoch: batch_size {loader.batch_size} is not a multiple of the group size {size}")
+
     def train_epoch(self, loader, epoch):
         """one optimizer step per batch of ``loader.epoch(epoch)``.  With ``graph=True`` the full-size batches replay
         ONE graph captured over the loader's static buffers (the loader launch runs eagerly in front of each replay);
         the tail batch has buffers of its own and runs eagerly, so it never replaces the captured graph.
-        ``train_loss``: sample-weighted mean of the batch losses; predictions / rating: those of the last batch."""
+        ``train_loss``: sample-weighted mean of the batch losses; predictions / rating: those of the last batch.
+        A loss over groups (one that has ``group_size``: ``loss.BPRLoss``, ``loss.SampledSoftmaxLoss``) needs a loader
+        that delivers whole groups of that size."""
+        self._check_groups(loader)
         self.model.train()
         static = loader.static_batch()
         total = torch.zeros((), dtype=torch.float64, device=loader.device)

@@ -708,6 +708,16 @@ int ctr_assemble_features(const int64_t* users, const int64_t* items, int64_t n,
  * (and in the feature join) and 0.0f in cols[rating_col].  The position range is checked against n * (1 + negatives);
  * negatives < 1, a column index out of range or of the wrong width or element size, num_items < 1 or >= 2^31, or
  * n * (1 + negatives) > 2^62 is CTR_EINVAL.  *fail_flag is raised when 2^14 draws of one slot were all observed.
+ * ctr_load_batch_groups is ctr_load_batch_neg with a grouped shuffle: same descriptors, arguments and refusals, and
+ * with k = negatives position p of epoch e holds
+ *     g = p / (1 + k);  j = p % (1 + k)
+ *     s = perm_n(seed, e, g)          (the keyed permutation over n, not over n * (1 + k);  s = g when shuffle == 0)
+ *     v = s * (1 + k) + j
+ *     outputs = exactly what ctr_load_batch_neg defines for virtual index v
+ *               (j == 0: positive s;  j >= 1: the draw keyed by (seed, e, v))
+ * so a batch whose first and count are multiples of 1 + k is a run of whole groups, positive first: what the group
+ * losses below (ctr_group_loss_fwd) read.  Unshuffled it equals ctr_load_batch_neg bit for bit; shuffled, an epoch
+ * emits the same multiset of samples as ctr_load_batch_neg for the same (seed, e).
  * ---------------------------------------------------------------------- */
 typedef struct ctr_loader_col {
   const void* src;      /* (n, width) elements, leading dimension lds */
@@ -763,6 +773,8 @@ typedef struct ctr_loader_neg {
 
 int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
                        int64_t first, int64_t count, int shuffle, void* stream);
+int ctr_load_batch_groups(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
+                          int64_t first, int64_t count, int shuffle, void* stream);
 
 /* ------------------------------------------------------------------------
  * Sampled leave-one-out evaluation (csrc/group_eval.hip): every held-out positive is ranked against k sampled
@@ -828,6 +840,28 @@ int ctr_bce_fwd(const float* prob, int64_t ldp, const float* target, int64_t ldt
 /* gprob[i*ldg] = (p_i - t_i) / max(p_i (1-p_i), 1e-12) * gloss[0] / n */
 int ctr_bce_bwd(const float* prob, int64_t ldp, const float* target, int64_t ldt, int64_t n,
                 const float* gloss, float* gprob, int64_t ldg, void* stream);
+
+/* Ranking losses over groups of 1 positive + k negatives (csrc/group_loss.hip): what a model scored by ctr_group_rank
+ * trains on, over the batches of ctr_load_batch_groups.  The models return probabilities, so the losses take
+ * probabilities like ctr_bce_fwd.  n groups of 1 + k samples, sample j of group g at prob[(g (1 + k) + j) * ldp],
+ * slot 0 the positive:
+ *   z_i  = max(log p_i, -100) - max(log(1 - p_i), -100)         (1 - p formed in fp32; a NaN stays a NaN)
+ *   kind 0, BPR:      L = 1/(n k) * sum_g sum_{j=1..k} softplus(z_gj - z_g0),  softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *   kind 1, softmax:  L = 1/n * sum_g [ m_g + log sum_{j=0..k} exp(z_gj - m_g) - z_g0 ],   m_g = max_j z_gj
+ *   dL/dz:    BPR      dz_gj = sigmoid(z_gj - z_g0) / (n k)  (j >= 1),   dz_g0 = -sum_j dz_gj
+ *             softmax  dz_gj = (softmax_j - [j == 0]) / n
+ *   dL/dp_i = dz_i / max(p_i (1 - p_i), 1e-12) * gloss[0]       (ctr_bce_bwd's floor; composes with the model's
+ *                                                                sigmoid backward to exactly dz)
+ * ctr_group_loss_fwd writes loss[0] in ONE launch; workspace (>= 256 floats), ticket and gprob_unit (nullable,
+ * n (1 + k) contiguous floats: what ctr_group_loss_bwd writes for gloss[0] == 1, bit-identical) are ctr_bce_fwd's, and
+ * the ticket word may be the same one.  The loss is bitwise reproducible from run to run.
+ * ctr_group_loss_bwd writes gprob[i * ldg] for every sample i.
+ * kind outside {0, 1}, k outside [1, CTR_GROUP_MAX_K], n < 1 (a mean over nothing), n > 2^40, a null pointer or a
+ * stride below 1 is CTR_EINVAL; fewer workspace floats than workgroups is CTR_ELIMIT. */
+int ctr_group_loss_fwd(const float* prob, int64_t ldp, int64_t n, int k, int kind, float* loss, float* workspace,
+                       int64_t workspace_floats, unsigned int* ticket, float* gprob_unit, void* stream);
+int ctr_group_loss_bwd(const float* prob, int64_t ldp, int64_t n, int k, int kind, const float* gloss, float* gprob,
+                       int64_t ldg, void* stream);
 
 /* history-position part of the DIN / DIEN table gradient for the E-wide operand (CTR_DIN_H):
  *   gtable[hist[b,l], :] += gh[(b*len+l)*ldgh + 0:E] + attn[b*len+l] * gpool[(summed ? b : b*len+l)*ldgp + 0:E]
