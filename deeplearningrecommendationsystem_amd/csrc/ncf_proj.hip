@@ -18,18 +18,20 @@
 // The segment sums are formed without a sort and without a global returning atomic.  The training forward builds a
 // bucket PLAN, once: the batch is cut into at most kChunks contiguous chunks, a workgroup per chunk (beside the
 // projection workgroups of ncfp_prep) counts the chunk's samples per table row in an LDS histogram -- the returning LDS
-// atomic is the sample's rank inside (row, chunk) -- and stores the histogram, zeros included; a few workgroups behind
-// the per-sample ones of ncfp_fwd turn every row's counts into exclusive prefixes over the chunks (base[chunk][row]) and
-// row totals, and the one that draws the last ticket scans the totals into rows + 1 bucket offsets.  The backward kernel
-// loads the offsets into LDS and stores each sample's gz0 row ONCE, at the sample's own row of a (batch + 1, 64) buffer,
-// plus a 16-byte record {gz, partner id, row, sample} into the sample's slot of its user's bucket and of its item's,
-// slot = offset[row] + base[chunk][row] + rank: a bucket is a run of records, and a record names the gz0 row and the
+// atomic is the sample's rank inside (row, chunk) -- and stores the histogram, zeros included, and its sums over every
+// block of 256 rows; a few workgroups behind the per-sample ones of ncfp_fwd, one per block, turn every row's counts
+// into exclusive prefixes over the chunks and a row total, scan their own totals and add the blocks in front of them
+// from those block sums: rows + 1 bucket offsets, each workgroup its own rows', with no ticket, fence or wait inside the
+// launch.  The prefixes are stored with the offset folded in (base[chunk][row] = offset[row] + the row's samples in
+// earlier chunks).  The backward kernel stores each sample's gz0 row ONCE, at the sample's own row of a (batch + 1, 64)
+// buffer, plus a 16-byte record {gz, partner id, row, sample} into the sample's slot of its user's bucket and of its
+// item's, slot = base[chunk][row] + rank: a bucket is a run of records, and a record names the gz0 row and the
 // partner GMF row of its sample.  A streaming kernel then sums the buckets, fetching both rows through the record
 // (balanced over SLOT ranges, so a hot row of a skewed id distribution is shared by many waves).  Same values as the
 // per-sample path up to fp32 summation order; inside a bucket the chunks follow each other in batch order, the order
 // inside (row, chunk) follows the LDS atomics, so table gradients are reproducible to rounding, not bitwise.
 //
-// Launches: forward  ncfp_prep (projected tables, head fold, chunk histograms) -> ncfp_fwd (+ prefixes, offsets);
+// Launches: forward  ncfp_prep (projected tables, head fold, chunk histograms + block sums) -> ncfp_fwd (+ bases, offsets);
 // backward  ncfp_bwd -> ncfp_segsum (+ tower dW partials, head fold chain rule) -> ncfp_finish (the table-row products).
 #include "ctr_common.h"
 
@@ -66,39 +68,55 @@ struct Ids {
 
 // ------------------------------------------------------------------ the bucket plan of a training forward
 // The caller's plan buffer (rows * CTR_NCF_PROJ_COUNT_STRIDE int32, rows = nu + ni):
-//   [0]                ticket of the prefix workgroups: zero at entry, re-armed by the one that draws the last
-//   base   [chunk][row]  after ncfp_prep: samples of `row` in `chunk`; after ncfp_fwd: the samples of `row` in EARLIER chunks
+//   [0 .. 3]           head: never touched by the device (word 0 is the word the caller keeps zero; base stays 16-byte aligned)
+//   base   [chunk][row]  after ncfp_prep: samples of `row` in `chunk`; after ncfp_fwd: the slot of the row's first sample
+//                        of that chunk = offsets[row] + the samples of `row` in EARLIER chunks
 //   totals [row]         samples of the row in the batch
 //   offsets[rows + 1]    exclusive scan of the totals (user rows first): where a row's bucket begins; [rows] = all slots
+//   blk    [chunk][block]  (more than kPlanBlock rows only) after ncfp_prep: samples of `chunk` in the rows of `block`
 // A chunk is 2^shift consecutive samples (at least one sample per thread of its workgroup, at most kChunks chunks), so
-// the chunk of a sample is a shift of its index.  Every entry a later launch reads is written by an earlier one, zeros
-// included: nothing but the ticket has to be clear, and nothing is cleared afterwards.
+// the chunk of a sample is a shift of its index.  A block is kPlanBlock consecutive rows: the rows of one plan workgroup.
+// Every entry a later launch reads is written by an earlier one, zeros included: nothing has to be clear, and nothing
+// is cleared afterwards.
 constexpr int kChunks = 64;
-constexpr int kPlanHead = 4;                   // int32 in front of base (the ticket; keeps base 16-byte aligned)
+constexpr int kPlanHead = 4;                   // int32 in front of base
+constexpr int kPlanBlock = 256;                // rows of a block = threads of a plan workgroup
 static_assert(kPlanHead + 2 * (kChunks + 2) + 1 <= 2 * CTR_NCF_PROJ_COUNT_STRIDE,
               "CTR_NCF_PROJ_COUNT_STRIDE: the plan of the smallest tables (two rows) does not fit");
+// blk exists from kPlanBlock + 1 rows on (two blocks); every kPlanBlock rows more add kChunks entries to it and
+// (CTR_NCF_PROJ_COUNT_STRIDE - kChunks - 2) * kPlanBlock to the room behind the offsets
+static_assert(kPlanHead + (kChunks + 2) * (kPlanBlock + 1) + 1 + kChunks * 2 <= (kPlanBlock + 1) * CTR_NCF_PROJ_COUNT_STRIDE &&
+                  kChunks <= (CTR_NCF_PROJ_COUNT_STRIDE - kChunks - 2) * kPlanBlock,
+              "CTR_NCF_PROJ_COUNT_STRIDE: the block totals do not fit behind the offsets");
 struct Plan {
-  unsigned int* ticket;
-  int32_t* base; int32_t* totals; int32_t* offsets;
+  int32_t* base; int32_t* totals; int32_t* offsets; int32_t* blk;
   int64_t rows;
-  int shift, chunks;
+  int shift, chunks, nblk;
 };
 Plan plan_of(int32_t* buf, int64_t rows, int64_t m) {
   int shift = 8;
   while (((int64_t)kChunks << shift) < m) ++shift;
   Plan p;
-  p.ticket = reinterpret_cast<unsigned int*>(buf);
   p.base = buf + kPlanHead;
   p.totals = p.base + kChunks * rows;
   p.offsets = p.totals + rows;
+  p.blk = p.offsets + rows + 1;
   p.rows = rows;
   p.shift = shift;
   p.chunks = (int)((m + ((int64_t)1 << shift) - 1) >> shift);
+  p.nblk = (int)((rows + kPlanBlock - 1) / kPlanBlock);
   return p;
 }
 
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // Ranks of one chunk, by workgroup `first` + chunk of a launch that has other work in its first workgroups: an LDS
-// histogram over the rows, a returning LDS atomic per sample and id column, an 8-byte record out, then the histogram.
+// histogram over the rows, a returning LDS atomic per sample and id column, an 8-byte record out, then the histogram
+// and its sums over the blocks of kPlanBlock rows.
 // All ids of a pass are requested before the first atomic (id -> atomic -> store, one sample after the other, is a chain
 // of round trips).  Ids sorted by user put a whole wave on one LDS counter: 64 serialised LDS operations, not 64
 // memory-side ones.
@@ -139,87 +157,85 @@ __device__ __forceinline__ void rank_role(const RankJob& R) {
   __syncthreads();
   int32_t* out = R.plan.base + (int64_t)chunk * rows;
   for (int i = threadIdx.x; i < rows; i += kThreads) out[i] = s_hist[i];
+  // block totals (more than one plan workgroup only): a wave per block, four LDS reads a lane and one wave sum -- the
+  // histogram is complete and only read from here on, so this needs no barrier and waits for none of the stores above
+  const int nblk = R.plan.nblk;
+  if (nblk > 1) {
+    const int lane = threadIdx.x & 63;
+    for (int k = threadIdx.x >> 6; k < nblk; k += kWaves) {
+      int v = 0;
+#pragma unroll
+      for (int e = 0; e < kPlanBlock / 64; ++e) {
+        const int i = k * kPlanBlock + e * 64 + lane;
+        v += i < rows ? s_hist[i] : 0;
+      }
+      v = wave_sum_int(v);
+      if (lane == 0) R.plan.blk[chunk * nblk + k] = v;
+    }
+  }
 }
 
-// Prefixes and offsets, by workgroups `first` .. of the launch behind ncfp_prep: a thread per row turns the row's chunk
-// counts into exclusive prefixes, in place, and stores the row's total; the workgroup that draws the last ticket
-// (bce_fwd_kernel's pattern: nobody waits for anybody) scans the totals into the offsets, in `lds` (rows + 1 int32).
+// Prefixes and offsets, by workgroups `first` .. of the launch behind ncfp_prep, workgroup k for the rows of block k: a
+// thread per row sums the row's chunk counts into exclusive prefixes and a total; the workgroup scans its totals (a
+// wave scan and one combine over the waves) and adds the samples of all blocks in front of it, which ncfp_prep left as
+// block totals per chunk -- so every workgroup finishes its own rows' offsets alone: nothing in this launch is ordered
+// against anything else in it.  Stored: the totals, the offsets, and base[chunk][row] = offset + prefix, in place.
 struct PlanJob {
   Plan plan;
   int first;
 };
-__device__ __forceinline__ void plan_role(const PlanJob& J, int* lds) {
-  __shared__ int s_scan[kWaves];
-  __shared__ bool s_last;
+constexpr int kBlkPer = 16;                    // block totals a thread sums: blocks kWaves e + wave of chunk `lane`
+static_assert(kChunks == 64 && kPlanBlock == kThreads && CTR_NCF_PROJ_MAX_ROWS <= kPlanBlock * kWaves * kBlkPer,
+              "plan_role: a lane per chunk, a thread per row of the block, kWaves * kBlkPer blocks at most");
+__device__ __forceinline__ void plan_role(const PlanJob& J) {
+  __shared__ int s_scan[kWaves], s_front[kWaves];
   const Plan& P = J.plan;
   const int64_t rows = P.rows;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  {
-    const int64_t row = ((int64_t)blockIdx.x - J.first) * kThreads + threadIdx.x;
-    const int64_t rr = row < rows ? row : rows - 1;
-    int v[kChunks];
+  const int k = (int)blockIdx.x - J.first;     // this workgroup's block
+  const int64_t row = (int64_t)k * kPlanBlock + threadIdx.x;
+  const int64_t rr = row < rows ? row : rows - 1;
+  // every load of the thread is requested before any is used: the block totals in front of block k (k <= 63 blocks x
+  // 64 chunks over 256 threads; the branch is uniform), then the row's chunk counts
+  int front = 0, f[kBlkPer];
 #pragma unroll
-    for (int c = 0; c < kChunks; ++c) v[c] = P.base[(int64_t)(c < P.chunks ? c : P.chunks - 1) * rows + rr];
-    int run = 0;
+  for (int e = 0; e < kBlkPer; ++e) {
+    f[e] = 0;
+    if (kWaves * e < k) f[e] = P.blk[(lane < P.chunks ? lane : P.chunks - 1) * P.nblk + (kWaves * e + wave < k ? kWaves * e + wave : 0)];
+  }
+  int v[kChunks];
+#pragma unroll
+  for (int c = 0; c < kChunks; ++c) v[c] = P.base[(int64_t)(c < P.chunks ? c : P.chunks - 1) * rows + rr];
+#pragma unroll
+  for (int e = 0; e < kBlkPer; ++e) front += (lane < P.chunks && kWaves * e + wave < k) ? f[e] : 0;
+  int total = 0;
+#pragma unroll
+  for (int c = 0; c < kChunks; ++c) total += c < P.chunks ? v[c] : 0;
+  total = row < rows ? total : 0;
+  int inc = total;   // inclusive scan of the totals over the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += t;
+  }
+  front = wave_sum_int(front);
+  if (lane == 63) s_scan[wave] = inc;
+  if (lane == 0) s_front[wave] = front;
+  __syncthreads();
+  int offset = (s_front[0] + s_front[1]) + (s_front[2] + s_front[3]) + inc - total;
+  for (int w = 0; w < wave; ++w) offset += s_scan[w];
+  if (row < rows) {
+    P.totals[row] = total;
+    P.offsets[row] = offset;
+    if (row == rows - 1) P.offsets[rows] = offset + total;
+    int run = offset;
 #pragma unroll
     for (int c = 0; c < kChunks; ++c)
-      if (c < P.chunks && row < rows) {
+      if (c < P.chunks) {
         P.base[(int64_t)c * rows + row] = run;
         run += v[c];
       }
-    if (row < rows) __hip_atomic_store(P.totals + row, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    // release this workgroup's totals, acquire everybody else's if it is the last
-    const unsigned int drawn = __hip_atomic_fetch_add(P.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = drawn == gridDim.x - (unsigned int)J.first - 1u;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  // the totals into LDS, kCnt coalesced loads in flight per thread (rows past the end re-read the last)
-  constexpr int kCnt = 12;
-  for (int64_t base = 0; base < rows; base += kCnt * kThreads) {
-    int v[kCnt];
-#pragma unroll
-    for (int e = 0; e < kCnt; ++e) {
-      const int64_t i = base + e * kThreads + threadIdx.x;
-      v[e] = __hip_atomic_load(P.totals + (i < rows ? i : rows - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#pragma unroll
-    for (int e = 0; e < kCnt; ++e) {
-      const int64_t i = base + e * kThreads + threadIdx.x;
-      if (i < rows) lds[i] = v[e];
-    }
-  }
-  __syncthreads();
-  // exclusive scan (users, then items), in place
-  const int per = (int)((rows + kThreads - 1) / kThreads);
-  const int64_t i0 = (int64_t)threadIdx.x * per;
-  int sum = 0;
-  for (int e = 0; e < per; ++e)
-    if (i0 + e < rows) sum += lds[i0 + e];
-  int inc = sum;   // inclusive scan of `sum` over the workgroup's threads
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int v = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += v;
-  }
-  if (lane == 63) s_scan[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  for (int w = 0; w < wave; ++w) before += s_scan[w];
-  int run = before + inc - sum;
-  for (int e = 0; e < per; ++e)
-    if (i0 + e < rows) {
-      const int c = lds[i0 + e];
-      lds[i0 + e] = run;
-      run += c;
-    }
-  if (threadIdx.x == kThreads - 1) lds[rows] = before + inc;
-  __syncthreads();
-  for (int64_t i = threadIdx.x; i <= rows; i += kThreads) P.offsets[i] = lds[i];
-  if (threadIdx.x == 0) __hip_atomic_store(P.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ------------------------------------------------------------------ prep: projected tables + head fold
@@ -348,7 +364,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2
 ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if ((int)blockIdx.x >= F.plan.first) {
-    plan_role(F.plan, reinterpret_cast<int*>(lds));
+    plan_role(F.plan);
     return;
   }
   float* s_w = lds;                                   // kWFloats
@@ -495,16 +511,10 @@ constexpr int kStripP = 3 * kTile;                        // per wave: tiles A0 
 // coalesced by LDS-DMA, 16-byte chunks XOR-swizzled with the row so that both read patterns (sample-major ds_read_b128,
 // unit-major ds_read_b32) spread over the banks
 constexpr int kSgPU = 0, kSgPI = 1024, kSgY1 = 2048, kSgY2 = 2560, kSgY3 = 2816, kBwdStage = 3072;
-// dynamic LDS of ncfp_bwd_kernel (floats): tower weights, per-wave tiles and staging, then the rows + 1 bucket offsets;
-// the wave sums parked at the end (kCopy per wave) reuse the same space
-constexpr int kBwdLdsMax = 150 * 1024 / 4;
-constexpr int64_t bwd_lds_floats(int64_t rows) {
-  const int64_t main_f = kWFloats + kWaves * (kStripP + kBwdStage) + (rows + 1 + 3) / 4 * 4, copy_f = (int64_t)kWaves * kCopy;
-  return main_f > copy_f ? main_f : copy_f;
-}
-// every table size pattern_ok() (and so the forward) admits, the backward must be able to run: 16384 rows take
-// 18944 + 16388 floats (138 of the 150 KB); the offsets would fit up to 19455 rows
-static_assert(bwd_lds_floats(CTR_NCF_PROJ_MAX_ROWS) <= kBwdLdsMax, "CTR_NCF_PROJ_MAX_ROWS: the backward's offsets do not fit in LDS");
+// dynamic LDS of ncfp_bwd_kernel (floats): tower weights, per-wave tiles and staging; the wave sums parked at the end
+// (kCopy per wave) reuse the same space
+constexpr int kBwdLdsFloats = kWFloats + kWaves * (kStripP + kBwdStage) > kWaves * kCopy ? kWFloats + kWaves * (kStripP + kBwdStage)
+                                                                                         : kWaves * kCopy;
 constexpr int kBwdDma = 12;                               // row fetches per group
 constexpr int kBwdStores = 6;                             // 4 pieces of the gz0 row + 2 slot records
 
@@ -515,8 +525,7 @@ struct Bwd {
   const float* prob; int64_t ldp;
   const float* gprob; int64_t ldgp;
   int act;
-  const int32_t* base;                         // the forward's plan: [chunk][row] samples of the row in earlier chunks,
-  const int32_t* offsets;                      // (nu + ni + 1) bucket offsets,
+  const int32_t* base;                         // the forward's plan: [chunk][row] slot of the row's first sample of the chunk,
   int shift;                                   // chunk of sample s = s >> shift
   const int32_t* ranks;                        // (m + 1, 2): rank of a sample inside (row, chunk)
   float* gz;                                   // (m + 1, 64): gz0 rows in sample order, one spare row
@@ -543,7 +552,6 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   float* stage = lds + kWFloats + kWaves * kStripP + wave * kBwdStage;
   const uint32_t stage_addr = ctr_lds_addr(stage);
   const int64_t nrows = B.ids.nu + B.ids.ni;
-  int* s_off = reinterpret_cast<int*>(lds + kWFloats + kWaves * (kStripP + kBwdStage));   // nrows + 1 exclusive offsets
   const int64_t groups = (m + 15) / 16;
   const int64_t wave0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * kThreads) >> 6;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -555,6 +563,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   STAMP(1, stamp++);
 
   // ---- clear what this call accumulates into (both 16-byte aligned multiples of 4 floats)
+  // (issued behind the group loop instead, in front of the last wait, they made the launch 0.9 us LONGER:
+  // profiles/r07_ncf_plan_blocks.txt section 3)
   {
     const int64_t t0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 4, step = (int64_t)gridDim.x * kThreads * 4;
     for (int64_t i = t0; i < B.zero_a_floats; i += step) stg4(B.zero_a + i, zero4);
@@ -573,7 +583,7 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   struct Scal {
     float gp, pb;
     int ru, ri;                       // ranks of this lane's sample in its user / item row, inside its chunk,
-    int bu, bi;                       // and the samples of those rows in earlier chunks
+    int bu, bi;                       // and the slots of those rows' first samples of the chunk
     uint32_t u, i;                    // its ids, clamped (bad ids: row 0, no slot)
     bool ubad, ibad;
   };
@@ -644,29 +654,13 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     int wdst[kStagePer];
     stage_transposed_load(T, wv, wdst);
     const float hw = threadIdx.x <= kHeadW ? B.wfold[threadIdx.x] : 0.0f;
-    // the bucket offsets into LDS, kCnt coalesced loads in flight per thread (entries past the end re-read the last):
-    // ml-100k's 2626 are ONE round trip (four in flight were three)
-    constexpr int kCnt = 12;
-    for (int64_t base = 0; base <= nrows; base += kCnt * kThreads) {
-      int v[kCnt];
-#pragma unroll
-      for (int e = 0; e < kCnt; ++e) {
-        const int64_t i = base + e * kThreads + threadIdx.x;
-        v[e] = B.offsets[i <= nrows ? i : nrows];
-      }
-#pragma unroll
-      for (int e = 0; e < kCnt; ++e) {
-        const int64_t i = base + e * kThreads + threadIdx.x;
-        if (i <= nrows) s_off[i] = v[e];
-      }
-    }
     issue_rows(wave0, sc);
     issue_ids(wave0 + nwaves);
     stage_transposed_store(s_wt, wv, wdst);
     if (threadIdx.x <= kHeadW) s_hw[threadIdx.x] = hw;
   }
   __syncthreads();
-  STAMP(1, stamp++);   // weights staged, offsets in LDS, first group requested
+  STAMP(1, stamp++);   // weights staged, first group requested
   // the first group's rows and scalars, the second group's ids (nothing else is in flight)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("" : "+v"(idu), "+v"(idi), "+v"(sc.gp), "+v"(sc.pb), "+v"(sc.ru), "+v"(sc.ri), "+v"(sc.bu), "+v"(sc.bi));
@@ -702,8 +696,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
       }
     }
     const int uu = (int)sc.u, ii = (int)sc.i;
-    const int su = (live && !sc.ubad && sc.ru >= 0) ? sc.ru + sc.bu + s_off[uu] : -1;
-    const int si = (live && !sc.ibad && sc.ri >= 0) ? sc.ri + sc.bi + s_off[nu + ii] : -1;
+    const int su = (live && !sc.ubad && sc.ru >= 0) ? sc.ru + sc.bu : -1;
+    const int si = (live && !sc.ibad && sc.ri >= 0) ? sc.ri + sc.bi : -1;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the stage is read: it may be overwritten
     STAMP(1, stamp++);   // operands read
     issue_rows(g + nwaves, sc);
@@ -1393,7 +1387,6 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   const Fwd F{ids, d->ptab, d->gmf_user, d->gmf_item, d->wfold, d->prob, d->ldprob, d->head_act, d->err_flag,
               PlanJob{plan, (int)grid}};
   constexpr size_t fwd_lds = sizeof(float) * (kWFloats + kBFloats + 80 + kWaves * kFwdStage);
-  static_assert(fwd_lds >= sizeof(int32_t) * (CTR_NCF_PROJ_MAX_ROWS + 1), "plan_role scans the offsets in the forward's LDS");
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)fwd_lds) != hipSuccess)
     return CTR_ELAUNCH;
@@ -1426,10 +1419,9 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   const Ids ids{d->user_idx, d->user_stride, d->item_idx, d->item_stride, nu, ni};
   const Plan plan = plan_of(d->plan, rows, m);
   const int32_t* offs = plan.offsets;
-  const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, g->gprob, g->ldgprob, d->head_act, plan.base, offs, plan.shift,
+  const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, g->gprob, g->ldgprob, d->head_act, plan.base, plan.shift,
               d->ranks, gzb, aux, slabs, stt, rows * 128, g->zero_buf, g->zero_buf ? g->zero_floats : 0};
-  const size_t lds_bytes = sizeof(float) * (size_t)bwd_lds_floats(rows);
-  CTR_REQUIRE(bwd_lds_floats(rows) <= kBwdLdsMax, CTR_ELIMIT);
+  constexpr size_t lds_bytes = sizeof(float) * (size_t)kBwdLdsFloats;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)lds_bytes) != hipSuccess)
     return CTR_ELAUNCH;

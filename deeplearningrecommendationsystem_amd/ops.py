@@ -652,9 +652,10 @@ def few_table_rows(rows: int, batch: int) -> bool:
 
 class NcfCounts:
     """the bucket plan of ``ctr_ncf_proj_fwd`` (one holder per model): per-row sample counts of the batch's chunks,
-    row totals and bucket offsets, built by every training forward and read by its backward.  The C entry points want
-    its ticket zero at a training forward and leave it zero, so in the usual forward -> backward rhythm the buffer is
-    filled once, here.  ``take`` hands it out when no forward owns it; while a forward's plan still waits for its
+    row totals, bucket offsets and block totals, built by every training forward and read by its backward.  The
+    kernels write every entry they read later and never touch the buffer's first word (it stays the zero written
+    here), so in the usual forward -> backward rhythm the buffer is filled once, here.  ``take`` hands it out when no
+    forward owns it; while a forward's plan still waits for its
     backward (two graphs alive at once) a later forward gets a freshly zeroed buffer of its own instead, and after a
     training forward that never got its backward the buffer is cleared before it is handed out again."""
 
@@ -728,7 +729,8 @@ class NcfProj:
 
     def bucket_offsets(self) -> torch.Tensor:
         """(rows + 1) int32 of the training forward's plan: row v's bucket is the slots [o[v], o[v + 1]), user rows first
-        (the plan's layout, csrc/ncf_proj.hip: 4 int32 of head, 64 chunks x rows prefixes, rows totals, the offsets)"""
+        (the plan's layout, csrc/ncf_proj.hip: 4 int32 of head, 64 chunks x rows bases, rows totals, the offsets, then
+        the block totals)"""
         rows = self.nu + self.ni
         return self.plan[4 + 65 * rows: 4 + 66 * rows + 1]
 
@@ -749,20 +751,23 @@ class NcfProj:
         while (64 << shift) < m:
             shift += 1
         chunks = -(-m // (1 << shift))
+        blocks = -(-rows // 256)             # the rows of one plan workgroup; block totals only for more than one
+        blk = chunks * blocks * 4 if blocks > 1 else 0
         return {
             # (rows, 64) tables read, (rows, 64) projected rows written; one 64 x 64 product per row
             # (+ in training, by the rank workgroups of the same launch: ids, an 8-byte rank record per sample, a
-            # histogram of the rows per chunk)
-            "ncfp_prep": lambda: (rows * 512 + ((m * (16 + 8) + chunks * rows * 4) if self.training else 0),
+            # histogram of the rows per chunk and its sums over the blocks)
+            "ncfp_prep": lambda: (rows * 512 + ((m * (16 + 8) + chunks * rows * 4 + blk) if self.training else 0),
                                   2 * rows * 64 * 64),
             # ids, four 256-byte rows (cache-resident tables), saved activations + prob written; tower + head
             # (+ in training, by the plan workgroups of the same launch: the histograms read and written back as
-            # prefixes, row totals, bucket offsets)
+            # absolute bases, row totals and bucket offsets written, and plan workgroup k reads the block totals of
+            # the k blocks in front of it)
             "ncfp_fwd": lambda: (m * (16 + 4 * 256 + 4 * (32 + 16 + 8) + 4) +
-                                 ((2 * chunks * rows * 4 + 3 * rows * 4) if self.training else 0),
+                                 ((2 * chunks * rows * 4 + 2 * rows * 4 + blk * (blocks - 1) // 2) if self.training else 0),
                                  2 * m * (tower + 72 + 64)),
-            # ids, prob, gprob, ranks, two chunk prefixes, two projected rows, saved activations read; gz0 row stored
-            # once + two records
+            # ids, prob, gprob, ranks, two absolute bases (slot = base + rank: no copy of the offsets), two projected
+            # rows, saved activations read; gz0 row stored once + two records
             "ncfp_bwd": lambda: (m * (16 + 16 + 8 + 2 * 256 + 4 * (32 + 16 + 8) + 256 + 32), 4 * m * tower + 2 * m * 8),
             # per slot: its record, the gz0 row and the partner row the record names read; (rows, 128) sums added
             "ncfp_segsum": lambda: (2 * m * (256 + 16 + 256) + rows * 512, 2 * 2 * m * 64 * 2),
@@ -822,7 +827,7 @@ class NcfProj:
                 rc = rc or _timed(label, self._meta(label), fn, C.byref(d), C.byref(g), _lib.stream_ptr())
         _lib.check(rc, "ctr_ncf_proj_bwd")
         if self._owns:
-            self._holder.state = "clean"     # (the plan has been read; the forward left its ticket zero)
+            self._holder.state = "clean"     # (the plan has been read; the next forward rewrites what it reads)
         self._owns = False
 
 

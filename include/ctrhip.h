@@ -466,16 +466,17 @@ int ctr_act_mask_bwd(float* g, int64_t ldg, const float* y, int64_t ldy, int64_t
  * with training != 0: ranks (a sample's rank among the samples of its chunk of the batch that carry its user id, and
  * the same for its item id) and plan ((num_users + num_items) * CTR_NCF_PROJ_COUNT_STRIDE int32: the bucket plan the
  * forward builds from the ids -- per table row the sample counts of up to 64 chunks of the batch as exclusive
- * prefixes, the row's total, the bucket offsets -- and the backward reads; csrc/ncf_proj.hip has the layout).  The
- * forward writes every entry of the plan that is read later; only its first word, a ticket of the forward's second
- * launch, must be ZERO when a training forward is enqueued, and that launch leaves it zero: a caller zero-fills the
- * buffer once.  The plan belongs to ONE forward until its backward has run: two forwards in flight need a buffer each.
+ * prefixes with the row's bucket offset added, the row's total, the bucket offsets, per chunk its samples in every
+ * block of 256 rows -- and the backward reads; csrc/ncf_proj.hip has the layout).  The forward writes every entry of
+ * the plan that is read later and never touches its first four words: nothing has to be cleared between steps (a
+ * caller that zero-fills the buffer once finds word 0 still zero).
+ * The plan belongs to ONE forward until its backward has run: two forwards in flight need a buffer each.
  * Parameters must not change between the forward and the backward (the backward re-reads tables and ptab).
  * The backward's workspace (ctr_ncf_proj_workspace_floats): gz0 rows in sample order (batch + 1, 64) | slot records
  * (2 batch + 1, 4) = {gz, partner id, row, sample}, the user rows' buckets first | segment sums (rows, 128) | the
  * per-sample kernel's slabs. */
 #define CTR_NCF_PROJ_MAX_ROWS 16384
-#define CTR_NCF_PROJ_COUNT_STRIDE 72   /* int32 of plan per table row: 64 chunk counts, total, offset, and room for the ticket */
+#define CTR_NCF_PROJ_COUNT_STRIDE 72   /* int32 of plan per table row: 64 chunk counts, total, offset, and room for the head and the block totals */
 typedef struct ctr_ncf_proj {
   const int64_t* user_idx; int64_t user_stride;   /* ids of the batch, element strides */
   const int64_t* item_idx; int64_t item_stride;
