@@ -2,12 +2,14 @@
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace as Params
 
 import numpy as np
 import torch
 from torch import nn
 
 from .. import _lib, ops, sparse
+from ..ops import Layer
 
 
 class CtrModule(nn.Module):
@@ -46,25 +48,47 @@ class CtrModule(nn.Module):
     def _need_device(*tensors):
         _lib.require_device(*tensors)
 
-    # ---- opt-in sparse mode of the big tables' gradients (sparse.py)
-    def sparse_ids(self, inputs):
-        """{position in the autograd node's parameter list: [id tensors scattered into that table]} -- models
-        whose tables can run in sparse mode override this"""
-        return {}
+    # ---- the way into the autograd node
+    @staticmethod
+    def _dense(t):
+        """an input in the layout the kernels read"""
+        return t.contiguous()
 
-    def _node_params(self):
-        return self._params()
+    def _run(self, inputs, p, exchanged=()):
+        """``inputs`` and the named parameters ``p`` through ``_ModelFunction``.  ``exchanged`` names the entries of
+        ``p`` that the caller replaced by rows of a sharded table (``_zero_grads``)."""
+        flat, spec = _flatten(p)
+        self._need_device(*inputs, *flat)
+        inputs = [self._dense(t) for t in inputs]
+        object.__setattr__(self, "_flag", self._err_flag(inputs[0].device))
+        out = _ModelFunction.apply(self, spec, exchanged, len(inputs), *inputs, *flat)
+        self._raise_if_bad_index()
+        return out
+
+    def _zero_grads(self, flat, rows=()):
+        """{id(t): zero gradient} for a backward pass: one flat buffer for the parameters ``flat``.  The exchanged
+        ``rows`` of a sharded table are an activation, not a replicated parameter: their gradient gets a buffer of
+        its own, so that the data-parallel all-reduce of the flat one does not carry it."""
+        own = {id(t) for t in rows}
+        zeros = ops.zero_grads([t for t in flat if id(t) not in own])
+        for t in rows:
+            zeros[id(t)] = torch.zeros_like(t)
+        return zeros
+
+    # ---- opt-in sparse mode of the big tables' gradients (sparse.py; SURVEY 8f-3)
+    def sparse_ids(self, inputs, p):
+        """[(table out of ``p``, [id tensors scattered into that table])] -- models whose tables can run in sparse
+        mode override this; ``inputs is None`` asks for the tables alone"""
+        return []
 
     def sparse_grads(self, enable: bool = True, min_rows: int = 65536):
         """switch the tables with at least ``min_rows`` rows to the sparse gradient mode (or back).  Call after the
         module is on its device; train with ``deeplearningrecommendationsystem_amd.optim.Adam`` (it updates the
         pending rows; a stock torch optimizer would see ``grad is None`` and skip these tables)."""
-        params = self._node_params()
-        positions = sorted(self.sparse_ids(None))
-        if enable and not positions:
+        tables = [t for t, _ in self.sparse_ids(None, self._params())]
+        if enable and not tables:
             raise NotImplementedError(f"{type(self).__name__} has no sparse-mode tables")
-        for k in positions:
-            p = params[k]
+        for p in tables:
             if enable and p.shape[0] >= min_rows:
                 if sparse.state_of(p) is None:
                     p._ctr_sparse = sparse.SparseRows(p)
@@ -81,59 +105,82 @@ def topk_rows(scores: torch.Tensor, k: int) -> np.ndarray:
     return ops.topk_rows(scores, k).cpu().numpy()
 
 
+def _flatten(p):
+    """named parameters -> (the tensors in the order autograd sees them, what ``_rebuild`` needs besides them).  An
+    entry of ``p`` is a tensor, an ``ops.Layer`` (weight, then bias) or a list of entries."""
+    flat = []
+
+    def walk(v):
+        if isinstance(v, Layer):
+            flat.extend((v.weight, v.bias))
+            return Layer(None, None, v.act)
+        if isinstance(v, (list, tuple)):
+            return [walk(item) for item in v]
+        flat.append(v)
+        return None
+
+    spec = {name: walk(v) for name, v in vars(p).items()}
+    return tuple(flat), spec
+
+
+def _rebuild(spec, flat):
+    """the named parameters of ``_flatten`` around the tensors ``flat``"""
+    flat = iter(flat)
+
+    def walk(s):
+        if isinstance(s, Layer):
+            return Layer(next(flat), next(flat), s.act)
+        return next(flat) if s is None else [walk(item) for item in s]
+
+    return Params(**{name: walk(s) for name, s in spec.items()})
+
+
 class _ModelFunction(torch.autograd.Function):
-    """one autograd node per model: ``impl.run_forward(inputs, params)`` returns
-    ``(output, state)``; ``impl.run_backward(state, inputs, params, gout)``
-    returns one gradient (or None) per parameter.  Forward and backward are
-    straight sequences of libctrhip launches on torch's current stream."""
+    """one autograd node per model: ``impl.run_forward(inputs, p)`` returns ``(output, state)``;
+    ``impl.run_backward(state, inputs, p, gout, zeros)`` leaves every parameter's gradient in ``zeros`` (keyed by
+    ``id``).  Forward and backward are straight sequences of libctrhip launches on torch's current stream."""
 
     @staticmethod
-    def forward(ctx, impl, n_inputs, *tensors):
-        inputs, params = tensors[:n_inputs], tensors[n_inputs:]
-        out, state = impl.run_forward(inputs, params)
-        ctx.impl, ctx.state, ctx.n_inputs = impl, state, n_inputs
+    def forward(ctx, impl, spec, exchanged, n_inputs, *tensors):
+        out, state = impl.run_forward(tensors[:n_inputs], _rebuild(spec, tensors[n_inputs:]))
+        ctx.impl, ctx.state, ctx.spec, ctx.exchanged, ctx.n_inputs = impl, state, spec, exchanged, n_inputs
         ctx.save_for_backward(*tensors)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         tensors = ctx.saved_tensors
-        inputs, params = tensors[:ctx.n_inputs], tensors[ctx.n_inputs:]
-        grads = ctx.impl.run_backward(ctx.state, inputs, params, gout.contiguous())
+        inputs, flat = tensors[:ctx.n_inputs], tensors[ctx.n_inputs:]
+        p, gout = _rebuild(ctx.spec, flat), gout.contiguous()
+        zeros = ctx.impl._zero_grads(flat, [getattr(p, name) for name in ctx.exchanged])
+        ctx.impl.run_backward(ctx.state, inputs, p, gout, zeros)
         ctx.state = None
-        if any(sparse.state_of(p) is not None for p in params):
+        grads = [zeros[id(t)] for t in flat]
+        if any(sparse.state_of(t) is not None for t in flat):
             # sparse mode: the scatter went into the tables' persistent buffers; list the rows it touched and
             # hand autograd no dense gradient for those tables
-            grads = list(grads)
+            slot = {id(t): k for k, t in enumerate(flat)}
             jobs = []
-            for k, id_list in ctx.impl.sparse_ids(inputs).items():
-                if sparse.state_of(params[k]) is not None:
-                    jobs += [(params[k], ids) for ids in id_list]
-                    grads[k] = None
+            for table, id_list in ctx.impl.sparse_ids(inputs, p):
+                if sparse.state_of(table) is not None:
+                    jobs += [(table, ids) for ids in id_list]
+                    grads[slot[id(table)]] = None
             sparse.mark(jobs)
-        return (None, None) + (None,) * ctx.n_inputs + tuple(grads)
+        return (None,) * (4 + ctx.n_inputs) + tuple(grads)
 
 
 class FeatureModel(CtrModule):
     """models fed by the (B,45) float feature matrix of data/reader.py:98-112"""
 
-    def _run_model(self, x, params):
-        self._need_device(x, params[0])
+    @staticmethod
+    def _dense(x):
+        return x if x.stride(1) == 1 else x.contiguous()     # the kernels take a row stride
+
+    def _run_model(self, x, p, exchanged=()):
+        self._need_device(x)
         if x.dim() != 2 or x.shape[1] != 45 or x.dtype != torch.float32:
             raise ValueError(f"expected a (B,45) float32 feature matrix, got {tuple(x.shape)} {x.dtype}")
-        x = x if x.stride(1) == 1 else x.contiguous()
-        object.__setattr__(self, "_flag", self._err_flag(x.device))
-        out = _ModelFunction.apply(self, 1, x, *params)
-        self._raise_if_bad_index()
-        return out
-
-    def _run_fields(self, idx, params):
-        """N-id-field generalisation: ``idx`` (B, F) int64 on the device"""
-        self._need_device(idx, params[0])
-        object.__setattr__(self, "_flag", self._err_flag(idx.device))
-        out = _ModelFunction.apply(self, 1, idx, *params)
-        self._raise_if_bad_index()
-        return out
+        return self._run([x], p, exchanged)
 
     def _aligned_weight(self, w, refresh=True):
         """weights whose rows are not a multiple of 4 floats long: the GEMM kernels stage 16-byte

@@ -8,7 +8,7 @@ from torch.nn.init import xavier_normal_
 from .. import ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec
 from .._lib import FIELD_BAG, FIELD_ID_F32
-from ._base import FeatureModel
+from ._base import FeatureModel, Params
 
 NVEC, NPAIRS = 6, 15
 
@@ -41,10 +41,11 @@ class AFM(FeatureModel):
             xavier_normal_(emb.weight.data)
 
     def _params(self):
-        return [self.user_embedding.weight, self.item_embedding.weight, self.gender_embedding.weight,
-                self.occupation_embedding.weight, self.movie_embedding.weight, self.attention_W, self.attention_b,
-                self.attention_h, self.output_layer.weight, self.output_layer.bias, self.user.weight,
-                self.item.weight, self.linear.weight, self.linear.bias]
+        return Params(tables=[e.weight for e in (self.user_embedding, self.item_embedding, self.gender_embedding,
+                                                 self.occupation_embedding, self.movie_embedding)],
+                      att_w=self.attention_W, att_b=self.attention_b, att_h=self.attention_h,
+                      out_w=self.output_layer.weight, out_b=self.output_layer.bias, user1=self.user.weight,
+                      item1=self.item.weight, lin_w=self.linear.weight, lin_b=self.linear.bias)
 
     def forward(self, x):
         return self._run_model(x, self._params())
@@ -67,41 +68,36 @@ class AFM(FeatureModel):
             FieldSpec(FIELD_BAG, e, 5 * e, table=movie, src_col=26, bag_size=19),
         ]
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        tables = params[:5]
-        att_w, att_b, att_h, out_w, out_b, user1, item1, lin_w, lin_b = params[5:14]
-        batch, e, dev = x.shape[0], tables[0].shape[1], x.device
+        batch, e, dev = x.shape[0], self.user_embedding.embedding_dim, x.device
         emb = torch.empty((batch, NVEC * e), dtype=torch.float32, device=dev)
-        ops.embed_fwd(self._specs(tables, e, dev), x, batch, emb, self._flag)
+        ops.embed_fwd(self._specs(p.tables, e, dev), x, batch, emb, self._flag)
         pairs = self._padded_rows(batch * NPAIRS, e, dev)
         ops.pairprod_fwd(emb, NVEC, e, pairs)
-        wt = att_w.t().contiguous()                       # (A, E): nn.Linear layout of the attention map
-        hidden = ops.linear_fwd(pairs, self._aligned_weight(wt), att_b, ACT_RELU)
-        ht = att_h.t().contiguous()                       # (1, A)
+        wt = p.att_w.t().contiguous()                       # (A, E): nn.Linear layout of the attention map
+        hidden = ops.linear_fwd(pairs, self._aligned_weight(wt), p.att_b, ACT_RELU)
+        ht = p.att_h.t().contiguous()                       # (1, A)
         score = ops.linear_fwd(hidden, ht, None, ACT_NONE)
         attn = torch.empty((batch, NPAIRS), dtype=torch.float32, device=dev)
         pooled = self._padded_rows(batch, e, dev)
         ops.din_pool_fwd(score, pairs, batch, NPAIRS, e, attn, pooled, summed=True)
         wide = torch.empty((batch, 1), dtype=torch.float32, device=dev)
-        ops.fm_wide_fwd(emb[:, :e], 1, e, x, user1, item1, lin_w, lin_b, wide, self._flag)
-        prob = ops.linear_fwd(pooled, out_w, out_b, ACT_SIGMOID, residual=wide)
+        ops.fm_wide_fwd(emb[:, :e], 1, e, x, p.user1, p.item1, p.lin_w, p.lin_b, wide, self._flag)
+        prob = ops.linear_fwd(pooled, p.out_w, p.out_b, ACT_SIGMOID, residual=wide)
         return prob, (emb, pairs, wt, ht, hidden, attn, pooled, prob)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         emb, pairs, wt, ht, hidden, attn, pooled, prob = state
-        tables = params[:5]
-        att_w, att_b, att_h, out_w, out_b, user1, item1, lin_w, lin_b = params[5:14]
-        batch, e, dev = x.shape[0], tables[0].shape[1], x.device
-        zeros = ops.zero_grads(params)
+        batch, e, dev = x.shape[0], self.user_embedding.embedding_dim, x.device
         # sigmoid(wide + pooled W^T + b): the residual's gradient is gz itself
         gz = torch.empty_like(prob)
         ops.act_bwd(prob, gprob, ACT_SIGMOID, gz, accumulate=False)
         gpooled = self._padded_rows(batch, e, dev)
-        ops.linear_bwd(pooled, out_w, None, gz, ACT_NONE, gpooled, zeros[id(out_w)], zeros[id(out_b)])
-        ops.fm_wide_bwd(emb[:, :e], 1, e, x, user1, item1, lin_w, lin_b, gz, zeros[id(user1)], zeros[id(item1)],
-                        zeros[id(lin_w)], zeros[id(lin_b)], None, accumulate=False)
+        ops.linear_bwd(pooled, p.out_w, None, gz, ACT_NONE, gpooled, zeros[id(p.out_w)], zeros[id(p.out_b)])
+        ops.fm_wide_bwd(emb[:, :e], 1, e, x, p.user1, p.item1, p.lin_w, p.lin_b, gz, zeros[id(p.user1)],
+                        zeros[id(p.item1)], zeros[id(p.lin_w)], zeros[id(p.lin_b)], None, accumulate=False)
         gscore = torch.empty((batch * NPAIRS, 1), dtype=torch.float32, device=dev)
         ops.din_pool_bwd(attn, pairs, batch, NPAIRS, e, gpooled, True, gscore)
         ghidden = torch.empty_like(hidden)
@@ -110,13 +106,12 @@ class AFM(FeatureModel):
         gpairs = self._padded_rows(batch * NPAIRS, e, dev)
         gwt = torch.zeros_like(wt)
         ops.linear_bwd(pairs, self._aligned_weight(wt, refresh=False), hidden, ghidden, ACT_RELU, gpairs, gwt,
-                       zeros[id(att_b)])
-        zeros[id(att_w)].copy_(gwt.t())
-        zeros[id(att_h)].copy_(ght.t())
+                       zeros[id(p.att_b)])
+        zeros[id(p.att_w)].copy_(gwt.t())
+        zeros[id(p.att_h)].copy_(ght.t())
         gemb = torch.empty_like(emb)
         ops.pairprod_bwd(emb, NVEC, e, gpairs, attn, gpooled, gemb, accumulate=False)
-        ops.embed_bwd(self._specs(tables, e, dev), x, batch, gemb, zeros)
-        return [zeros[id(p)] for p in params]
+        ops.embed_bwd(self._specs(p.tables, e, dev), x, batch, gemb, zeros)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)

@@ -6,7 +6,7 @@ from torch import nn
 
 from .. import ops
 from ..ops import ACT_SIGMOID, Layer
-from ._base import CtrModule, _ModelFunction
+from ._base import CtrModule, Params
 
 
 class AutoRec(CtrModule):
@@ -19,12 +19,22 @@ class AutoRec(CtrModule):
         self.encoder = nn.Linear(num_input, hidden_units)
         self.decoder = nn.Linear(hidden_units, num_input)
 
+    def _params(self):
+        return Params(enc=Layer(self.encoder.weight, self.encoder.bias, ACT_SIGMOID),
+                      dec=Layer(self.decoder.weight, self.decoder.bias, ACT_SIGMOID))
+
+    def _err_flag(self, device):
+        return None       # no ids: no kernel here can raise the flag, so there is none to read back
+
+    @staticmethod
+    def _dense(x):
+        return x          # ``_rows4`` stages whatever layout arrives
+
     def forward(self, x):
-        params = [self.encoder.weight, self.encoder.bias, self.decoder.weight, self.decoder.bias]
-        self._need_device(x, params[0])
+        self._need_device(x, self.encoder.weight)
         if x.dim() != 2 or x.shape[1] != self.encoder.in_features or x.dtype != torch.float32:
             raise ValueError(f"expected a (B,{self.encoder.in_features}) float32 matrix, got {tuple(x.shape)} {x.dtype}")
-        return _ModelFunction.apply(self, 1, x, *params)
+        return self._run([x], self._params())
 
     @staticmethod
     def _rows4(t):
@@ -35,23 +45,21 @@ class AutoRec(CtrModule):
         buf.copy_(t)
         return buf
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        w1, b1, w2, b2 = params
+        (w1, b1), (w2, b2) = (p.enc.weight, p.enc.bias), (p.dec.weight, p.dec.bias)
         xa = self._rows4(x)
         hidden = ops.linear_fwd(xa, self._rows4(w1.detach()), b1, ACT_SIGMOID)
         out = torch.empty((x.shape[0], (w2.shape[0] + 3) // 4 * 4), dtype=torch.float32, device=x.device)[:, :w2.shape[0]]
         ops.linear_fwd(hidden, w2, b2, ACT_SIGMOID, out=out)
         return out, (xa, hidden, out)
 
-    def run_backward(self, state, inputs, params, gout):
+    def run_backward(self, state, inputs, p, gout, zeros):
         xa, hidden, out = state
-        w1, b1, w2, b2 = params
-        zeros = ops.zero_grads(params)
+        (w1, b1), (w2, b2) = (p.enc.weight, p.enc.bias), (p.dec.weight, p.dec.bias)
         ghidden = torch.empty_like(hidden)
         ops.linear_bwd(hidden, w2, out, self._rows4(gout), ACT_SIGMOID, ghidden, zeros[id(w2)], zeros[id(b2)])
         ops.linear_bwd(xa, self._rows4(w1.detach()), hidden, ghidden, ACT_SIGMOID, None, zeros[id(w1)], zeros[id(b1)])
-        return [zeros[id(p)] for p in params]
 
     def recommendation(self, rating_matrix, k):
         with torch.no_grad():

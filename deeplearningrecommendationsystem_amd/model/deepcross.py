@@ -6,8 +6,8 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import ops
-from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID
-from ._base import FeatureModel
+from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
+from ._base import FeatureModel, Params
 from .deepcrossing import DeepCrossing
 
 
@@ -58,85 +58,68 @@ class DeepCross(FeatureModel):
                     self.movie_embedding):
             xavier_normal_(emb.weight.data)
 
-    def _deep_linears(self):
-        return [m for m in self.deep_network.network if isinstance(m, nn.Linear)]
-
     def _params(self):
-        p = [e.weight for e in (self.user_embedding, self.item_embedding, self.gender_embedding,
-                                self.occupation_embedding, self.movie_embedding)]
-        p += [lin.weight for lin in self.cross_network.cross_weights]
-        p += list(self.cross_network.cross_biases)
-        for lin in self._deep_linears():
-            p += [lin.weight, lin.bias]
-        p += [self.output_layer.weight, self.output_layer.bias]
-        return p
+        return Params(tables=[e.weight for e in (self.user_embedding, self.item_embedding, self.gender_embedding,
+                                                 self.occupation_embedding, self.movie_embedding)],
+                      cw=[lin.weight for lin in self.cross_network.cross_weights],
+                      cb=list(self.cross_network.cross_biases),
+                      deep=[Layer(m.weight, m.bias, ACT_RELU) for m in self.deep_network.network
+                            if isinstance(m, nn.Linear)],
+                      out_w=self.output_layer.weight, out_b=self.output_layer.bias)
 
     def forward(self, x):
         return self._run_model(x, self._params())
 
-    def _split(self, params):
-        nc, nd = self.cross_network.num_layers, len(self._deep_linears())
-        tables = params[:5]
-        cw, cb = params[5:5 + nc], params[5 + nc:5 + 2 * nc]
-        deep = params[5 + 2 * nc:5 + 2 * nc + 2 * nd]
-        out_w, out_b = params[-2:]
-        return tables, cw, cb, [(deep[2 * k], deep[2 * k + 1]) for k in range(nd)], out_w, out_b
-
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        tables, cw, cb, deep, out_w, out_b = self._split(params)
-        batch, e = x.shape[0], tables[0].shape[1]
+        batch, e = x.shape[0], self.user_embedding.embedding_dim
         d, dev = 5 * e + 1, x.device
-        hl = deep[-1][0].shape[0]
         x0 = self._padded_rows(batch, d, dev)
-        ops.embed_fwd(DeepCrossing._specs(tables, e), x, batch, x0, self._flag)
-        comb = self._padded_rows(batch, d + hl, dev)        # [x_L | deep_out]: operand of the output layer
+        ops.embed_fwd(DeepCrossing._specs(p.tables, e), x, batch, x0, self._flag)
+        *_, last = p.deep
+        comb = self._padded_rows(batch, d + last.weight.shape[0], dev)   # [x_L | deep_out]: operand of the output layer
         xs, us = [x0], []
-        for l in range(len(cw)):
-            u = ops.linear_fwd(xs[-1], self._aligned_weight(cw[l]), None, ACT_NONE, out=self._padded_rows(batch, d, dev))
-            out = comb[:, :d] if l == len(cw) - 1 else self._padded_rows(batch, d, dev)
-            ops.cross_fwd(x0, u, xs[-1], cb[l], out)
+        for l, (w, b) in enumerate(zip(p.cw, p.cb)):
+            u = ops.linear_fwd(xs[-1], self._aligned_weight(w), None, ACT_NONE, out=self._padded_rows(batch, d, dev))
+            out = comb[:, :d] if l == len(p.cw) - 1 else self._padded_rows(batch, d, dev)
+            ops.cross_fwd(x0, u, xs[-1], b, out)
             us.append(u)
             xs.append(out)
-        if not cw:
+        if not p.cw:
             comb[:, :d].copy_(x0)
         hs = [x0]
-        for k, (w, b) in enumerate(deep):
-            out = comb[:, d:] if k == len(deep) - 1 else None
-            hs.append(ops.linear_fwd(hs[-1], self._aligned_weight(w) if k == 0 else w, b, ACT_RELU, out=out))
-        prob = ops.linear_fwd(comb, self._aligned_weight(out_w), out_b, ACT_SIGMOID)
+        for k, layer in enumerate(p.deep):
+            out = comb[:, d:] if k == len(p.deep) - 1 else None
+            w = self._aligned_weight(layer.weight) if k == 0 else layer.weight
+            hs.append(ops.linear_fwd(hs[-1], w, layer.bias, ACT_RELU, out=out))
+        prob = ops.linear_fwd(comb, self._aligned_weight(p.out_w), p.out_b, ACT_SIGMOID)
         return prob, (xs, us, hs, comb, prob)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         xs, us, hs, comb, prob = state
-        tables, cw, cb, deep, out_w, out_b = self._split(params)
-        batch, e = x.shape[0], tables[0].shape[1]
+        batch, e = x.shape[0], self.user_embedding.embedding_dim
         d, dev = 5 * e + 1, x.device
-        hl = deep[-1][0].shape[0]
-        zeros = ops.zero_grads(params)
-        gcomb = self._padded_rows(batch, d + hl, dev)
-        ops.linear_bwd(comb, self._aligned_weight(out_w, refresh=False), prob, gprob, ACT_SIGMOID, gcomb,
-                       zeros[id(out_w)], zeros[id(out_b)])
+        gcomb = self._padded_rows(batch, comb.shape[1], dev)
+        ops.linear_bwd(comb, self._aligned_weight(p.out_w, refresh=False), prob, gprob, ACT_SIGMOID, gcomb,
+                       zeros[id(p.out_w)], zeros[id(p.out_b)])
         # deep tower: its input gradient starts the accumulator of d loss / d x0
         gh = gcomb[:, d:]
-        for k in range(len(deep) - 1, -1, -1):
-            w, b = deep[k]
+        for k, layer in reversed(list(enumerate(p.deep))):
             gin = self._padded_rows(batch, hs[k].shape[1], dev)
-            ops.linear_bwd(hs[k], self._aligned_weight(w, refresh=False) if k == 0 else w, hs[k + 1], gh, ACT_RELU, gin,
-                           zeros[id(w)], zeros[id(b)])
+            w = self._aligned_weight(layer.weight, refresh=False) if k == 0 else layer.weight
+            ops.linear_bwd(hs[k], w, hs[k + 1], gh, ACT_RELU, gin, zeros[id(layer.weight)], zeros[id(layer.bias)])
             gh = gin
         gx0 = gh
         # cross layers, last to first: gx holds d loss / d x_{l+1}, becomes d loss / d x_l in place
         gx = gcomb[:, :d]
-        for l in range(len(cw) - 1, -1, -1):
+        for l, (w, b) in reversed(list(enumerate(zip(p.cw, p.cb)))):
             gu = self._padded_rows(batch, d, dev)
-            ops.cross_bwd(xs[0], us[l], gx, gu, gx0, zeros[id(cb[l])])
-            ops.linear_bwd(xs[l], self._aligned_weight(cw[l], refresh=False), None, gu, ACT_NONE, gx, zeros[id(cw[l])],
+            ops.cross_bwd(xs[0], us[l], gx, gu, gx0, zeros[id(b)])
+            ops.linear_bwd(xs[l], self._aligned_weight(w, refresh=False), None, gu, ACT_NONE, gx, zeros[id(w)],
                            None, accumulate_gx=True)
         ops.act_bwd(gx, gx, ACT_NONE, gx0, accumulate=True)   # x_0 is x0 itself: gx0 += gx
-        ops.embed_bwd(DeepCrossing._specs(tables, e), x, batch, gx0, zeros)
-        return [zeros[id(p)] for p in params]
+        ops.embed_bwd(DeepCrossing._specs(p.tables, e), x, batch, gx0, zeros)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)

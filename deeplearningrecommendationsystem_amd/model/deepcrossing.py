@@ -6,9 +6,9 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import ops
-from ..ops import ACT_RELU, ACT_SIGMOID, FieldSpec
+from ..ops import ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
 from .._lib import FIELD_BAG, FIELD_DENSE, FIELD_ID_F32
-from ._base import FeatureModel
+from ._base import FeatureModel, Params
 
 
 class ResidualBlock(nn.Module):
@@ -44,12 +44,12 @@ class DeepCrossing(FeatureModel):
         self.linear = nn.Linear(dim_stack, 1)
 
     def _params(self):
-        p = [e.weight for e in (self.user_embedding, self.item_embedding, self.gender_embedding,
-                                self.occupation_embedding, self.movie_embedding)]
-        p += [self.linear.weight, self.linear.bias]
-        for blk in self.res_layers:
-            p += [blk.linear1.weight, blk.linear1.bias, blk.linear2.weight, blk.linear2.bias]
-        return p
+        """``res``: one [linear1, linear2] pair per residual block"""
+        return Params(tables=[e.weight for e in (self.user_embedding, self.item_embedding, self.gender_embedding,
+                                                 self.occupation_embedding, self.movie_embedding)],
+                      lin_w=self.linear.weight, lin_b=self.linear.bias,
+                      res=[[Layer(lin.weight, lin.bias, ACT_RELU) for lin in (blk.linear1, blk.linear2)]
+                           for blk in self.res_layers])
 
     def forward(self, feature_vector):
         return self._run_model(feature_vector, self._params())
@@ -71,52 +71,41 @@ class DeepCrossing(FeatureModel):
         padded = (width + 3) // 4 * 4
         return torch.empty((batch, padded), dtype=torch.float32, device=device)[:, :width]
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        tables, (lin_w, lin_b) = params[:5], params[5:7]
-        batch, e = x.shape[0], tables[0].shape[1]
+        batch, e = x.shape[0], self.user_embedding.embedding_dim
         width = 5 * e + 1
         r = self._stack_buffer(batch, width, x.device)
-        ops.embed_fwd(self._specs(tables, e), x, batch, r, self._flag)
+        ops.embed_fwd(self._specs(p.tables, e), x, batch, r, self._flag)
         rs, hs = [r], []
-        for k in range(len(self.res_layers)):
-            w1, b1, w2, b2 = params[7 + 4 * k: 11 + 4 * k]
-            h = ops.linear_fwd(rs[-1], self._aligned_weight(w1), b1, ACT_RELU)
+        for lin1, lin2 in p.res:
+            h = ops.linear_fwd(rs[-1], self._aligned_weight(lin1.weight), lin1.bias, ACT_RELU)
             out = self._stack_buffer(batch, width, x.device)
-            ops.linear_fwd(h, w2, b2, ACT_RELU, out=out, residual=rs[-1])
+            ops.linear_fwd(h, lin2.weight, lin2.bias, ACT_RELU, out=out, residual=rs[-1])
             hs.append(h)
             rs.append(out)
-        prob = ops.linear_fwd(rs[-1], self._aligned_weight(lin_w), lin_b, ACT_SIGMOID)
+        prob = ops.linear_fwd(rs[-1], self._aligned_weight(p.lin_w), p.lin_b, ACT_SIGMOID)
         return prob, (rs, hs, prob)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         rs, hs, prob = state
-        tables, (lin_w, lin_b) = params[:5], params[5:7]
-        batch, e = x.shape[0], tables[0].shape[1]
+        batch, e = x.shape[0], self.user_embedding.embedding_dim
         width = 5 * e + 1
-        zeros = ops.zero_grads(params)
-        g_lin_w, g_lin_b = zeros[id(lin_w)], zeros[id(lin_b)]
         gr = self._stack_buffer(batch, width, x.device)
-        ops.linear_bwd(rs[-1], self._aligned_weight(lin_w, refresh=False), prob, gprob, ACT_SIGMOID, gr, g_lin_w, g_lin_b)
-        block_grads = []
-        for k in range(len(self.res_layers) - 1, -1, -1):
-            w1, b1, w2, b2 = params[7 + 4 * k: 11 + 4 * k]
+        ops.linear_bwd(rs[-1], self._aligned_weight(p.lin_w, refresh=False), prob, gprob, ACT_SIGMOID, gr,
+                       zeros[id(p.lin_w)], zeros[id(p.lin_b)])
+        for k, (lin1, lin2) in reversed(list(enumerate(p.res))):
             r_in, r_out, h = rs[k], rs[k + 1], hs[k]
-            gw1, gb1, gw2, gb2 = (zeros[id(t)] for t in (w1, b1, w2, b2))
             gh = torch.empty_like(h)
-            ops.linear_bwd(h, w2, r_out, gr, ACT_RELU, gh, gw2, gb2)            # through relu(linear2(h)+r)
+            ops.linear_bwd(h, lin2.weight, r_out, gr, ACT_RELU, gh, zeros[id(lin2.weight)],
+                           zeros[id(lin2.bias)])                                # through relu(linear2(h)+r)
             gr_in = self._stack_buffer(batch, width, x.device)
-            ops.linear_bwd(r_in, self._aligned_weight(w1, refresh=False), h, gh, ACT_RELU, gr_in, gw1, gb1)  # relu(linear1(r))
+            ops.linear_bwd(r_in, self._aligned_weight(lin1.weight, refresh=False), h, gh, ACT_RELU, gr_in,
+                           zeros[id(lin1.weight)], zeros[id(lin1.bias)])        # relu(linear1(r))
             ops.act_bwd(r_out, gr, ACT_RELU, gr_in, accumulate=True)            # the skip connection
             gr = gr_in
-            block_grads.append((gw1, gb1, gw2, gb2))
-        tgrads = zeros
-        ops.embed_bwd(self._specs(tables, e), x, batch, gr, tgrads)
-        grads = [tgrads[id(t)] for t in tables] + [g_lin_w, g_lin_b]
-        for bg in reversed(block_grads):
-            grads += list(bg)
-        return grads
+        ops.embed_bwd(self._specs(p.tables, e), x, batch, gr, zeros)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)

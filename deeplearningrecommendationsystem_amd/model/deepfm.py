@@ -8,7 +8,7 @@ from torch.nn.init import xavier_normal_
 from .. import ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
 from .._lib import FIELD_BAG, FIELD_ID_F32
-from ._base import FeatureModel
+from ._base import FeatureModel, Params
 
 
 def six_field_specs(tables, dim):
@@ -95,115 +95,81 @@ class DeepFM(FeatureModel):
                     self.occupation_embedding, self.movie_embedding, self.user, self.item):
             xavier_normal_(emb.weight.data)
 
-    # parameter order handed to the autograd node
     def _params(self):
+        """``deep``: ``linear`` without activation, then Linear+ReLU"""
+        deep = [Layer(self.linear.weight, self.linear.bias, ACT_NONE)]
+        deep += [Layer(lin.weight, lin.bias, ACT_RELU) for lin in self.dnn_network]
         if self.num_fields is not None:
-            p = [e.weight for e in self.embeddings] + [e.weight for e in self.first_order]
-            p += [self.first_order_bias, self.output.weight, self.output.bias, self.linear.weight, self.linear.bias]
-            for lin in self.dnn_network:
-                p += [lin.weight, lin.bias]
-            return p
-        p = [e.weight for e in (self.user_embedding, self.item_embedding, self.age_embedding,
-                                self.gender_embedding, self.occupation_embedding, self.movie_embedding)]
-        p += [self.user.weight, self.item.weight, self.wide.weight, self.wide.bias,
-              self.output.weight, self.output.bias, self.linear.weight, self.linear.bias]
-        for lin in self.dnn_network:
-            p += [lin.weight, lin.bias]
-        return p
+            return Params(tables=[e.weight for e in self.embeddings], firsts=[e.weight for e in self.first_order],
+                          bias=self.first_order_bias, out_w=self.output.weight, out_b=self.output.bias, deep=deep)
+        return Params(tables=[e.weight for e in (self.user_embedding, self.item_embedding, self.age_embedding,
+                                                 self.gender_embedding, self.occupation_embedding,
+                                                 self.movie_embedding)],
+                      user1=self.user.weight, item1=self.item.weight, wide_w=self.wide.weight, wide_b=self.wide.bias,
+                      out_w=self.output.weight, out_b=self.output.bias, deep=deep)
 
-    def sparse_ids(self, inputs):
+    def sparse_ids(self, inputs, p):
         """sparse mode: the id tables and their first-order (V,1) companions"""
         if self.num_fields is not None:
-            nf = self.num_fields
-            cols = [[] if inputs is None else [inputs[0][:, f]] for f in range(nf)]
-            return {k: cols[k % nf] for k in range(2 * nf)}
+            cols = [[] if inputs is None else [inputs[0][:, f]] for f in range(self.num_fields)]
+            return list(zip(p.tables + p.firsts, cols + cols))
         cols = [[] if inputs is None else [inputs[0][:, c]] for c in (0, 1)]   # float id columns of the (B,45) matrix
-        return {0: cols[0], 1: cols[1], 6: cols[0], 7: cols[1]}
+        user, item, *_ = p.tables
+        return list(zip((user, item, p.user1, p.item1), cols + cols))
 
     def forward(self, x):
         if self.num_fields is not None:
-            return self._run_fields(FieldsInput.ids(x, self.num_fields), self._params())
+            return self._run([FieldsInput.ids(x, self.num_fields)], self._params())
         return self._run_model(x, self._params())
 
-    def _layers(self, params, first=12):
-        layers = [Layer(params[first], params[first + 1], ACT_NONE)]
-        for k in range(len(self.dnn_network)):
-            layers.append(Layer(params[first + 2 + 2 * k], params[first + 3 + 2 * k], ACT_RELU))
-        return layers
-
     # ---- N id fields: gather fused with the FM term (csrc/fields.hip)
-    def _fields_forward(self, idx, params):
-        nf = self.num_fields
-        tables, firsts = params[:nf], params[nf:2 * nf]
-        bias, out_w, out_b = params[2 * nf:2 * nf + 3]
-        batch, dim = idx.shape[0], tables[0].shape[1]
-        layers = self._layers(params, 2 * nf + 3)
-        emb = torch.empty((batch, nf * dim), dtype=torch.float32, device=idx.device)
-        comb = torch.empty((batch, 1 + layers[-1].weight.shape[0]), dtype=torch.float32, device=idx.device)
-        ops.fields_fm_fwd(idx, tables, firsts, bias, emb, comb[:, 0:1], self._flag)
-        acts = ops.mlp_fwd(emb, layers, last_out=comb[:, 1:])
-        prob = ops.linear_fwd(comb, out_w, out_b, ACT_SIGMOID)
+    def _fields_forward(self, idx, p):
+        batch, dim = idx.shape[0], self.linear.in_features // self.num_fields
+        *_, last = p.deep
+        emb = torch.empty((batch, self.num_fields * dim), dtype=torch.float32, device=idx.device)
+        comb = torch.empty((batch, 1 + last.weight.shape[0]), dtype=torch.float32, device=idx.device)
+        ops.fields_fm_fwd(idx, p.tables, p.firsts, p.bias, emb, comb[:, 0:1], self._flag)
+        acts = ops.mlp_fwd(emb, p.deep, last_out=comb[:, 1:])
+        prob = ops.linear_fwd(comb, p.out_w, p.out_b, ACT_SIGMOID)
         return prob, (emb, comb, acts, prob)
 
-    def _fields_backward(self, state, idx, params, gprob):
-        nf = self.num_fields
+    def _fields_backward(self, state, idx, p, gprob, zeros):
         emb, comb, acts, prob = state
-        tables, firsts = params[:nf], params[nf:2 * nf]
-        bias, out_w, out_b = params[2 * nf:2 * nf + 3]
-        layers = self._layers(params, 2 * nf + 3)
-        zeros = ops.zero_grads(params)
         gcomb = torch.empty_like(comb)
-        ops.linear_bwd(comb, out_w, prob, gprob, ACT_SIGMOID, gcomb, zeros[id(out_w)], zeros[id(out_b)])
+        ops.linear_bwd(comb, p.out_w, prob, gprob, ACT_SIGMOID, gcomb, zeros[id(p.out_w)], zeros[id(p.out_b)])
         gemb = torch.empty_like(emb)
-        layer_grads, _ = ops.mlp_bwd(acts, layers, gcomb[:, 1:], gemb, zeros=zeros)
-        ops.fields_fm_bwd(idx, self.vocabs, tables[0].shape[1], emb, gemb, gcomb[:, 0:1],
-                          [zeros[id(t)] for t in tables], [zeros[id(t)] for t in firsts], zeros[id(bias)])
-        grads = [zeros[id(t)] for t in tables] + [zeros[id(t)] for t in firsts]
-        grads += [zeros[id(bias)], zeros[id(out_w)], zeros[id(out_b)]]
-        for gw, gb in layer_grads:
-            grads += [gw, gb]
-        return grads
+        ops.mlp_bwd(acts, p.deep, gcomb[:, 1:], gemb, zeros=zeros)
+        ops.fields_fm_bwd(idx, self.vocabs, emb.shape[1] // self.num_fields, emb, gemb, gcomb[:, 0:1],
+                          [zeros[id(t)] for t in p.tables], [zeros[id(t)] for t in p.firsts], zeros[id(p.bias)])
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
         if self.num_fields is not None:
-            return self._fields_forward(x, params)
-        tables = params[:6]
-        user1, item1, wide_w, wide_b, out_w, out_b = params[6:12]
-        batch, dim = x.shape[0], tables[0].shape[1]
+            return self._fields_forward(x, p)
+        batch, dim = x.shape[0], self.user_embedding.embedding_dim
+        *_, last = p.deep
         emb = torch.empty((batch, 6 * dim), dtype=torch.float32, device=x.device)
-        ops.embed_fwd(six_field_specs(tables, dim), x, batch, emb, self._flag)
-        layers = self._layers(params)
-        comb = torch.empty((batch, 1 + layers[-1].weight.shape[0]), dtype=torch.float32, device=x.device)
-        acts = ops.mlp_fwd(emb, layers, last_out=comb[:, 1:])
-        ops.fm_wide_fwd(emb, 6, dim, x, user1, item1, wide_w, wide_b, comb[:, 0:1], self._flag)
-        prob = ops.linear_fwd(comb, out_w, out_b, ACT_SIGMOID)
+        ops.embed_fwd(six_field_specs(p.tables, dim), x, batch, emb, self._flag)
+        comb = torch.empty((batch, 1 + last.weight.shape[0]), dtype=torch.float32, device=x.device)
+        acts = ops.mlp_fwd(emb, p.deep, last_out=comb[:, 1:])
+        ops.fm_wide_fwd(emb, 6, dim, x, p.user1, p.item1, p.wide_w, p.wide_b, comb[:, 0:1], self._flag)
+        prob = ops.linear_fwd(comb, p.out_w, p.out_b, ACT_SIGMOID)
         return prob, (emb, comb, acts, prob)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         if self.num_fields is not None:
-            return self._fields_backward(state, x, params, gprob)
+            self._fields_backward(state, x, p, gprob, zeros)
+            return
         emb, comb, acts, prob = state
-        tables = params[:6]
-        user1, item1, wide_w, wide_b, out_w, out_b = params[6:12]
-        batch, dim = x.shape[0], tables[0].shape[1]
-        layers = self._layers(params)
-        zeros = ops.zero_grads(params)
+        batch, dim = x.shape[0], self.user_embedding.embedding_dim
         gcomb = torch.empty_like(comb)
-        g_out_w, g_out_b = zeros[id(out_w)], zeros[id(out_b)]
-        ops.linear_bwd(comb, out_w, prob, gprob, ACT_SIGMOID, gcomb, g_out_w, g_out_b)
+        ops.linear_bwd(comb, p.out_w, prob, gprob, ACT_SIGMOID, gcomb, zeros[id(p.out_w)], zeros[id(p.out_b)])
         gemb = torch.empty_like(emb)
-        layer_grads, _ = ops.mlp_bwd(acts, layers, gcomb[:, 1:], gemb, zeros=zeros)
-        g_user1, g_item1, g_wide_w, g_wide_b = (zeros[id(t)] for t in (user1, item1, wide_w, wide_b))
-        ops.fm_wide_bwd(emb, 6, dim, x, user1, item1, wide_w, wide_b, gcomb[:, 0:1], g_user1, g_item1,
-                        g_wide_w, g_wide_b, gemb, accumulate=True)
-        tgrads = zeros
-        ops.embed_bwd(six_field_specs(tables, dim), x, batch, gemb, tgrads)
-        grads = [tgrads[id(t)] for t in tables] + [g_user1, g_item1, g_wide_w, g_wide_b, g_out_w, g_out_b]
-        for gw, gb in layer_grads:
-            grads += [gw, gb]
-        return grads
+        ops.mlp_bwd(acts, p.deep, gcomb[:, 1:], gemb, zeros=zeros)
+        ops.fm_wide_bwd(emb, 6, dim, x, p.user1, p.item1, p.wide_w, p.wide_b, gcomb[:, 0:1], zeros[id(p.user1)],
+                        zeros[id(p.item1)], zeros[id(p.wide_w)], zeros[id(p.wide_b)], gemb, accumulate=True)
+        ops.embed_bwd(six_field_specs(p.tables, dim), x, batch, gemb, zeros)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)

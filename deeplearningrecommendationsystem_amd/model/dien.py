@@ -8,9 +8,9 @@ import torch.nn as nn
 from torch.nn.init import xavier_normal_
 
 from .. import ops
-from ..ops import ACT_NONE, Layer
-from .din import (SequenceModel, _zero_grads, attention_layers, fc_layers, fold_attention_weight,
-                  unfold_attention_grad)
+from ..ops import ACT_NONE, ACT_SIGMOID
+from ._base import Params
+from .din import SequenceModel, folded_attention, mlp_layers, unfold_attention_grad
 
 # the GRU kernels form the input projection themselves (ctr_gru_fused_fwd / _bwd); CTR_DIEN_FUSED_GRU=0 keeps the
 # gi GEMM + recurrence + three gradient GEMMs for A/B
@@ -47,33 +47,21 @@ class DIEN(SequenceModel):
                                 nn.Linear(64, 1), nn.Sigmoid())
 
     def _params(self):
-        p = [self.din.item_embedding.weight]
-        for k in (0, 2, 4):
-            p += [self.din.attention[k].weight, self.din.attention[k].bias]
-        for k in (0, 2, 4):
-            p += [self.fc[k].weight, self.fc[k].bias]
         g = self.interest_evolution
-        p += [g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0]
-        return p
+        return Params(table=self.din.item_embedding.weight, att=mlp_layers(self.din.attention, ACT_NONE),
+                      fc=mlp_layers(self.fc, ACT_SIGMOID), w_ih=g.weight_ih_l0, w_hh=g.weight_hh_l0, b_ih=g.bias_ih_l0,
+                      b_hh=g.bias_hh_l0)
 
     def forward(self, hist, target_item):
-        params = self._params()
-        if self.sharded:
-            self._need_device(hist, target_item, params[0])
-            rows, hist, target_item = self._lookup_sharded(self.din.item_embedding, hist, target_item)
-            params[0] = rows
-        return self._run_sequence(hist, target_item, params)
+        return self._run_sequence(self.din.item_embedding, hist, target_item, self._params())
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         hist, target = inputs
-        table = params[0]
-        att, fc = attention_layers(params[1:7]), fc_layers(params[7:13])
-        w_ih, w_hh, b_ih, b_hh = params[13:17]
+        table = p.table
         batch, length = hist.shape
         dim = table.shape[1]
         dev = table.device
-        w1f = fold_attention_weight(att[0].weight, dim)  # [h, t] operand instead of [h, h-t, t]
-        att[0] = Layer(w1f, att[0].bias, att[0].act)
+        att, w1f, _ = folded_attention(p.att, dim)  # [h, t] operand instead of [h, h-t, t]
         c = torch.empty((batch * length, 2 * dim), dtype=torch.float32, device=dev)
         fcin = torch.empty((batch, 2 * dim), dtype=torch.float32, device=dev)
         ops.din_concat_fwd(table, hist, target, c, fcin[:, dim:], self._flag, pair=True)
@@ -84,56 +72,46 @@ class DIEN(SequenceModel):
         hbuf = torch.empty((batch * (length + 1), dim), dtype=torch.float32, device=dev)
         # the recurrence kernel forms the input projection itself where it can (E = 16): no (B*L, 3E) gi
         gi = None
-        if not (FUSED_GRU and ops.gru_fused_fwd(seq, w_ih, b_ih, w_hh, b_hh, batch, length, dim, hbuf, fcin[:, :dim])):
-            gi = ops.linear_fwd(seq, w_ih, b_ih)
-            ops.gru_fwd(gi, w_hh, b_hh, batch, length, dim, hbuf, fcin[:, :dim])
-        fc_acts = ops.mlp_fwd(fcin, fc)
+        if not (FUSED_GRU and ops.gru_fused_fwd(seq, p.w_ih, p.b_ih, p.w_hh, p.b_hh, batch, length, dim, hbuf,
+                                                fcin[:, :dim])):
+            gi = ops.linear_fwd(seq, p.w_ih, p.b_ih)
+            ops.gru_fwd(gi, p.w_hh, p.b_hh, batch, length, dim, hbuf, fcin[:, :dim])
+        fc_acts = ops.mlp_fwd(fcin, p.fc)
         return fc_acts[-1], (att_acts, attn, seq, gi, hbuf, fc_acts, w1f)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         hist, target = inputs
         att_acts, attn, seq, gi, hbuf, fc_acts, w1f = state
-        table = params[0]
-        att, fc = attention_layers(params[1:7]), fc_layers(params[7:13])
-        w1 = att[0].weight
-        att[0] = Layer(w1f, att[0].bias, att[0].act)
-        w_ih, w_hh, b_ih, b_hh = params[13:17]
+        table = p.table
         batch, length = hist.shape
         dim = table.shape[1]
         dev = table.device
         c = att_acts[0]
-        zeros = _zero_grads(self, params)
+        att, _, w1 = folded_attention(p.att, dim, w1f)
         zeros[id(w1f)] = torch.zeros_like(w1f)
-        fc_grads, gfcin = ops.mlp_bwd(fc_acts, fc, gprob, None, zeros=zeros)
-        g_w_ih, g_w_hh, g_b_ih, g_b_hh = (zeros[id(t)] for t in (w_ih, w_hh, b_ih, b_hh))
+        _, gfcin = ops.mlp_bwd(fc_acts, p.fc, gprob, None, zeros=zeros)
+        g_w_ih, g_w_hh, g_b_ih, g_b_hh = (zeros[id(t)] for t in (p.w_ih, p.w_hh, p.b_ih, p.b_hh))
         gseq = torch.empty_like(seq)
         if gi is None:
             # input gradient and the four parameter gradients straight out of the recurrence's backward
-            ops.gru_fused_bwd(seq, w_ih, b_ih, w_hh, b_hh, hbuf, batch, length, dim, gfcin[:, :dim], gseq, g_w_ih,
-                              g_b_ih, g_w_hh, g_b_hh)
+            ops.gru_fused_bwd(seq, p.w_ih, p.b_ih, p.w_hh, p.b_hh, hbuf, batch, length, dim, gfcin[:, :dim], gseq,
+                              g_w_ih, g_b_ih, g_w_hh, g_b_hh)
         else:
             dgi = torch.empty((batch * length, 3 * dim), dtype=torch.float32, device=dev)
             dgh = torch.empty((batch * (length + 1), 3 * dim), dtype=torch.float32, device=dev)
-            ops.gru_bwd(gi, w_hh, b_hh, hbuf, batch, length, dim, gfcin[:, :dim], dgi, dgh)
-            ops.linear_bwd(seq, w_ih, None, dgi, ACT_NONE, gseq, g_w_ih, g_b_ih)
+            ops.gru_bwd(gi, p.w_hh, p.b_hh, hbuf, batch, length, dim, gfcin[:, :dim], dgi, dgh)
+            ops.linear_bwd(seq, p.w_ih, None, dgi, ACT_NONE, gseq, g_w_ih, g_b_ih)
             # dW_hh = sum_{b,t} dgh_t (x) h_{t-1}: rows r+1 of dgh against rows r of hbuf; the
             # zero row at the head of every sample makes the pairs that straddle samples vanish
             rows = batch * (length + 1) - 1
             if rows > 0:
-                ops.linear_bwd(hbuf[:rows], w_hh, None, dgh[1:], ACT_NONE, None, g_w_hh, g_b_hh)
+                ops.linear_bwd(hbuf[:rows], p.w_hh, None, dgh[1:], ACT_NONE, None, g_w_hh, g_b_hh)
         gscore = torch.empty((batch * length, 1), dtype=torch.float32, device=dev)
         ops.din_pool_bwd(attn, c, batch, length, dim, gseq, False, gscore)
-        att_grads, gc = ops.mlp_bwd(att_acts, att, gscore, None, zeros=zeros)
-        gtable = zeros[id(table)]
-        ops.din_concat_bwd(hist, target, table.shape[0], dim, gc, attn, gseq, False, gfcin[:, dim:], gtable,
+        _, gc = ops.mlp_bwd(att_acts, att, gscore, None, zeros=zeros)
+        ops.din_concat_bwd(hist, target, table.shape[0], dim, gc, attn, gseq, False, gfcin[:, dim:], zeros[id(table)],
                            pair=True)
-        unfold_attention_grad(att_grads[0][0], zeros[id(w1)], dim)
-        att_grads[0] = (zeros[id(w1)], att_grads[0][1])
-        grads = [gtable]
-        for gw, gb in att_grads + fc_grads:
-            grads += [gw, gb]
-        grads += [g_w_ih, g_w_hh, g_b_ih, g_b_hh]
-        return grads
+        unfold_attention_grad(zeros[id(w1f)], zeros[id(w1)], dim)
 
     def recommendation(self, num_users, num_items, hist_list, k):
         return self._rank_histories(num_users, num_items, hist_list, k)

@@ -9,17 +9,20 @@ import torch.nn as nn
 from torch.nn.init import xavier_normal_
 
 from .. import ops
+from .._lib import FIELD_ID_I64
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
-from ._base import CtrModule, _ModelFunction
+from ._base import CtrModule, Params
 
 # the history gradient of the E-wide attention leaves the first layer's dX GEMM as atomics on the table gradient
 # (ctr_linear_dx_scatter); CTR_DIN_FUSED_SCATTER=0 keeps the two-pass form (dX to memory, seq_scatter) for A/B
 FUSED_SCATTER = os.environ.get("CTR_DIN_FUSED_SCATTER", "1") != "0"
 
 
-def attention_layers(p):
-    """(w0,b0,w2,b2,w4,b4) -> Linear+ReLU, Linear+ReLU, Linear"""
-    return [Layer(p[0], p[1], ACT_RELU), Layer(p[2], p[3], ACT_RELU), Layer(p[4], p[5], ACT_NONE)]
+def mlp_layers(seq, last_act):
+    """the three Linear of an ``nn.Sequential`` (Linear, ReLU, Linear, ReLU, Linear[, Sigmoid]) as Linear+ReLU,
+    Linear+ReLU, Linear+``last_act``"""
+    lin1, _, lin2, _, lin3, *_ = seq
+    return [Layer(lin.weight, lin.bias, act) for lin, act in ((lin1, ACT_RELU), (lin2, ACT_RELU), (lin3, last_act))]
 
 
 def fold_attention_weight(w1, dim):
@@ -33,32 +36,21 @@ def fold_attention_weight(w1, dim):
     return folded
 
 
+def folded_attention(att, dim, w1f=None):
+    """the attention stack on the [h, t] operand: its first layer carries the folded weight ``w1f`` (formed here
+    unless the forward's is handed in).  Returns (layers, w1f, the first layer's own weight)."""
+    first, *rest = att
+    if w1f is None:
+        w1f = fold_attention_weight(first.weight, dim)
+    return [Layer(w1f, first.bias, first.act)] + rest, w1f, first.weight
+
+
 def unfold_attention_grad(gfolded, gw1, dim):
     """chain rule of ``fold_attention_weight``: dWa = g1, dWb = g1 - g2, dWc = g2"""
     g1, g2 = gfolded[:, :dim], gfolded[:, dim:]
     gw1[:, :dim].copy_(g1)
     torch.sub(g1, g2, out=gw1[:, dim:2 * dim])
     gw1[:, 2 * dim:].copy_(g2)
-
-
-def _lib_field_id():
-    from .._lib import FIELD_ID_I64
-    return FIELD_ID_I64
-
-
-def fc_layers(p):
-    return [Layer(p[0], p[1], ACT_RELU), Layer(p[2], p[3], ACT_RELU), Layer(p[4], p[5], ACT_SIGMOID)]
-
-
-def _zero_grads(model, params):
-    """one flat zero buffer for the parameters' gradients; the exchanged rows of a sharded
-    table are an activation, not a replicated parameter: their gradient gets its own buffer
-    so that the data-parallel all-reduce of the flat one does not carry it"""
-    if not getattr(model, "sharded", False):
-        return ops.zero_grads(params)
-    zeros = ops.zero_grads(params[1:])
-    zeros[id(params[0])] = torch.zeros_like(params[0])
-    return zeros
 
 
 class SequenceModel(CtrModule):
@@ -74,11 +66,11 @@ class SequenceModel(CtrModule):
         from ..dist import ShardedEmbedding
         return ShardedEmbedding(num_items, embed_size, group=group)
 
-    def sparse_ids(self, inputs):
-        """sparse mode: the item table (position 0) is touched by every history id and the target ids"""
+    def sparse_ids(self, inputs, p):
+        """sparse mode: the item table is touched by every history id and the target ids"""
         if getattr(self, "sharded", False):
-            return {}
-        return {0: [] if inputs is None else [inputs[0].reshape(-1), inputs[1]]}
+            return []
+        return [(p.table, [] if inputs is None else [inputs[0].reshape(-1), inputs[1]])]
 
     def _lookup_sharded(self, table_module, hist, target):
         """rows of every (hist, target) id through the all-to-all exchange, then the model runs
@@ -93,14 +85,16 @@ class SequenceModel(CtrModule):
         pos = torch.arange(batch * (length + 1), device=hist.device, dtype=torch.int64)
         return rows, pos[:batch * length].view(batch, length), pos[batch * length:]
 
-    def _run_sequence(self, hist, target, params):
-        self._need_device(hist, target, params[0])
+    def _run_sequence(self, table_module, hist, target, p):
+        """``p.table`` is ``table_module``'s weight, or -- sharded -- the exchanged rows of this batch"""
+        self._need_device(hist, target, p.table)
+        exchanged = ()
+        if self.sharded:
+            p.table, hist, target = self._lookup_sharded(table_module, hist, target)
+            exchanged = ("table",)
         if hist.dim() != 2 or target.dim() != 1 or hist.shape[0] != target.shape[0]:
             raise ValueError(f"expected hist (B,L) and target (B,), got {tuple(hist.shape)} {tuple(target.shape)}")
-        object.__setattr__(self, "_flag", self._err_flag(hist.device))
-        out = _ModelFunction.apply(self, 2, hist.contiguous(), target.contiguous(), *params)
-        self._raise_if_bad_index()
-        return out
+        return self._run([hist, target], p, exchanged)
 
     def _rank_histories(self, num_users, num_items, hist_list, k, max_positions: int = 1 << 22):
         """reference recommendation() (model/din.py:55-66): every user's WHOLE history (any length) against every
@@ -144,19 +138,11 @@ class DIN(SequenceModel):
                                 nn.Linear(128, 1), nn.Sigmoid())
 
     def _params(self):
-        p = [self.item_embedding.weight]
-        for seq in (self.attention, self.fc):
-            for k in (0, 2, 4):
-                p += [seq[k].weight, seq[k].bias]
-        return p
+        return Params(table=self.item_embedding.weight, att=mlp_layers(self.attention, ACT_NONE),
+                      fc=mlp_layers(self.fc, ACT_SIGMOID))
 
     def forward(self, hist, target_item):
-        params = self._params()
-        if self.sharded:
-            self._need_device(hist, target_item, params[0])
-            rows, hist, target_item = self._lookup_sharded(self.item_embedding, hist, target_item)
-            params[0] = rows
-        return self._run_sequence(hist, target_item, params)
+        return self._run_sequence(self.item_embedding, hist, target_item, self._params())
 
     # ---- attention on the E-wide operand: W1 [h, h-t, t] + b1 = (Wa+Wb) h + u[b],  u[b] = (Wc-Wb) t_b + b1
     # (model/din.py:39-44).  The GEMM over all B*L positions contracts E columns instead of 3E (reference) or 2E
@@ -165,64 +151,60 @@ class DIN(SequenceModel):
     e_wide = True
 
     def _use_e_wide(self, hist, dim):
-        n1 = self.attention[0].weight.shape[0]
-        return (self.e_wide and dim >= 4 and dim <= 256 and (dim & (dim - 1)) == 0 and hist.shape[1] >= 32 and n1 <= 128
-                and self.attention[2].weight.shape[0] >= 4 and hist.numel() < 2 ** 32)
+        lin1, _, lin2, *_ = self.attention
+        return (self.e_wide and dim >= 4 and dim <= 256 and (dim & (dim - 1)) == 0 and hist.shape[1] >= 32
+                and lin1.out_features <= 128 and lin2.out_features >= 4 and hist.numel() < 2 ** 32)
 
-    def _forward_e_wide(self, hist, target, params):
-        table = params[0]
-        att, fc = attention_layers(params[1:7]), fc_layers(params[7:13])
+    def _forward_e_wide(self, hist, target, p):
+        table, (att1, att2, att3) = p.table, p.att
         batch, length = hist.shape
         dim, dev = table.shape[1], table.device
-        w1 = att[0].weight
+        w1 = att1.weight
         wf = torch.empty((2, w1.shape[0], dim), dtype=torch.float32, device=dev)
         torch.add(w1[:, :dim], w1[:, dim:2 * dim], out=wf[0])        # Wh = Wa + Wb
         torch.sub(w1[:, 2 * dim:], w1[:, dim:2 * dim], out=wf[1])    # Wu = Wc - Wb
         hrows = torch.empty((batch * length, dim), dtype=torch.float32, device=dev)
         fcin = torch.empty((batch, 2 * dim), dtype=torch.float32, device=dev)
         ops.din_concat_fwd(table, hist, target, hrows, fcin[:, dim:], self._flag, h_only=True)
-        u = ops.linear_fwd(fcin[:, dim:], wf[1], att[0].bias)                       # (B, n1)
+        u = ops.linear_fwd(fcin[:, dim:], wf[1], att1.bias)                       # (B, n1)
         # the ReLU sign bits of z1 travel to the backward as 1 bit per element when the width allows whole words
         n1 = w1.shape[0]
         bits = torch.empty((batch * length, n1 // 32), dtype=torch.int32, device=dev) if n1 % 32 == 0 else None
         z1 = ops.linear_group_fwd(hrows, wf[0], None, u, length, ACT_RELU, sign_bits=bits)   # (B*L, n1)
-        if att[1].weight.shape[0] <= 128 and att[2].weight.shape[0] == 1 and att[2].act == ACT_NONE:
+        if att2.weight.shape[0] <= 128 and att3.weight.shape[0] == 1 and att3.act == ACT_NONE:
             # the score layer rides in layer 2's epilogue (its rows are whole in a workgroup)
-            h2, score = ops.linear_fwd_dot(z1, att[1].weight, att[1].bias, ACT_RELU, att[2].weight, att[2].bias)
+            h2, score = ops.linear_fwd_dot(z1, att2.weight, att2.bias, ACT_RELU, att3.weight, att3.bias)
         else:
-            h2 = ops.linear_fwd(z1, att[1].weight, att[1].bias, ACT_RELU)
-            score = ops.linear_fwd(h2, att[2].weight, att[2].bias, ACT_NONE)
+            h2 = ops.linear_fwd(z1, att2.weight, att2.bias, ACT_RELU)
+            score = ops.linear_fwd(h2, att3.weight, att3.bias, ACT_NONE)
         attn = torch.empty((batch, length), dtype=torch.float32, device=dev)
         ops.din_pool_fwd(score, hrows, batch, length, dim, attn, fcin[:, :dim], summed=True)
-        fc_acts = ops.mlp_fwd(fcin, fc)
+        fc_acts = ops.mlp_fwd(fcin, p.fc)
         return fc_acts[-1], ("e", hrows, z1, h2, attn, fc_acts, wf, bits, [False])
 
-    def _backward_e_wide(self, state, hist, target, params, gprob):
+    def _backward_e_wide(self, state, hist, target, p, gprob, zeros):
         _, hrows, z1, h2, attn, fc_acts, wf, bits, spent = state
         if spent[0]:
             raise RuntimeError("DIN backward overwrites its saved activations: run the forward again before a second "
                                "backward (retain_graph is not supported)")
         spent[0] = True
-        table = params[0]
-        att, fc = attention_layers(params[1:7]), fc_layers(params[7:13])
-        w1, b1 = att[0].weight, att[0].bias
+        table, (att1, att2, att3) = p.table, p.att
+        w1, b1 = att1.weight, att1.bias
         batch, length = hist.shape
         dim, dev = table.shape[1], table.device
         n1 = w1.shape[0]
         fcin = fc_acts[0]
-        zeros = _zero_grads(self, params)
-        fc_grads, gfcin = ops.mlp_bwd(fc_acts, fc, gprob, None, zeros=zeros)
+        _, gfcin = ops.mlp_bwd(fc_acts, p.fc, gprob, None, zeros=zeros)
         gscore = torch.empty((batch * length, 1), dtype=torch.float32, device=dev)
         ops.din_pool_bwd(attn, hrows, batch, length, dim, gfcin[:, :dim], True, gscore)
         # layer 3 (n2 -> 1) with layer 2's ReLU derivative folded in: h2 is overwritten by the pre-activation
         # gradient of layer 2, so neither layer-2 kernel below reads an activation to mask with
         gz2 = h2
-        ops.linear_n1_bwd_masked(h2, att[2].weight, gscore, ACT_RELU, gz2, zeros[id(att[2].weight)],
-                                 zeros[id(att[2].bias)])
-        ops.linear_bwd(z1, att[1].weight, None, gz2, ACT_NONE, None, zeros[id(att[1].weight)], zeros[id(att[1].bias)])
+        ops.linear_n1_bwd_masked(h2, att3.weight, gscore, ACT_RELU, gz2, zeros[id(att3.weight)], zeros[id(att3.bias)])
+        ops.linear_bwd(z1, att2.weight, None, gz2, ACT_NONE, None, zeros[id(att2.weight)], zeros[id(att2.bias)])
         gz1 = torch.empty_like(z1)
         gu = torch.zeros((batch, n1), dtype=torch.float32, device=dev)
-        ops.linear_dx_masked(att[1].weight, None, gz2, ACT_NONE, z1, ACT_RELU, gz1, gu, length, sign_bits=bits)
+        ops.linear_dx_masked(att2.weight, None, gz2, ACT_NONE, z1, ACT_RELU, gz1, gu, length, sign_bits=bits)
         # layer 1 on the E-wide operand (gz1 already carries relu'(z1))
         gwf = torch.zeros_like(wf)
         gtable = zeros[id(table)]
@@ -244,62 +226,46 @@ class DIN(SequenceModel):
         gw1[:, 2 * dim:].copy_(gwf[1])
         if not fused_scatter:
             ops.din_scatter_bwd(hist, table.shape[0], dim, ghrows, attn, gfcin[:, :dim], True, gtable)
-        ops.embed_bwd([ops.FieldSpec(_lib_field_id(), dim, dim, table=table, idx=target)], None, batch, gfcin,
+        ops.embed_bwd([ops.FieldSpec(FIELD_ID_I64, dim, dim, table=table, idx=target)], None, batch, gfcin,
                       {id(table): gtable})
-        grads = [gtable]
-        for layer in att:
-            grads += [zeros[id(layer.weight)], zeros[id(layer.bias)]]
-        for gw, gb in fc_grads:
-            grads += [gw, gb]
-        return grads
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         hist, target = inputs
-        table = params[0]
+        table = p.table
         if self._use_e_wide(hist, table.shape[1]):
-            return self._forward_e_wide(hist, target, params)
-        att, fc = attention_layers(params[1:7]), fc_layers(params[7:13])
+            return self._forward_e_wide(hist, target, p)
         batch, length = hist.shape
         dim = table.shape[1]
         dev = table.device
-        w1f = fold_attention_weight(att[0].weight, dim)
-        att[0] = Layer(w1f, att[0].bias, att[0].act)
+        att, w1f, _ = folded_attention(p.att, dim)
         c = torch.empty((batch * length, 2 * dim), dtype=torch.float32, device=dev)
         fcin = torch.empty((batch, 2 * dim), dtype=torch.float32, device=dev)
         ops.din_concat_fwd(table, hist, target, c, fcin[:, dim:], self._flag, pair=True)
         att_acts = ops.mlp_fwd(c, att)
         attn = torch.empty((batch, length), dtype=torch.float32, device=dev)
         ops.din_pool_fwd(att_acts[-1], c, batch, length, dim, attn, fcin[:, :dim], summed=True)
-        fc_acts = ops.mlp_fwd(fcin, fc)
+        fc_acts = ops.mlp_fwd(fcin, p.fc)
         return fc_acts[-1], (att_acts, attn, fc_acts, w1f)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         hist, target = inputs
         if state[0] == "e":
-            return self._backward_e_wide(state, hist, target, params, gprob)
+            self._backward_e_wide(state, hist, target, p, gprob, zeros)
+            return
         att_acts, attn, fc_acts, w1f = state
-        table = params[0]
-        att, fc = attention_layers(params[1:7]), fc_layers(params[7:13])
-        w1 = att[0].weight
-        att[0] = Layer(w1f, att[0].bias, att[0].act)
+        table = p.table
         batch, length = hist.shape
         dim = table.shape[1]
         c, fcin = att_acts[0], fc_acts[0]
-        zeros = _zero_grads(self, params)
+        att, _, w1 = folded_attention(p.att, dim, w1f)
         zeros[id(w1f)] = torch.zeros_like(w1f)
-        fc_grads, gfcin = ops.mlp_bwd(fc_acts, fc, gprob, None, zeros=zeros)
+        _, gfcin = ops.mlp_bwd(fc_acts, p.fc, gprob, None, zeros=zeros)
         gscore = torch.empty((batch * length, 1), dtype=torch.float32, device=table.device)
         ops.din_pool_bwd(attn, c, batch, length, dim, gfcin[:, :dim], True, gscore)
-        att_grads, gc = ops.mlp_bwd(att_acts, att, gscore, None, zeros=zeros)
-        gtable = zeros[id(table)]
-        ops.din_concat_bwd(hist, target, table.shape[0], dim, gc, attn, gfcin[:, :dim], True, gfcin[:, dim:], gtable,
-                           pair=True)
-        unfold_attention_grad(att_grads[0][0], zeros[id(w1)], dim)
-        att_grads[0] = (zeros[id(w1)], att_grads[0][1])
-        grads = [gtable]
-        for gw, gb in att_grads + fc_grads:
-            grads += [gw, gb]
-        return grads
+        _, gc = ops.mlp_bwd(att_acts, att, gscore, None, zeros=zeros)
+        ops.din_concat_bwd(hist, target, table.shape[0], dim, gc, attn, gfcin[:, :dim], True, gfcin[:, dim:],
+                           zeros[id(table)], pair=True)
+        unfold_attention_grad(zeros[id(w1f)], zeros[id(w1)], dim)
 
     def recommendation(self, num_users, num_items, hist_list, k):
         return self._rank_histories(num_users, num_items, hist_list, k)

@@ -14,7 +14,7 @@ from torch.nn.init import xavier_normal_
 from .. import ops
 from ..ops import FieldSpec
 from .._lib import FIELD_ID_I64
-from ._base import CtrModule, _ModelFunction
+from ._base import CtrModule, Params
 
 
 class EmbeddingStage(CtrModule):
@@ -30,34 +30,26 @@ class EmbeddingStage(CtrModule):
 
     def _specs(self, idx, tables):
         f, e = self.num_fields, self.dim
-        return [FieldSpec(FIELD_ID_I64, e, k * e, table=tables[k], idx=idx[:, k], idx_stride=f) for k in range(f)]
+        return [FieldSpec(FIELD_ID_I64, e, k * e, table=t, idx=idx[:, k], idx_stride=f) for k, t in enumerate(tables)]
 
-    def _node_params(self):
-        return list(self.tables)
+    def _params(self):
+        return Params(tables=list(self.tables))
 
-    def sparse_ids(self, inputs):
-        if inputs is None:
-            return {k: [] for k in range(self.num_fields)}
-        return {k: [inputs[0][:, k]] for k in range(self.num_fields)}
+    def sparse_ids(self, inputs, p):
+        return [(t, [] if inputs is None else [inputs[0][:, k]]) for k, t in enumerate(p.tables)]
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (idx,) = inputs
-        out = torch.empty((idx.shape[0], self.num_fields * self.dim), dtype=torch.float32, device=params[0].device)
-        ops.embed_fwd(self._specs(idx, params), None, idx.shape[0], out, self._flag)
+        out = torch.empty((idx.shape[0], self.num_fields * self.dim), dtype=torch.float32, device=idx.device)
+        ops.embed_fwd(self._specs(idx, p.tables), None, idx.shape[0], out, self._flag)
         return out, None
 
-    def run_backward(self, state, inputs, params, gout):
+    def run_backward(self, state, inputs, p, gout, zeros):
         (idx,) = inputs
-        zeros = ops.zero_grads(list(params))
-        ops.embed_bwd(self._specs(idx, params), None, idx.shape[0], gout, zeros)
-        return [zeros[id(p)] for p in params]
+        ops.embed_bwd(self._specs(idx, p.tables), None, idx.shape[0], gout, zeros)
 
     def forward(self, idx: torch.Tensor) -> torch.Tensor:
-        params = list(self.tables)
-        self._need_device(idx, params[0])
+        self._need_device(idx, *self.tables)
         if idx.dim() != 2 or idx.shape[1] != self.num_fields or idx.dtype != torch.int64:
             raise ValueError(f"expected a (B,{self.num_fields}) int64 index matrix, got {tuple(idx.shape)} {idx.dtype}")
-        object.__setattr__(self, "_flag", self._err_flag(idx.device))
-        out = _ModelFunction.apply(self, 1, idx.contiguous(), *params)
-        self._raise_if_bad_index()
-        return out
+        return self._run([idx], self._params())

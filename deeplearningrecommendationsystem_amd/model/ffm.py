@@ -8,7 +8,7 @@ from torch.nn.init import xavier_normal_
 from .. import ops
 from ..ops import FieldSpec
 from .._lib import FIELD_BAG, FIELD_ID_F32, FIELD_ID_I64
-from ._base import FeatureModel
+from ._base import FeatureModel, Params
 
 # the 12 field-aware vectors in buffer order, and the reference's 15 dot products
 # (model/ffm.py:62-80) as index pairs into that order
@@ -59,28 +59,29 @@ class FFM(FeatureModel):
     fused_forward = True   # False: the two-launch forward of round 1 (embed_fwd + ffm_head_fwd), kept for A/B
 
     def _params(self):
-        return [getattr(self, n).weight for n in VECTORS] + [self.user.weight, self.item.weight,
-                                                              self.linear.weight, self.linear.bias]
+        """the twelve tables under their ``VECTORS`` names, then the first-order part"""
+        return Params(**{name: getattr(self, name).weight for name in VECTORS}, user1=self.user.weight,
+                      item1=self.item.weight, lin_w=self.linear.weight, lin_b=self.linear.bias)
 
     def forward(self, feature_vector):
-        params = self._params()
-        if self.sharded:
-            # rows of this batch through the exchange; the kernels then see each of them as a
-            # (B, k) table indexed 0..B-1, and its gradient flows back through the exchange
-            self._need_device(feature_vector, params[12])
-            uid, iid = feature_vector[:, 0].long(), feature_vector[:, 1].long()
-            # every table's rows are requested first and waited for afterwards: table k+1's all-to-all runs on the
-            # collective stream while table k's rows are put back into batch order.  The ids are a temporary of the
-            # feature matrix: its identity / version key the exchange plan, which the two field-aware tables of an id
-            # column share (one id exchange per column)
-            flights = {}
-            for k, name in enumerate(VECTORS):
-                if name in SHARDED:
-                    user = name.startswith("userid")
-                    flights[k] = getattr(self, name).start(uid if user else iid, plan_key=(feature_vector, 0 if user else 1))
-            for k, flight in flights.items():
-                params[k] = flight.wait()
-        return self._run_model(feature_vector, params)
+        p = self._params()
+        if not self.sharded:
+            return self._run_model(feature_vector, p)
+        # rows of this batch through the exchange; the kernels then see each of them as a
+        # (B, k) table indexed 0..B-1, and its gradient flows back through the exchange
+        self._need_device(feature_vector, p.user1)
+        uid, iid = feature_vector[:, 0].long(), feature_vector[:, 1].long()
+        # every table's rows are requested first and waited for afterwards: table k+1's all-to-all runs on the
+        # collective stream while table k's rows are put back into batch order.  The ids are a temporary of the
+        # feature matrix: its identity / version key the exchange plan, which the two field-aware tables of an id
+        # column share (one id exchange per column)
+        flights = {}
+        for name in SHARDED:
+            user = name.startswith("userid")
+            flights[name] = getattr(self, name).start(uid if user else iid, plan_key=(feature_vector, 0 if user else 1))
+        for name, flight in flights.items():
+            setattr(p, name, flight.wait())
+        return self._run_model(feature_vector, p, exchanged=SHARDED)
 
     def _specs(self, tables, dim):
         specs = []
@@ -93,45 +94,33 @@ class FFM(FeatureModel):
                 specs.append(FieldSpec(kind, dim, k * dim, table=table, src_col=col, bag_size=bag))
         return specs
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        tables, (user1, item1, lin_w, lin_b) = params[:12], params[12:16]
-        batch, dim = x.shape[0], tables[0].shape[1]
+        tables = [getattr(p, name) for name in VECTORS]
+        batch, dim = x.shape[0], self.age_user.embedding_dim
         emb = torch.empty((batch, 12 * dim), dtype=torch.float32, device=x.device)
         prob = torch.empty((batch, 1), dtype=torch.float32, device=x.device)
         if self.fused_forward and not self.sharded and dim in (8, 16, 32, 64):
             # gather, bags, the 15 dots and the head in one launch (csrc/ffm_fused.hip)
-            ops.ffm_fused_fwd(x, tables, user1, item1, lin_w, lin_b, emb, prob, self._flag)
+            ops.ffm_fused_fwd(x, tables, p.user1, p.item1, p.lin_w, p.lin_b, emb, prob, self._flag)
             return prob, (emb, prob)
         ops.embed_fwd(self._specs(tables, dim), x, batch, emb, self._flag)
-        ops.ffm_head_fwd(emb, 12, dim, PAIRS, x, user1, item1, lin_w, lin_b, prob, self._flag)
+        ops.ffm_head_fwd(emb, 12, dim, PAIRS, x, p.user1, p.item1, p.lin_w, p.lin_b, prob, self._flag)
         return prob, (emb, prob)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         emb, prob = state
-        tables, (user1, item1, lin_w, lin_b) = params[:12], params[12:16]
-        batch, dim = x.shape[0], tables[0].shape[1]
+        batch, dim = x.shape[0], self.age_user.embedding_dim
         gemb = torch.empty_like(emb)
-        if self.sharded:
-            # exchanged rows are activations: their gradients stay out of the flat buffer that the
-            # data-parallel all-reduce works on
-            rows = [k for k, name in enumerate(VECTORS) if name in SHARDED]
-            zeros = ops.zero_grads([p for k, p in enumerate(params) if k not in rows])
-            for k in rows:
-                zeros[id(params[k])] = torch.zeros_like(params[k])
-        else:
-            zeros = ops.zero_grads(params)
-        g_user1, g_item1, g_w, g_b = (zeros[id(t)] for t in (user1, item1, lin_w, lin_b))
+        g_user1, g_item1, g_w, g_b = (zeros[id(t)] for t in (p.user1, p.item1, p.lin_w, p.lin_b))
         if self.fused_forward and not self.sharded and dim in (8, 16, 32, 64):
-            ops.ffm_fused_bwd(x, emb, user1.shape[0], item1.shape[0], lin_w, prob, gprob.view(batch, 1), g_user1, g_item1,
-                              g_w, g_b, gemb)
+            ops.ffm_fused_bwd(x, emb, p.user1.shape[0], p.item1.shape[0], p.lin_w, prob, gprob.view(batch, 1), g_user1,
+                              g_item1, g_w, g_b, gemb)
         else:
-            ops.ffm_head_bwd(emb, 12, dim, PAIRS, x, user1, item1, lin_w, lin_b, prob, gprob.view(batch, 1),
+            ops.ffm_head_bwd(emb, 12, dim, PAIRS, x, p.user1, p.item1, p.lin_w, p.lin_b, prob, gprob.view(batch, 1),
                              g_user1, g_item1, g_w, g_b, gemb)
-        tgrads = zeros
-        ops.embed_bwd(self._specs(tables, dim), x, batch, gemb, tgrads)
-        return [tgrads[id(t)] for t in tables] + [g_user1, g_item1, g_w, g_b]
+        ops.embed_bwd(self._specs([getattr(p, name) for name in VECTORS], dim), x, batch, gemb, zeros)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)

@@ -7,7 +7,7 @@ from torch.nn.init import xavier_normal_
 
 from .. import ops
 from ..ops import ACT_SIGMOID
-from ._base import FeatureModel
+from ._base import FeatureModel, Params
 
 
 class LogisticRegression(FeatureModel):
@@ -24,7 +24,7 @@ class LogisticRegression(FeatureModel):
         xavier_normal_(self.item.weight.data)
 
     def _params(self):
-        return [self.user.weight, self.item.weight, self.linear.weight, self.linear.bias]
+        return Params(user1=self.user.weight, item1=self.item.weight, w=self.linear.weight, b=self.linear.bias)
 
     def forward(self, feature_vector):
         return self._run_model(feature_vector, self._params())
@@ -33,26 +33,22 @@ class LogisticRegression(FeatureModel):
     def _unit(device):
         return torch.ones((1, 1), dtype=torch.float32, device=device)
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        user1, item1, w, b = params
         batch, dev = x.shape[0], x.device
         none = torch.zeros((batch, 4), dtype=torch.float32, device=dev)   # the "FM vectors": one zero vector
         logit = torch.empty((batch, 1), dtype=torch.float32, device=dev)
-        ops.fm_wide_fwd(none, 1, 4, x, user1, item1, w, b, logit, self._flag)
+        ops.fm_wide_fwd(none, 1, 4, x, p.user1, p.item1, p.w, p.b, logit, self._flag)
         prob = ops.linear_fwd(logit, self._unit(dev), None, ACT_SIGMOID)   # sigmoid(1 * logit)
         return prob, (none, logit, prob)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         none, logit, prob = state
-        user1, item1, w, b = params
-        zeros = ops.zero_grads(params)
         glogit = torch.empty_like(logit)
         ops.linear_bwd(logit, self._unit(x.device), prob, gprob, ACT_SIGMOID, glogit, None, None)
-        ops.fm_wide_bwd(none, 1, 4, x, user1, item1, w, b, glogit, zeros[id(user1)], zeros[id(item1)],
-                        zeros[id(w)], zeros[id(b)], None, accumulate=False)
-        return [zeros[id(p)] for p in params]
+        ops.fm_wide_bwd(none, 1, 4, x, p.user1, p.item1, p.w, p.b, glogit, zeros[id(p.user1)], zeros[id(p.item1)],
+                        zeros[id(p.w)], zeros[id(p.b)], None, accumulate=False)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)

@@ -7,7 +7,7 @@ from torch.nn.init import xavier_normal_
 
 from .. import ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
-from ._base import FeatureModel
+from ._base import FeatureModel, Params
 from .deepfm import FieldsInput, field_vocabs, six_field_specs
 from .._lib import FIELD_ID_I64
 
@@ -80,57 +80,46 @@ class PNN(FeatureModel):
             self.register_buffer("_sum_selector", torch.eye(embed_dim).repeat(1, 6), persistent=False)
 
     def _params(self):
+        """``dnn`` then ``out`` is the stack on top of the product layer"""
         if self.num_fields is not None:
-            p = [e.weight for e in self.embeddings]
+            tables = [e.weight for e in self.embeddings]
         else:
-            p = [e.weight for e in (self.user_embed, self.item_embed, self.age_embed, self.gender_embed,
-                                    self.occupation_embed, self.movie_embed)]
-        p += [self.product.linear1.weight, self.product.linear1.bias, self.product.linear2.weight,
-              self.product.linear2.bias, self.output.weight, self.output.bias]
-        for lin in self.dnn.dnn_network:
-            p += [lin.weight, lin.bias]
-        return p
+            tables = [e.weight for e in (self.user_embed, self.item_embed, self.age_embed, self.gender_embed,
+                                         self.occupation_embed, self.movie_embed)]
+        return Params(tables=tables, w1=self.product.linear1.weight, b1=self.product.linear1.bias,
+                      w2=self.product.linear2.weight, b2=self.product.linear2.bias,
+                      out=Layer(self.output.weight, self.output.bias, ACT_SIGMOID),
+                      dnn=[Layer(lin.weight, lin.bias, ACT_RELU) for lin in self.dnn.dnn_network])
 
-    def sparse_ids(self, inputs):
-        if self.num_fields is not None:
-            return {f: ([] if inputs is None else [inputs[0][:, f]]) for f in range(self.num_fields)}
-        return {c: ([] if inputs is None else [inputs[0][:, c]]) for c in (0, 1)}
+    def sparse_ids(self, inputs, p):
+        """sparse mode: every table of the N-field form, the user and item tables of the six-field one"""
+        ids = len(p.tables) if self.num_fields is not None else 2
+        return [(t, [] if inputs is None else [inputs[0][:, c]]) for c, t in zip(range(ids), p.tables)]
 
     def forward(self, x):
         if self.num_fields is not None:
-            return self._run_fields(FieldsInput.ids(x, self.num_fields), self._params())
+            return self._run([FieldsInput.ids(x, self.num_fields)], self._params())
         return self._run_model(x, self._params())
-
-    def _nvec(self):
-        return 6 if self.num_fields is None else self.num_fields
-
-    def _tail(self, params):
-        n = self._nvec()
-        layers = [Layer(params[n + 6 + 2 * k], params[n + 7 + 2 * k], ACT_RELU) for k in range(len(self.dnn.dnn_network))]
-        return layers + [Layer(params[n + 4], params[n + 5], ACT_SIGMOID)]
 
     def _specs(self, x, tables, dim):
         """the embedding stage's field list: the reference's six fields out of the (B,45) matrix, or F id columns"""
         if self.num_fields is None:
             return six_field_specs(tables, dim), x
-        nf = self.num_fields
-        return [ops.FieldSpec(FIELD_ID_I64, dim, f * dim, table=tables[f], idx=x[:, f], idx_stride=x.stride(0))
-                for f in range(nf)], None
+        return [ops.FieldSpec(FIELD_ID_I64, dim, f * dim, table=table, idx=x[:, f], idx_stride=x.stride(0))
+                for f, table in enumerate(tables)], None
 
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        n = self._nvec()
+        n = len(p.tables)
         npairs = n * (n - 1) // 2
-        tables = params[:n]
-        w1, b1, w2, b2 = params[n:n + 4]
-        batch, dim = x.shape[0], tables[0].shape[1]
+        batch, dim = x.shape[0], self.product.linear1.in_features // n
         emb = torch.empty((batch, n * dim), dtype=torch.float32, device=x.device)
-        specs, xin = self._specs(x, tables, dim)
+        specs, xin = self._specs(x, p.tables, dim)
         ops.embed_fwd(specs, xin, batch, emb, self._flag)
         if self.product.model == "in":
             prod = ops.allpairs_fwd(emb, n, dim, out=self._padded_rows(batch, npairs, x.device))
-            lz = ops.linear_fwd(emb, w1, b1)
-            h0 = ops.linear_fwd(prod, self._aligned_weight(w2), b2, residual=lz)
+            lz = ops.linear_fwd(emb, p.w1, p.b1)
+            h0 = ops.linear_fwd(prod, self._aligned_weight(p.w2), p.b2, residual=lz)
             extra = (prod,)
         else:
             if batch != dim:
@@ -139,45 +128,36 @@ class PNN(FeatureModel):
             s = ops.linear_fwd(emb, self._sum_selector, None)                       # (B,E) = sum_f v_f
             prod = torch.zeros((dim, dim), dtype=torch.float32, device=x.device)
             ops.linear_bwd(s, prod, None, s, ACT_NONE, None, prod, None)           # p = S^T S
-            lp = ops.linear_fwd(prod, w2, b2)                                       # (E,H0)
-            h0 = ops.linear_fwd(emb, w1, b1, residual=lp)
+            lp = ops.linear_fwd(prod, p.w2, p.b2)                                   # (E,H0)
+            h0 = ops.linear_fwd(emb, p.w1, p.b1, residual=lp)
             extra = (prod, s)
-        acts = ops.mlp_fwd(h0, self._tail(params))
+        acts = ops.mlp_fwd(h0, p.dnn + [p.out])
         return acts[-1].view(-1, 1), (emb, acts, extra)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         emb, acts, extra = state
-        n = self._nvec()
+        n = len(p.tables)
         npairs = n * (n - 1) // 2
-        tables = params[:n]
-        w1, b1, w2, b2 = params[n:n + 4]
-        batch, dim = x.shape[0], tables[0].shape[1]
-        tail = self._tail(params)
-        zeros = ops.zero_grads(params)
-        tail_grads, gh0 = ops.mlp_bwd(acts, tail, gprob.view(batch, 1), None, zeros=zeros)
-        gw1, gb1, gw2, gb2 = (zeros[id(t)] for t in (w1, b1, w2, b2))
+        batch, dim = x.shape[0], emb.shape[1] // n
+        _, gh0 = ops.mlp_bwd(acts, p.dnn + [p.out], gprob.view(batch, 1), None, zeros=zeros)
+        gw1, gb1, gw2, gb2 = (zeros[id(t)] for t in (p.w1, p.b1, p.w2, p.b2))
         gemb = torch.empty_like(emb)
-        ops.linear_bwd(emb, w1, None, gh0, ACT_NONE, gemb, gw1, gb1)
+        ops.linear_bwd(emb, p.w1, None, gh0, ACT_NONE, gemb, gw1, gb1)
         if self.product.model == "in":
             (prod,) = extra
             gprod = self._padded_rows(batch, npairs, x.device)
-            ops.linear_bwd(prod, self._aligned_weight(w2, refresh=False), None, gh0, ACT_NONE, gprod, gw2, gb2)
+            ops.linear_bwd(prod, self._aligned_weight(p.w2, refresh=False), None, gh0, ACT_NONE, gprod, gw2, gb2)
             ops.allpairs_bwd(emb, n, dim, gprod, gemb, accumulate=True)
         else:
             prod, s = extra
             gprod = torch.empty_like(prod)
-            ops.linear_bwd(prod, w2, None, gh0, ACT_NONE, gprod, gw2, gb2)          # glp = gh0 as (E,H0)
+            ops.linear_bwd(prod, p.w2, None, gh0, ACT_NONE, gprod, gw2, gb2)        # glp = gh0 as (E,H0)
             gs = ops.linear_fwd(s, gprod, None)                                     # S gp^T
             ops.linear_bwd(s, gprod, None, s, ACT_NONE, gs, None, None, accumulate_gx=True)   # += S gp
             ops.linear_bwd(emb, self._sum_selector, None, gs, ACT_NONE, gemb, None, None, accumulate_gx=True)
-        tgrads = zeros
-        specs, xin = self._specs(x, tables, dim)
-        ops.embed_bwd(specs, xin, batch, gemb, tgrads)
-        grads = [tgrads[id(t)] for t in tables] + [gw1, gb1, gw2, gb2, tail_grads[-1][0], tail_grads[-1][1]]
-        for gw, gb in tail_grads[:-1]:
-            grads += [gw, gb]
-        return grads
+        specs, xin = self._specs(x, p.tables, dim)
+        ops.embed_bwd(specs, xin, batch, gemb, zeros)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)

@@ -6,8 +6,8 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import ops
-from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID
-from ._base import FeatureModel
+from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
+from ._base import FeatureModel, Params
 from .deepcrossing import DeepCrossing
 
 
@@ -38,64 +38,50 @@ class WideDeep(FeatureModel):
             xavier_normal_(emb.weight.data)
 
     def _params(self):
-        p = [e.weight for e in (self.user_embedding, self.item_embedding, self.gender_embedding,
-                                self.occupation_embedding, self.movie_embedding)]
-        p += [self.user.weight, self.item.weight, self.wide.weight, self.wide.bias,
-              self.output.weight, self.output.bias, self.linear.weight, self.linear.bias]
-        for lin in self.dnn_network:
-            p += [lin.weight, lin.bias]
-        return p
+        """``deep``: ``linear`` without activation, then Linear+ReLU"""
+        return Params(tables=[e.weight for e in (self.user_embedding, self.item_embedding, self.gender_embedding,
+                                                 self.occupation_embedding, self.movie_embedding)],
+                      user1=self.user.weight, item1=self.item.weight, wide_w=self.wide.weight, wide_b=self.wide.bias,
+                      out_w=self.output.weight, out_b=self.output.bias,
+                      deep=[Layer(self.linear.weight, self.linear.bias, ACT_NONE)]
+                      + [Layer(lin.weight, lin.bias, ACT_RELU) for lin in self.dnn_network])
 
     def forward(self, x):
         return self._run_model(x, self._params())
 
-    def _deep(self, params):
-        """[(weight, bias, act)]: ``linear`` without activation, then Linear+ReLU"""
-        layers = [(params[11], params[12], ACT_NONE)]
-        for k in range(len(self.dnn_network)):
-            layers.append((params[13 + 2 * k], params[14 + 2 * k], ACT_RELU))
-        return layers
-
-    def run_forward(self, inputs, params):
+    def run_forward(self, inputs, p):
         (x,) = inputs
-        tables = params[:5]
-        user1, item1, wide_w, wide_b, out_w, out_b = params[5:11]
-        batch, e = x.shape[0], tables[0].shape[1]
+        batch, e = x.shape[0], self.user_embedding.embedding_dim
         d, dev = 5 * e + 1, x.device
         stack = self._padded_rows(batch, d, dev)
-        ops.embed_fwd(DeepCrossing._specs(tables, e), x, batch, stack, self._flag)
-        deep = self._deep(params)
-        comb = torch.empty((batch, 1 + deep[-1][0].shape[0]), dtype=torch.float32, device=dev)
+        ops.embed_fwd(DeepCrossing._specs(p.tables, e), x, batch, stack, self._flag)
+        *_, last = p.deep
+        comb = torch.empty((batch, 1 + last.weight.shape[0]), dtype=torch.float32, device=dev)
         hs = [stack]
-        for k, (w, b, act) in enumerate(deep):
-            out = comb[:, 1:] if k == len(deep) - 1 else None
-            hs.append(ops.linear_fwd(hs[-1], self._aligned_weight(w) if k == 0 else w, b, act, out=out))
-        ops.fm_wide_fwd(stack[:, :e], 1, e, x, user1, item1, wide_w, wide_b, comb[:, 0:1], self._flag)
-        prob = ops.linear_fwd(comb, out_w, out_b, ACT_SIGMOID)
+        for k, layer in enumerate(p.deep):
+            out = comb[:, 1:] if k == len(p.deep) - 1 else None
+            w = self._aligned_weight(layer.weight) if k == 0 else layer.weight
+            hs.append(ops.linear_fwd(hs[-1], w, layer.bias, layer.act, out=out))
+        ops.fm_wide_fwd(stack[:, :e], 1, e, x, p.user1, p.item1, p.wide_w, p.wide_b, comb[:, 0:1], self._flag)
+        prob = ops.linear_fwd(comb, p.out_w, p.out_b, ACT_SIGMOID)
         return prob, (hs, comb, prob)
 
-    def run_backward(self, state, inputs, params, gprob):
+    def run_backward(self, state, inputs, p, gprob, zeros):
         (x,) = inputs
         hs, comb, prob = state
-        tables = params[:5]
-        user1, item1, wide_w, wide_b, out_w, out_b = params[5:11]
-        batch, e = x.shape[0], tables[0].shape[1]
+        batch, e = x.shape[0], self.user_embedding.embedding_dim
         dev = x.device
-        deep = self._deep(params)
-        zeros = ops.zero_grads(params)
         gcomb = torch.empty_like(comb)
-        ops.linear_bwd(comb, out_w, prob, gprob, ACT_SIGMOID, gcomb, zeros[id(out_w)], zeros[id(out_b)])
+        ops.linear_bwd(comb, p.out_w, prob, gprob, ACT_SIGMOID, gcomb, zeros[id(p.out_w)], zeros[id(p.out_b)])
         gh = gcomb[:, 1:]
-        for k in range(len(deep) - 1, -1, -1):
-            w, b, act = deep[k]
+        for k, layer in reversed(list(enumerate(p.deep))):
             gin = self._padded_rows(batch, hs[k].shape[1], dev)
-            ops.linear_bwd(hs[k], self._aligned_weight(w, refresh=False) if k == 0 else w, hs[k + 1], gh, act, gin,
-                           zeros[id(w)], zeros[id(b)])
+            w = self._aligned_weight(layer.weight, refresh=False) if k == 0 else layer.weight
+            ops.linear_bwd(hs[k], w, hs[k + 1], gh, layer.act, gin, zeros[id(layer.weight)], zeros[id(layer.bias)])
             gh = gin
-        ops.fm_wide_bwd(hs[0][:, :e], 1, e, x, user1, item1, wide_w, wide_b, gcomb[:, 0:1], zeros[id(user1)],
-                        zeros[id(item1)], zeros[id(wide_w)], zeros[id(wide_b)], None, accumulate=False)
-        ops.embed_bwd(DeepCrossing._specs(tables, e), x, batch, gh, zeros)
-        return [zeros[id(p)] for p in params]
+        ops.fm_wide_bwd(hs[0][:, :e], 1, e, x, p.user1, p.item1, p.wide_w, p.wide_b, gcomb[:, 0:1], zeros[id(p.user1)],
+                        zeros[id(p.item1)], zeros[id(p.wide_w)], zeros[id(p.wide_b)], None, accumulate=False)
+        ops.embed_bwd(DeepCrossing._specs(p.tables, e), x, batch, gh, zeros)
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)
