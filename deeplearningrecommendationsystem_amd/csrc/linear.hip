@@ -473,7 +473,7 @@ extern "C" int ctr_linear_bwd(const float* x, int64_t ldx, const float* w, int64
   CTR_REQUIRE(!gx || (w && ldw >= k && ldgx >= k), CTR_EINVAL);
   CTR_REQUIRE(!(gw || gb) || (x && ldx >= k), CTR_EINVAL);
   CTR_REQUIRE(!gw || ldgw >= k, CTR_EINVAL);
-  if (m == 0) return CTR_OK;
+  CTR_REQUIRE(!gb || gw, CTR_EINVAL);  // gb without gw is not used by any model; refused before dX is enqueued
   hipStream_t st = (hipStream_t)stream;
   if (n == 1 && ctr_n1_supported(k) && (gx || gw || gb))
     return ctr_n1_bwd(x, ldx, w, y, ldy, gy, ldgy, gx, ldgx, accumulate_gx, gw, gb, m, k, act, workspace,
@@ -482,9 +482,13 @@ extern "C" int ctr_linear_bwd(const float* x, int64_t ldx, const float* w, int64
   // the tile kernel, which beat the streaming variants tried for them
   if (gw && workspace && ctr_skinny_dw_ok(x, ldx, y, ldy, gy, ldgy, gw, ldgw, m, n, k, act)) {
     int rc = ctr_skinny_dw(x, ldx, y, ldy, gy, ldgy, gw, gb, m, n, k, act, workspace, workspace_floats, st);
-    if (rc != CTR_OK || !gx) return rc;
-    gw = nullptr;
-    gb = nullptr;
+    if (rc == CTR_OK) {
+      if (!gx) return rc;
+      gw = nullptr;
+      gb = nullptr;
+    } else if (rc != CTR_ELIMIT) {  // (a workspace of less than one slab: the tile kernel below takes any size)
+      return rc;
+    }
   }
   // wide layers with aligned operands: gY, Y and X stream global -> LDS directly (gemm_dlds_dw.hip)
   if (gw && workspace && ctr_gemm_dlds_dw_ok(x, ldx, y, ldy, gy, ldgy, gw, ldgw, m, n, k, act)) {
@@ -525,7 +529,6 @@ extern "C" int ctr_linear_bwd(const float* x, int64_t ldx, const float* w, int64
     const int64_t max_splits = ctr_ceil_div(m, 128);   // at least 128 rows each
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
-    CTR_REQUIRE(gw != nullptr, CTR_EINVAL);  // gb without gw is not used by any model
     // every chunk adds its partial to the same n*k outputs.  More than a handful of
     // chunks -> per-chunk slabs in the workspace + one reduction pass; same-address
     // atomic chains are serialised by the memory side (~60 ns per link)
