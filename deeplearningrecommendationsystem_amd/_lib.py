@@ -93,7 +93,8 @@ class NcfProjGrad(C.Structure):
                 ("g_mlp_user", C.c_void_p), ("g_mlp_item", C.c_void_p), ("g_gmf_user", C.c_void_p), ("g_gmf_item", C.c_void_p),
                 ("g_proj_w", C.c_void_p), ("ld_g_proj_w", C.c_int64), ("g_proj_b", C.c_void_p), ("g_head_w", C.c_void_p),
                 ("g_head_b", C.c_void_p), ("workspace", C.c_void_p), ("workspace_floats", C.c_int64),
-                ("zero_buf", C.c_void_p), ("zero_floats", C.c_int64), ("phases", C.c_int32), ("reserved", C.c_int32)]
+                ("zero_buf", C.c_void_p), ("zero_floats", C.c_int64), ("phases", C.c_int32), ("reserved", C.c_int32),
+                ("target", C.c_void_p), ("ldtarget", C.c_int64), ("loss", C.c_void_p)]
 
 
 class AdamTensor(C.Structure):

@@ -494,7 +494,8 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
 // pass, slab_reduce_role, does the index arithmetic once per output instead of every workgroup once per element):
 //   [vector v][lane][register r]: dW accumulator vectors  v < 8: layer 0 block (v / 4, v % 4);  8, 9: layer 1;  10: layer 2
 //   (register r of lane (q, lo) = row 16 b + 4 q + r, column 16 j + lo of its layer's weight gradient)
-//   then kSmall sums: layer-0 bias (32), layer-1 bias (16), layer-2 bias (8), sum gz * h (8), sum gz (1)
+//   then kSmall sums: layer-0 bias (32), layer-1 bias (16), layer-2 bias (8), sum gz * h (8), sum gz (1), and in the
+//   loss-fused mode the sum of the samples' BCE terms (1, word 65; zero otherwise)
 // (the GMF part of the head's weight gradient comes from the table rows, ncfp_finish)
 constexpr int slab_w(int l) {
   int o = 0;
@@ -505,6 +506,7 @@ constexpr int kSlabHead = slab_w(kL);                     // 2744 tower outputs:
 constexpr int kVecs = 8 + 2 + 1;                          // dW accumulator vectors of a lane
 constexpr int kSmall = 32 + 16 + 8 + 8 + 1;               // bias sums, sum gz * h, sum gz
 constexpr int kCopy = kVecs * 256 + 68;                   // one wave's sums parked in LDS (16-byte multiple)
+constexpr int kSlabLoss = kVecs * 256 + 65;               // the first of the three spare words behind the kSmall sums
 constexpr int kSlab = kCopy;                              // 2884
 constexpr int kStripP = 3 * kTile;                        // per wave: tiles A0 A1 | B0
 // the staged operands of a sample group (floats, per wave): sixteen rows each of P_U, P_I, Y1, Y2, Y3 -- fetched
@@ -523,7 +525,7 @@ struct Bwd {
   const float* ptab;
   const float* wfold;
   const float* prob; int64_t ldp;
-  const float* gprob; int64_t ldgp;
+  const float* gprob; int64_t ldgp;            // kLoss: the TARGET and its stride -- the gradient is formed here
   int act;
   const int32_t* base;                         // the forward's plan: [chunk][row] slot of the row's first sample of the chunk,
   int shift;                                   // chunk of sample s = s >> shift
@@ -540,6 +542,13 @@ __device__ __forceinline__ int sw1(int r) { return (r >> 1) & 7; }   // chunk sw
 __device__ __forceinline__ int sw2(int r) { return (r >> 2) & 3; }
 __device__ __forceinline__ int sw3(int r) { return (r >> 3) & 1; }
 
+// kLoss: the binary cross entropy of (prob, target) and its gradient for an upstream of exactly 1 are formed HERE
+// instead of by a launch of their own in front of this one (bce_fwd_kernel, csrc/train_step.hip: the same expressions,
+// so the gradient has the same bits): the per-sample scalar load that fetches gprob fetches the target instead -- the
+// number and order of vector-memory operations per group, and with them the hand-placed waits, are the same in both
+// instantiations -- and one lane per sample sums the loss terms, which leave through word kSlabLoss of the slab; the
+// slab second pass (slab_reduce_role) adds them over the workgroups in its fixed order and stores the mean.
+template <bool kLoss>
 __global__ void __launch_bounds__(kThreads)
 ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -627,7 +636,7 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
         ctr_dma16(T.y[2] + gr * T.ldy[2] + 4 * ((lane & 1) ^ sw3(row)), stage_addr + (uint32_t)(kSgY3 * 4));
       }
     }
-    r.gp = B.gprob[rc * B.ldgp];
+    r.gp = B.gprob[rc * B.ldgp];      // (kLoss: the sample's target)
     r.pb = B.prob[rc * B.ldp];
     r.ru = B.ranks[2 * rc];
     r.ri = B.ranks[2 * rc + 1];
@@ -640,6 +649,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   f32x4 dw0[2][4], dw1[2], dw2;                // dW blocks: register r = row 4q + r, column lo
   f32x4 sb0[2], sb1, sb2, hy = zero4;          // bias sums of this lane's sample: units 4q + r
   float hc = 0.0f;
+  float lc = 0.0f;                             // kLoss: the loss terms of this lane's samples (q == 0 alone)
+  const float inv_n = 1.0f / (float)m;         // (as ctr_bce_fwd forms it on the host: a correctly rounded quotient)
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
     sb0[b] = zero4;
@@ -668,7 +679,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
   for (int64_t g = wave0; g < groups; g += nwaves) {
     const bool live = g * 16 + lo < m;
     // ---- staged rows of g -> operands
-    const float gp = live ? sc.gp : 0.0f;                    // a dead lane's gz is zero: it adds nothing anywhere
+    float gp = kLoss ? 0.0f : live ? sc.gp : 0.0f;           // a dead lane's gz is zero: it adds nothing anywhere
+    const float yv = sc.gp;                                  // (kLoss: what that load brought is the target)
     const float pb = sc.pb;
     f32x4 y3d, y2d, y2t, y1d[2], y1t[2], a0d[4], a0t[4];
     y3d = *reinterpret_cast<const f32x4*>(stage + kSgY3 + lo * 8 + 4 * ((q & 1) ^ sw3(lo)));
@@ -704,6 +716,13 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     issue_ids(g + 2 * nwaves);
     STAMP(1, stamp++);   // next group requested
     // ---- head: gz, the head's sums, the tower's (masked) gY
+    if constexpr (kLoss) {
+      // bce_fwd_kernel's expressions on (prob, target), behind the requests so that they run under the fetches; a sample
+      // with an id outside its table has a prob, and counts
+      const float lp = fmaxf(logf(pb), -100.0f), l1p = fmaxf(logf(1.0f - pb), -100.0f);
+      if (q == 0 && live) lc -= yv * lp + (1.0f - yv) * l1p;
+      gp = live ? (pb - yv) / fmaxf((1.0f - pb) * pb, 1e-12f) * inv_n : 0.0f;
+    }
     const float gzs = gp * ctr_act_grad(pb, B.act);
     if (q == 0) hc += gzs;
     f32x4 gz3[1];
@@ -797,6 +816,7 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     for (int v = 0; v < kVecs; ++v) *reinterpret_cast<f32x4*>(copy + (v * 64 + lane) * 4) = vec(v);
     const f32x4 s00 = rsum(sb0[0]), s01 = rsum(sb0[1]), s1 = rsum(sb1), s2 = rsum(sb2), shy = rsum(hy);
     const float vc = row_sum16(hc);
+    const float vl = kLoss ? row_sum16(lc) : 0.0f;
     if (lo == 0) {
       *reinterpret_cast<f32x4*>(small + 4 * q) = s00;              // layer 0 bias sums: units 4q .. (block 0)
       *reinterpret_cast<f32x4*>(small + 16 + 4 * q) = s01;         //                     16 + 4q ..
@@ -808,7 +828,8 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
     }
     if (lane == 0) {
       small[64] = vc;
-      small[65] = small[66] = small[67] = 0.0f;
+      small[65] = vl;
+      small[66] = small[67] = 0.0f;
     }
   }
   __syncthreads();
@@ -848,6 +869,7 @@ struct Seg {
   // head fold chain rule: u = linear2.weight (128), w / b = `linear` (64 x 8)
   const float* fold_u; const float* fold_w; int64_t fold_ldw; const float* fold_b;
   float* g_u; float* g_w; int64_t ld_g_w; float* g_b; float* g_b2;   // (+=), nullable
+  float* loss; float inv_n;                    // nullable: the mean of the slabs' loss words is STORED here (loss-fused backward)
 };
 
 // float offset inside a slab of tower output e (e in the order [dW_l | db_l], l = 0..2)
@@ -865,13 +887,16 @@ __device__ __forceinline__ int slab_raw_of(int e) {
 }
 
 __device__ __forceinline__ void slab_reduce_role(const Seg& A, int blk) {
-  // outputs [32 blk, 32 blk + 32) of the kSlabHead tower sums: lane (o, pl) adds every 8th partial, 8 loads in flight
+  // outputs [32 blk, 32 blk + 32) of the kSlabHead tower sums: lane (o, pl) adds every 8th partial, 8 loads in flight.
+  // The last block has spare outputs: the first of them, e == kSlabHead, is the loss of a loss-fused backward -- the
+  // slabs' word kSlabLoss summed in the same fixed order, times 1 / batch, stored (not added) to the caller's word
   __shared__ float s_part[kWaves][32];
   const int o = threadIdx.x & 31, pl = threadIdx.x >> 5, wave = threadIdx.x >> 6;
   const int e = blk * 32 + o;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (e < kSlabHead) {
-    const float* src = A.slabs + slab_raw_of(e);
+  const bool is_loss = A.loss && e == kSlabHead;
+  if (e < kSlabHead || is_loss) {
+    const float* src = A.slabs + (is_loss ? kSlabLoss : slab_raw_of(e));
     int p = pl;
     for (; p + 7 * 8 < A.parts; p += 8 * 8) {
 #pragma unroll
@@ -899,6 +924,7 @@ __device__ __forceinline__ void slab_reduce_role(const Seg& A, int blk) {
     float* dst = r < wn ? A.gw[l] + r : A.gb[l] + (r - wn);
     dst[0] += total;
   }
+  if (threadIdx.x < 32 && is_loss) A.loss[0] = ((s_part[0][o] + s_part[1][o]) + (s_part[2][o] + s_part[3][o])) * A.inv_n;
 }
 
 __device__ __forceinline__ void head_fold_role(const Seg& A) {
@@ -1328,6 +1354,7 @@ constexpr int kFwdWgs = 256;        // per-sample workgroups of the forward, at 
 constexpr int kBwdWgs = 256;        // per-sample workgroups of the backward, at most: one slab each
 constexpr int kSlabsMax = 768;      // workspace_floats() reserves slabs for this many backward workgroups
 static_assert(kBwdWgs <= kSlabsMax, "the backward's slabs must fit the workspace");
+static_assert(kSlabHead < 32 * ((kSlabHead + 31) / 32), "the loss needs a spare output in the last slab-reduce block");
 
 static int64_t workspace_floats(int64_t batch, int64_t num_users, int64_t num_items) {
   const int64_t rows = num_users + num_items;
@@ -1348,7 +1375,8 @@ extern "C" int ctr_ncf_proj_workspace_floats(int64_t batch, int64_t num_users, i
 
 // `phases`: 0 = the whole call; else a mask of its launches (a profiler brackets them one by one): forward 1 = projected
 // tables + head fold (+ chunk histograms), 2 = the per-sample kernel (+ the plan's prefixes and offsets); backward 1 = the per-sample kernel, 2 = segment sums + slab reduction +
-// head fold, 4 = the table-row products
+// head fold, 4 = the table-row products.  With a target the backward's launch 1 forms the loss terms and launch 2
+// stores the loss.
 extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   CTR_REQUIRE(d && d->batch >= 0, CTR_EINVAL);
   const int phases = d->phases ? d->phases : 3;
@@ -1397,7 +1425,11 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
 extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad_t* g, void* stream) {
   CTR_REQUIRE(d && g && d->batch >= 0, CTR_EINVAL);
   if (!pattern_ok(d)) return CTR_ELIMIT;
-  CTR_REQUIRE(d->plan && d->ranks && d->prob && g->gprob && g->ldgprob >= 1 && g->workspace, CTR_EINVAL);
+  CTR_REQUIRE(d->plan && d->ranks && d->prob && g->workspace, CTR_EINVAL);
+  // the gradient of prob: the caller's, or (target set) the binary cross entropy's, formed by the per-sample kernel
+  const bool fused = g->target != nullptr;
+  CTR_REQUIRE(fused ? g->ldtarget >= 1 : (g->gprob && g->ldgprob >= 1 && !g->loss), CTR_EINVAL);
+  CTR_REQUIRE(!g->loss || d->batch > 0, CTR_EINVAL);   // (no mean over no samples)
   CTR_REQUIRE(!g->zero_buf || (ctr_aligned16(g->zero_buf) && g->zero_floats % 4 == 0 && g->zero_floats >= 0), CTR_EALIGN);
   Tower T;
   int rc = fill_tower(&T, d->layers, true);
@@ -1419,14 +1451,16 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   const Ids ids{d->user_idx, d->user_stride, d->item_idx, d->item_stride, nu, ni};
   const Plan plan = plan_of(d->plan, rows, m);
   const int32_t* offs = plan.offsets;
-  const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, g->gprob, g->ldgprob, d->head_act, plan.base, plan.shift,
+  const Bwd B{ids, d->ptab, d->wfold, d->prob, d->ldprob, fused ? g->target : g->gprob, fused ? g->ldtarget : g->ldgprob,
+              d->head_act, plan.base, plan.shift,
               d->ranks, gzb, aux, slabs, stt, rows * 128, g->zero_buf, g->zero_buf ? g->zero_floats : 0};
   constexpr size_t lds_bytes = sizeof(float) * (size_t)kBwdLdsFloats;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+  const auto bwd_kernel = fused ? ncfp_bwd_kernel<true> : ncfp_bwd_kernel<false>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)lds_bytes) != hipSuccess)
     return CTR_ELAUNCH;
   const int phases = g->phases ? g->phases : 7;
-  if (phases & 1) hipLaunchKernelGGL(ncfp_bwd_kernel, dim3((unsigned)grid), dim3(kThreads), lds_bytes, st, T, m, B);
+  if (phases & 1) hipLaunchKernelGGL(bwd_kernel, dim3((unsigned)grid), dim3(kThreads), lds_bytes, st, T, m, B);
   rc = ctr_launch_status();
   if (rc != CTR_OK) return rc;
   // segment sums over the buckets, and beside them (own workgroups) the tower's dW / db partials and the head fold's
@@ -1434,7 +1468,7 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   Seg S{gzb, aux, offs, d->gmf_user, d->gmf_item, nu, ni, m, stt, (int)ctr_ceil_div(2 * m, kSegWgSlots),
         (kSlabHead + 31) / 32,
         slabs, (int)grid, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, d->head_w, d->proj_w, d->ld_proj_w,
-        d->proj_b, g->g_head_w, g->g_proj_w, g->ld_g_proj_w, g->g_proj_b, g->g_head_b};
+        d->proj_b, g->g_head_w, g->g_proj_w, g->ld_g_proj_w, g->g_proj_b, g->g_head_b, g->loss, 1.0f / (float)m};
   for (int l = 0; l < kL; ++l) {
     S.gw[l] = g->layers[l + 1].gw;
     S.gb[l] = g->layers[l + 1].gb;

@@ -10,12 +10,19 @@ static-shape, static-address case a captured graph needs.  ``GraphedStep`` captu
 kernels) and replays it with one ``hipGraphLaunch`` per step.  Parameters are updated
 in place by the optimizer between replays, so the graph always sees current weights;
 ``.grad`` tensors live in the graph's memory pool and are rewritten by every replay.
+
+With ``loss.BCELoss`` on NeuralCF's table-row path the captured step has no loss launch: the model's backward forms the
+loss and its gradient from (prob, target) itself (``loss.deferred_bce``).  Every other model, loss, target dtype or path
+is captured with the launches an eager step makes.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Sequence
 
 import torch
+
+from . import loss as _loss
 
 
 class GraphedStep:
@@ -32,18 +39,29 @@ class GraphedStep:
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 self._eager()
+            # the root gradient of loss.backward() is a constant 1: made once here instead of by a fill
+            # kernel inside every replay (BCELoss recognises this tensor and skips its scaling launch)
+            self._one = _loss.unit_grad(target.device)
+            # a step whose loss may defer runs once as it will be captured: the launches only that form makes happen for
+            # the first time here, not under capture
+            if type(loss_fn) is _loss.BCELoss:
+                model.zero_grad(set_to_none=True)
+                self._step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         model.zero_grad(set_to_none=True)
-        # the root gradient of loss.backward() is a constant 1: made once here instead of by a fill
-        # kernel inside every replay
-        from .loss import unit_grad  # BCELoss recognises this tensor and skips its scaling launch
-        self._one = unit_grad(target.device)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.prob = model(*self.inputs)
-            self.loss = loss_fn(self.prob, self.target)
-            self.loss.backward(self._one)
+            self.prob, self.loss = self._step()
+
+    def _step(self):
+        """forward, loss, backward against THE 1.0; a ``BCELoss`` (that class itself) may defer into the backward"""
+        defer = _loss.deferred_bce() if type(self.loss_fn) is _loss.BCELoss else contextlib.nullcontext()
+        with defer:
+            prob = self.model(*self.inputs)
+            loss = self.loss_fn(prob, self.target)
+            loss.backward(self._one)
+        return prob, loss
 
     def _eager(self):
         self.model.zero_grad(set_to_none=True)

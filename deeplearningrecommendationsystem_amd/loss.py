@@ -8,8 +8,15 @@ contiguous samples, the positive first: the batches of a ``data.DeviceLoader(...
 model's probabilities like ``BCELoss`` (every model of the package ends in a sigmoid) and go back to the logit; the
 definitions stand in the header comment of csrc/group_loss.hip.  Same launch structure as ``BCELoss``: one forward
 launch that also writes the gradient for an upstream of exactly 1, one backward pass otherwise.  The reference has
-no loss over a group."""
+no loss over a group.
+
+Inside a captured step (``graph.GraphedStep``) ``BCELoss`` on NeuralCF's table-row path launches nothing at all: the
+model's backward launch forms the gradient from (prob, target) itself and its second launch stores the loss
+(``deferred_bce`` below, csrc/ncf_proj.hip).  Eager code never takes that road: its loss has to be valid when
+``loss_fn`` returns."""
 from __future__ import annotations
+
+import contextlib
 
 import torch
 
@@ -82,10 +89,89 @@ class _BCEFunction(torch.autograd.Function):
         return gp.view(ctx.shape), None
 
 
+# ---------------------------------------------------------------------------
+# the loss deferred into the backward of the model that produced ``prob``
+# ---------------------------------------------------------------------------
+class _Deferral:
+    """what a step that runs under ``deferred_bce`` knows: ``run`` is the forward (``ops.NcfProj``) whose backward can
+    form the loss, ``prob`` the tensor it returned.  The model offers both (``offer_deferral``); nobody else does."""
+
+    def __init__(self):
+        self.run = self.prob = None
+
+
+_deferral = None     # set only inside ``deferred_bce``
+
+
+@contextlib.contextmanager
+def deferred_bce():
+    """Inside, ``BCELoss()(prob, target)`` on a ``prob`` that a model offered with ``offer_deferral`` launches nothing:
+    it hands the model's backward the target and the loss tensor it returns.  The loss is valid only after
+    ``loss.backward(unit_grad(device))`` has run -- which is why only a step that always runs the backward right behind
+    the loss (``GraphedStep``) may enter here.  The state is gone when the block is left, by an exception too."""
+    global _deferral
+    if _deferral is not None:
+        raise RuntimeError("deferred_bce does not nest")
+    _deferral = _Deferral()
+    try:
+        yield _deferral
+    finally:
+        _deferral = None
+
+
+def offer_deferral(run, prob: torch.Tensor) -> None:
+    """a model's forward says: the backward of ``run`` (its ``backward`` takes ``target`` and ``loss``) can form the BCE
+    loss of ``prob``.  Outside ``deferred_bce`` this is nothing."""
+    if _deferral is not None:
+        _deferral.run, _deferral.prob = run, prob
+
+
+class _DeferredBCEFunction(torch.autograd.Function):
+    """no launch: the gradient it passes back is a PLACEHOLDER that is never read -- ``run``'s backward recognises it by
+    address (as this one recognises ``unit_grad``) and forms the real one itself"""
+
+    @staticmethod
+    def forward(ctx, prob, target, run):
+        loss = torch.empty((), dtype=torch.float32, device=prob.device)
+        placeholder = torch.empty(prob.numel(), dtype=torch.float32, device=prob.device)
+        run.deferred = (target, loss, placeholder)
+        ctx.shape, ctx.placeholder, ctx.device = prob.shape, placeholder, prob.device
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        unit = _units.get(ctx.device.index)
+        if unit is None or gloss.data_ptr() != unit.data_ptr():
+            raise RuntimeError("a deferred BCELoss takes loss.backward(unit_grad(device)) and nothing else: the model's "
+                               "backward forms the gradient for an upstream of exactly 1")
+        return ctx.placeholder.view(ctx.shape), None, None
+
+
+def _deferrable(input: torch.Tensor, target: torch.Tensor):
+    """the flat view of ``target`` the model's backward reads, if this call can be deferred; else None"""
+    d = _deferral
+    if d is None or d.run is None or not input.requires_grad or not torch.is_grad_enabled():
+        return None
+    # THE tensor the model returned (or a view of all of it: its gradient arrives at the model as a view of ours)
+    if input.data_ptr() != d.prob.data_ptr() or input.numel() != d.prob.numel() or not input.is_contiguous():
+        return None
+    if not target.is_cuda or target.dtype != torch.float32 or target.numel() != input.numel() or target.requires_grad:
+        return None
+    flat = target.reshape(-1)
+    if flat.numel() > 1 and flat.untyped_storage().data_ptr() != target.untyped_storage().data_ptr():
+        return None      # reshape had to copy: a replay would read the copy's launch, not the caller's buffer -- today's path
+    return flat
+
+
 class BCELoss(torch.nn.Module):
     """``BCELoss()(prob, target)`` -> scalar mean loss, like ``torch.nn.BCELoss()``"""
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if _deferral is not None and type(self) is BCELoss:
+            flat = _deferrable(input, target)
+            if flat is not None:
+                run, _deferral.run, _deferral.prob = _deferral.run, None, None
+                return _DeferredBCEFunction.apply(input, flat, run)
         return _BCEFunction.apply(input, target)
 
 

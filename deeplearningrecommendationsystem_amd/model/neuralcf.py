@@ -8,6 +8,7 @@ import torch
 from torch import nn
 from torch.nn.init import xavier_normal_
 
+from .. import loss as _loss
 from .. import ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
 from .._lib import FIELD_ID_I64, FIELD_PROD_I64, CtrHipError
@@ -70,6 +71,8 @@ class _ProjPath:
         prob = run.forward()
         if prob is None:
             raise CtrHipError("ctr_ncf_proj_fwd refused a shape NcfProj.supported() accepted")
+        if training:
+            _loss.offer_deferral(run, prob)      # (inside a captured step alone: this backward can form the BCE loss)
         return prob, (), {"run": run if training else None}
 
     @staticmethod
@@ -80,7 +83,16 @@ class _ProjPath:
         state["run"] = None
         zeros = ops.zero_grads(list(p.flat), lazy=True)   # cleared by the backward's first launch
         flat = zeros.pop("flat")
-        run.backward(gprob.contiguous(), zeros, flat)
+        deferred = getattr(run, "deferred", None)
+        if deferred is None:
+            run.backward(gprob.contiguous(), zeros, flat)
+        else:
+            # a deferred BCELoss sits on prob: its gradient is a placeholder nobody wrote.  Anything but that very tensor
+            # (a sum with another consumer's gradient, a copy) cannot be honoured -- and is never computed from
+            target, loss, placeholder = deferred
+            if gprob.data_ptr() != placeholder.data_ptr() or gprob.numel() != placeholder.numel():
+                raise RuntimeError("NeuralCF backward: prob of a step with a deferred BCELoss may feed that loss alone")
+            run.backward(None, zeros, flat, target=target, loss=loss)
         return zeros
 
 

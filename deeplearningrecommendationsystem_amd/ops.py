@@ -790,9 +790,12 @@ class NcfProj:
         _lib.check(rc, "ctr_ncf_proj_fwd")
         return self.prob
 
-    def backward(self, gprob: torch.Tensor, grads: dict, zero: Optional[torch.Tensor]) -> None:
+    def backward(self, gprob: Optional[torch.Tensor], grads: dict, zero: Optional[torch.Tensor],
+                 target: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> None:
         """``grads[id(param)]``: where each parameter's gradient accumulates; ``zero``: the flat buffer behind them,
-        cleared by the call's first launch"""
+        cleared by the call's first launch.  With ``target`` (float32, one element per sample, any stride) ``gprob`` is
+        not read: the gradient is the binary cross entropy's for an upstream of exactly 1, formed inside the per-sample
+        launch, and ``loss`` (a float32 scalar, optional) receives the mean loss from the call's second launch."""
         if getattr(self, "_spent", False):
             # the first backward hands the plan buffer back to its holder: the next forward may have rebuilt it for
             # other ids by the time a second backward over this forward would read it
@@ -802,8 +805,19 @@ class NcfProj:
         gmf_u, gmf_i, mlp_u, mlp_i = self.tables
         d = self._desc()
         g = _lib.NcfProjGrad()
-        gprob = gprob.reshape(-1)
-        g.gprob, g.ldgprob = gprob.data_ptr(), gprob.stride(0) if gprob.numel() > 1 else 1
+        if gprob is not None:
+            gprob = gprob.reshape(-1)
+            g.gprob, g.ldgprob = gprob.data_ptr(), gprob.stride(0) if gprob.numel() > 1 else 1
+        if target is not None:
+            _lib.require_device(target)
+            if target.dtype != torch.float32 or target.dim() != 1 or target.numel() != self.batch:
+                raise ValueError("NcfProj.backward: target must be float32 with one element per sample, flattened")
+            g.target, g.ldtarget = target.data_ptr(), target.stride(0) if target.numel() > 1 else 1
+        if loss is not None:
+            _lib.require_device(loss)
+            if loss.dtype != torch.float32 or loss.numel() != 1:
+                raise ValueError("NcfProj.backward: loss must be one float32")
+            g.loss = loss.data_ptr()
         for k, layer in enumerate(self.hidden):
             g.layers[k].gw, g.layers[k].gb = grads[id(layer.weight)].data_ptr(), grads[id(layer.bias)].data_ptr()
         g.g_mlp_user, g.g_mlp_item, g.g_gmf_user, g.g_gmf_item = (grads[id(t)].data_ptr() for t in (mlp_u, mlp_i, gmf_u, gmf_i))

@@ -479,7 +479,15 @@ int ctr_act_mask_bwd(float* g, int64_t ldg, const float* y, int64_t ldy, int64_t
  * Parameters must not change between the forward and the backward (the backward re-reads tables and ptab).
  * The backward's workspace (ctr_ncf_proj_workspace_floats): gz0 rows in sample order (batch + 1, 64) | slot records
  * (2 batch + 1, 4) = {gz, partner id, row, sample}, the user rows' buckets first | segment sums (rows, 128) | the
- * per-sample kernel's slabs. */
+ * per-sample kernel's slabs.
+ * The backward with the loss inside (ctr_ncf_proj_grad_t.target set): the gradient of prob is not passed in, it is
+ * the binary cross entropy's for an upstream gradient of exactly 1 -- (p - y) / max(p (1 - p), 1e-12) / batch, the
+ * expression and the bits of ctr_bce_fwd's gprob_unit -- formed by the per-sample kernel from prob and target; gprob
+ * is then not read and may be null.  With `loss` set as well the call STORES the mean loss there (ctr_bce_fwd's
+ * value up to fp32 summation order, the same bits from run to run): the per-sample kernel sums the terms, the second
+ * launch adds the workgroups' sums in a fixed order, so the word is valid once launch 2 of `phases` has run.  No
+ * launch, ticket or buffer is added.  Refused with CTR_EINVAL before anything is enqueued: `loss` without `target`,
+ * ldtarget < 1, neither target nor gprob, and `loss` with an empty batch (there is no mean over no samples). */
 #define CTR_NCF_PROJ_MAX_ROWS 16384
 #define CTR_NCF_PROJ_COUNT_STRIDE 72   /* int32 of plan per table row: 64 chunk counts, total, offset, and room for the head and the block totals */
 typedef struct ctr_ncf_proj {
@@ -508,6 +516,8 @@ typedef struct ctr_ncf_proj_grad {
   float* zero_buf; int64_t zero_floats;           /* nullable: cleared by the call's first launch (see ctr_embed_mlp_head_bwd) */
   int32_t phases; int32_t reserved;               /* 0: the whole call; else a mask (1 per-sample kernel, 2 segment sums + slab
                                                      reduction + head fold, 4 table-row products), issued in that order */
+  const float* target; int64_t ldtarget;          /* nullable: (batch) BCE targets, element stride; set: gprob is not read */
+  float* loss;                                    /* nullable, only with target: the mean BCE loss is stored here */
 } ctr_ncf_proj_grad_t;
 int ctr_ncf_proj_workspace_floats(int64_t batch, int64_t num_users, int64_t num_items, int64_t* floats /*host, out*/);
 int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream);
