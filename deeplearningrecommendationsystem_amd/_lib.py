@@ -24,6 +24,9 @@ CTR_NCF_PROJ_COUNT_STRIDE = 72
 CTR_ROWS1_MAX_ROWS = 32768
 CTR_GDCF_MAX_DIM = 256
 CTR_GROUP_MAX_K = 4095
+CTR_SCORE_CHUNK = 65536
+CTR_GAUC_SMALL = 64
+CTR_GAUC_SLAB = 1024
 FIELD_ID_I64, FIELD_ID_F32, FIELD_BAG, FIELD_DENSE, FIELD_PROD_I64 = range(5)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = range(3)
 
@@ -203,6 +206,8 @@ SIGNATURES = {
     "ctr_load_batch_groups": (_i, [_p, _p, C.c_uint64, _l, _l, _l, _i, _p]),   # as ctr_load_batch_neg
     "ctr_eval_candidates": (_i, [_p, _p, _l, _p, _p, _l, _l, _l, _i, C.c_uint64, _p, _l, _p, _p, _p]),
     "ctr_group_rank": (_i, [_p, _l, _l, _i, _p, _p, _p]),
+    "ctr_score_counts": (_i, [_p, _p, _l, _p, _p, _p]),
+    "ctr_gauc_groups": (_i, [_p, _p, _l, _p, _p, _l, _p, _l, _p, _p, _l, _p, _p, _p, _p, _p]),
     "ctr_shard_bucket": (_i, [_p, _l, _i, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_bucket_padded": (_i, [_p, _l, _i, _l, _l, _p, _p, _p, _p, _p, _p]),
     "ctr_shard_recv_rows": (_i, [_p, _l, _l, _p, _p, _p, _p]),

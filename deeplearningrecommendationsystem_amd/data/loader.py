@@ -193,6 +193,7 @@ class DeviceLoader:
         self.batch_size, self.seed, self.shuffle = int(batch_size), int(seed), bool(shuffle)
         self.drop_last, self.rank, self.world = bool(drop_last), int(rank), int(world)
         ids = [t.contiguous() for t in ids]
+        self._users = ids[0]                               # every family: the users come first
         self._feature = None if feature is None else (feature, ids[0], ids[1])
         self._history = None if history is None else (history.contiguous(), ids[0])
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -327,6 +328,11 @@ class DeviceLoader:
         _lib.check(rc, "ctr_loader_indices")
         group = torch.div(pos, per, rounding_mode="floor")
         return order[group - g0] * per + (pos - group * per)
+
+    def user_ids(self) -> torch.Tensor:
+        """(num_samples,) int64 user of every sample of the unshuffled epoch: with ``negatives=k`` sample v has the
+        user of positive ``v // (1 + k)``, grouped or not -- what ``evaluator.UserGroups`` is built from"""
+        return self._users.repeat_interleave(1 + self.negatives) if self.negatives else self._users
 
     def check_bad_index(self):
         """raise the IndexError of an id outside its join table seen by any batch since the last call, or the

@@ -1618,3 +1618,69 @@ def group_rank(scores: torch.Tensor, k: int, hist: torch.Tensor, ranks: Optional
                 _lib.load().ctr_group_rank, _lib.ptr(scores) if n else None, ld, n, int(k), _lib.ptr(ranks),
                 hist.data_ptr(), _lib.stream_ptr())
     _lib.check(rc, "ctr_group_rank")
+
+
+# ---------------------------------------------------------------------------
+# score-level evaluation (csrc/score_eval.hip)
+# ---------------------------------------------------------------------------
+SCORE_CHUNK = _lib.CTR_SCORE_CHUNK
+GAUC_SMALL, GAUC_SLAB = _lib.CTR_GAUC_SMALL, _lib.CTR_GAUC_SLAB
+
+
+def _flat_f32(name, what, t, n=None):
+    if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.shape[0] != n):
+        raise ValueError(f"{name}: {what} must be a contiguous (N,) float32 tensor")
+
+
+def _flat_int(name, what, t, dtype, n):
+    if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n:
+        raise ValueError(f"{name}: {what} must be a contiguous ({n},) {str(dtype).replace('torch.', '')} tensor")
+
+
+def score_counts(prob: torch.Tensor, target: torch.Tensor, counts: torch.Tensor, sums: torch.Tensor) -> None:
+    """``ctr_score_counts``: prob / target contiguous (N,) float32; ``counts`` (8,) int64 is added to
+    ({positives, negatives, tp, fp, fn, tn, bad, 0}), ``sums`` (ceil(N / SCORE_CHUNK), 4) float64 receives one row
+    {sum BCE term, sum p, sum (p - y)^2, sum y} per chunk of SCORE_CHUNK samples"""
+    _lib.require_device(prob, target, counts, sums)
+    _flat_f32("score_counts", "prob", prob)
+    n = prob.shape[0]
+    _flat_f32("score_counts", "target", target, n)
+    _flat_int("score_counts", "counts", counts, torch.int64, 8)
+    chunks = -(-n // SCORE_CHUNK)
+    if sums.dtype != torch.float64 or sums.shape != (chunks, 4) or not sums.is_contiguous():
+        raise ValueError(f"score_counts: sums must be a contiguous ({chunks}, 4) float64 tensor")
+    rc = _timed("score_counts", lambda: (8 * n + 32 * chunks, 0), _lib.load().ctr_score_counts,
+                _lib.ptr(prob) if n else None, _lib.ptr(target) if n else None, n, counts.data_ptr(),
+                _lib.ptr(sums) if n else None, _lib.stream_ptr())
+    _lib.check(rc, "ctr_score_counts")
+
+
+def gauc_groups(prob: torch.Tensor, target: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor,
+                small_groups: torch.Tensor, slab_group: torch.Tensor, slab_first: torch.Tensor, pos: torch.Tensor,
+                neg: torch.Tensor, u2: torch.Tensor, err: torch.Tensor) -> None:
+    """``ctr_gauc_groups``: prob / target contiguous (N,) float32, group g = the samples order[offsets[g] ..
+    offsets[g + 1]) (order (N,) int32, offsets (G + 1,) int64), ``small_groups`` / ``slab_group`` / ``slab_first`` the
+    int32 work lists of ``evaluator.score.UserGroups``.  ``pos`` / ``neg`` (G,) int32 receive the class counts,
+    ``u2`` (G,) int64 is added to; ``err``: device int32 flag, raised and never cleared."""
+    _lib.require_device(prob, target, order, offsets, small_groups, slab_group, slab_first, pos, neg, u2, err)
+    _flat_f32("gauc_groups", "prob", prob)
+    n = prob.shape[0]
+    _flat_f32("gauc_groups", "target", target, n)
+    _flat_int("gauc_groups", "order", order, torch.int32, n)
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1 or not offsets.is_contiguous():
+        raise ValueError("gauc_groups: offsets must be a contiguous (G + 1,) int64 tensor")
+    groups = offsets.shape[0] - 1
+    if n >= 1 << 31 or groups >= 1 << 31:
+        raise ValueError("gauc_groups: N and G must be below 2^31")
+    _flat_int("gauc_groups", "small_groups", small_groups, torch.int32, small_groups.numel())
+    _flat_int("gauc_groups", "slab_group", slab_group, torch.int32, slab_group.numel())
+    _flat_int("gauc_groups", "slab_first", slab_first, torch.int32, slab_group.numel())
+    _flat_int("gauc_groups", "pos", pos, torch.int32, groups)
+    _flat_int("gauc_groups", "neg", neg, torch.int32, groups)
+    _flat_int("gauc_groups", "u2", u2, torch.int64, groups)
+    _flat_int("gauc_groups", "err", err, torch.int32, 1)
+    nz = lambda t: _lib.ptr(t) if t.numel() else None                                     # noqa: E731
+    rc = _timed("gauc_groups", lambda: (12 * n + 24 * groups, 0), _lib.load().ctr_gauc_groups, nz(prob), nz(target), n,
+                nz(order), offsets.data_ptr(), groups, nz(small_groups), small_groups.numel(), nz(slab_group),
+                nz(slab_first), slab_group.numel(), nz(pos), nz(neg), nz(u2), err.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "ctr_gauc_groups")

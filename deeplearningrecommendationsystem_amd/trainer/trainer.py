@@ -18,6 +18,7 @@ class Trainer:
         self.predictions_train = self.predictions_valid = self.predictions_test = None
         self.train_rating = self.valid_rating = self.test_rating = None
         self.rank_metrics = self.predictions_rank = self.rank_rating = self.rank_loss = None
+        self.score_metrics = self.predictions_score = self.score_rating = self.score_loss = None
         self._graph = graph
         self._graphed = None
         self._graph_key = None
@@ -199,6 +200,24 @@ class Trainer:
         self.predictions_rank, self.rank_rating, self.rank_loss = self._eval_epoch(loader)
         self.rank_metrics = group_ranking_metrics(self.predictions_rank, negatives, cutoffs)
         return self.rank_metrics
+
+    def score_epoch(self, loader, groups=None):
+        """score-level evaluation: an unshuffled pass over ``loader``, then log-loss, the thresholded metrics,
+        calibration, RMSE and AUC of the gathered predictions, and with ``groups`` -- the ``evaluator.UserGroups`` of
+        ``loader.user_ids()``, built once per evaluation set -- GAUC (``evaluator.score``).  The log-loss is there
+        whatever ``loss_fn`` is.  Keeps and returns ``score_metrics``; the predictions, ratings and loss of the pass are
+        kept as ``predictions_score`` / ``score_rating`` / ``score_loss``."""
+        from ..evaluator.score import score_metrics
+        if groups is not None:
+            if loader.world != 1:
+                raise ValueError("score_epoch: a loader with world > 1 shows this rank a part of the samples, and the "
+                                 "groups are those of all of them; evaluate with a world=1 loader")
+            if groups.num_samples != loader.num_samples:
+                raise ValueError(f"score_epoch: the groups hold {groups.num_samples} samples, the loader "
+                                 f"{loader.num_samples}")
+        self.predictions_score, self.score_rating, self.score_loss = self._eval_epoch(loader)
+        self.score_metrics = score_metrics(self.score_rating, self.predictions_score, groups)
+        return self.score_metrics
 
     def model_eval(self, epoch):
         """prints the reference's per-epoch report (trainer/trainer.py:116-146)"""

@@ -824,6 +824,42 @@ int ctr_group_rank(const float* scores, int64_t ld, int64_t n, int k, int32_t* r
                    void* stream);
 
 /* ------------------------------------------------------------------------
+ * Score-level evaluation (csrc/score_eval.hip): log-loss, confusion counts, calibration and RMSE in one pass over
+ * (prob, target), and the integer counts behind every user's own AUC (GAUC).  prob / target: n contiguous float32.
+ * Class rule: a sample is positive iff target > 0.5f (a NaN target is negative); a prediction is hard iff
+ * prob >= 0.5f.
+ * ctr_score_counts.  counts (8) int64 = {positives, negatives, tp, fp, fn, tn, bad, 0}, bad = #{prob NaN or outside
+ * [0, 1]}, ADDED to by integer atomics: the caller zeroes it.  sums: ceil(n / CTR_SCORE_CHUNK) rows of 4 float64, every
+ * row STORED; row c, over the samples [c CTR_SCORE_CHUNK, min(n, (c + 1) CTR_SCORE_CHUNK)):
+ *   [0] sum of the fp32 term -(y max(logf(p), -100) + (1 - y) max(logf(1.0f - p), -100)), widened to double; the max
+ *       is fmaxf, which drops a NaN: a NaN logarithm (p NaN, p < 0, p > 1) counts as -100
+ *   [1] sum p      [2] sum ((double) p - (double) y)^2      [3] sum y
+ * A row is summed in a fixed order by one workgroup and depends on its chunk's data only; the caller adds the rows in
+ * float64 in chunk order, so the totals are bitwise reproducible.  n == 0 is a no-op; n < 0 or a null pointer with
+ * n > 0 is CTR_EINVAL.
+ * ctr_gauc_groups.  Group g holds the samples order[offsets[g] .. offsets[g + 1]); order (n) int32, offsets
+ * (num_groups + 1) int64.  small_groups (num_small) lists the groups of at most CTR_GAUC_SMALL samples; every larger
+ * group g of s samples has ceil(s / CTR_GAUC_SLAB) slabs (slab_group = g, slab_first = 0, CTR_GAUC_SLAB, ..).  With i
+ * over the positives of group g and j over its negatives:
+ *   pos_out[g] = #positives     neg_out[g] = #negatives                                 (int32, stored)
+ *   u2_out[g] += sum_i sum_j ( 2 [prob_j < prob_i] + [prob_j == prob_i] )               (int64, ADDED to: zero it)
+ * so that AUC_g = u2 / (2 pos neg).  IEEE comparisons: a NaN score on either side adds 0, -0.0 == 0.0.  Integers only:
+ * exact, whatever the launch geometry or the order of the atomics.  An order entry outside [0, n) is skipped and raises
+ * *err_flag (device int32, nullable); so does a work item that does not fit the plan (group id outside
+ * [0, num_groups), offsets outside 0 <= lo <= hi <= n, a small group longer than CTR_GAUC_SMALL, a slab that starts
+ * outside its group), which is skipped whole.  n or num_groups >= 2^31 is CTR_ELIMIT; a negative count, or a null
+ * pointer with work to do, is CTR_EINVAL; num_groups == 0 is a no-op.
+ * ---------------------------------------------------------------------- */
+#define CTR_SCORE_CHUNK 65536
+#define CTR_GAUC_SMALL 64      /* groups up to this size: one wave each */
+#define CTR_GAUC_SLAB  1024    /* larger groups: one work item per this many samples */
+int ctr_score_counts(const float* prob, const float* target, int64_t n, int64_t* counts, double* sums, void* stream);
+int ctr_gauc_groups(const float* prob, const float* target, int64_t n, const int32_t* order, const int64_t* offsets,
+                    int64_t num_groups, const int32_t* small_groups, int64_t num_small, const int32_t* slab_group,
+                    const int32_t* slab_first, int64_t num_slabs, int32_t* pos_out, int32_t* neg_out, int64_t* u2_out,
+                    int32_t* err_flag, void* stream);
+
+/* ------------------------------------------------------------------------
  * Head folding: a linear layer W (n x k, bias b) whose output feeds ONLY a single-unit layer u is the
  * k-wide dot product  (h W^T + b).u + b2 == h.v + c,  v = W^T u,  c = b.u + b2.  NeuralCF ends like
  * that (model/neuralcf.py:27 linear, :50-56 cat + linear2): folding per step keeps the 8 -> mf_dim
