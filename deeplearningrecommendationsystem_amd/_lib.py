@@ -197,6 +197,8 @@ SIGNATURES = {
     "ctr_ncf_proj_workspace_floats": (_i, [_l, _l, _l, C.POINTER(C.c_int64)]),
     "ctr_ncf_proj_fwd": (_i, [C.POINTER(NcfProj), _p]),
     "ctr_ncf_proj_bwd": (_i, [C.POINTER(NcfProj), C.POINTER(NcfProjGrad), _p]),
+    "ctr_ncf_grid_scores": (_i, [_p, _p, _p, _p, _l, _l, _i, _i, C.POINTER(MlpLayer), _i, _p, _p, _i, _p, _l, _l, _i,
+                                 _p, _l, _p]),
     "ctr_mlp_bwd": (_i, [_p, _l, _l, C.POINTER(MlpLayer), _i, _p, _l, _p, _l, _p, _l, _p]),
     "ctr_negative_sample": (_i, [_p, _l, _l, _l, _i, C.c_uint64, _p, _p, _p, _p]),
     "ctr_assemble_features": (_i, [_p, _p, _l, _p, _i, _l, _p, _i, _l, _p, _l, _p, _p]),

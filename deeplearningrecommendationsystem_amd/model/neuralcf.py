@@ -10,6 +10,7 @@ from torch.nn.init import xavier_normal_
 
 from .. import loss as _loss
 from .. import ops
+from ..cf import _MAX_BATCH, _SCORE_CHUNK_FLOATS, _users_tensor
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
 from .._lib import FIELD_ID_I64, FIELD_PROD_I64, CtrHipError
 from ._base import CtrModule
@@ -354,3 +355,118 @@ class NeuralCF(CtrModule):
             for lo in range(0, users.numel(), chunk):
                 scores[lo:lo + chunk] = self.forward(users[lo:lo + chunk], items[lo:lo + chunk]).view(-1)
         return ops.topk_rows(scores.view(num_users, num_items), num_items).cpu().numpy()
+
+    # ---- the user x item grid: row scorers and a bounded-workspace ranker (no gradients, training paths untouched)
+    def _table_sizes(self):
+        return self.GMF_Embedding_User.weight.shape[0], self.GMF_Embedding_Item.weight.shape[0]
+
+    @torch.no_grad()
+    def score_rows(self, start: int, stop: int) -> torch.Tensor:
+        """(stop - start, num_items) float32 device tensor, fresh and row-major: the probabilities of users
+        [start, stop) against every item -- the ``scores(start, stop)`` callable ``ranking_metrics`` takes.  Not
+        chunked: the caller chose the rows."""
+        num_users, _ = self._table_sizes()
+        start, stop = int(start), int(stop)
+        if not 0 <= start <= stop <= num_users:
+            raise IndexError(f"users [{start}, {stop}) are outside [0, {num_users})")
+        return _GridScorer(self)(start=start, stop=stop)
+
+    @torch.no_grad()
+    def score_grid(self, users=None) -> torch.Tensor:
+        """(len(users), num_items) float32 probabilities for any 1-D list of user ids (repeats and any order allowed;
+        an id outside the table raises IndexError); ``None``: every user.  Not chunked: the caller chose the rows."""
+        num_users, _ = self._table_sizes()
+        if users is None:
+            return _GridScorer(self)(start=0, stop=num_users)
+        return _GridScorer(self)(users=_users_tensor(users, num_users, self.GMF_Embedding_User.weight.device))
+
+    @torch.no_grad()
+    def recommend(self, users=None, n: int = 20, exclude=None) -> torch.Tensor:
+        """(len(users), n) int64: the items with the highest probability, best first, ties by ascending item id.
+        ``exclude``: an ``ObservedPairs`` whose pairs are left out (``ops.rank_mask``), or None; rows with fewer than
+        ``n`` items left end in -1.  Users are scored in chunks, so the workspace stays bounded."""
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        num_users, num_items = self._table_sizes()
+        if exclude is not None and (exclude.num_users, exclude.num_items) != (num_users, num_items):
+            raise ValueError(f"exclude was built for {exclude.num_users} x {exclude.num_items}, the model is "
+                             f"{num_users} x {num_items}")
+        dev = self.GMF_Embedding_User.weight.device
+        u = _users_tensor(users, num_users, dev)
+        out = torch.full((u.numel(), n), -1, dtype=torch.int64, device=dev)
+        take = min(n, num_items)
+        chunk = max(1, min(_MAX_BATCH, _SCORE_CHUNK_FLOATS // num_items))
+        scorer = _GridScorer(self)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        place = torch.arange(take, device=dev)
+        for s in range(0, u.numel(), chunk):
+            rows = u[s:s + chunk]
+            scores = scorer(users=rows)
+            if exclude is not None:
+                off, ids = _excluded_rows(exclude, rows)
+                ops.rank_mask(scores, off, ids, err)
+            idx = ops.topk_rows(scores, take)
+            if exclude is not None:     # the masked items rank last: what lies past a row's survivors is padding
+                idx = idx.masked_fill(place[None, :] >= (num_items - off.diff())[:, None], -1)
+            out[s:s + chunk, :take] = idx
+        if exclude is not None and int(err.item()):
+            raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
+        return out
+
+
+def grid_path(tables, hidden, proj) -> str:
+    """how ``score_rows`` / ``score_grid`` / ``recommend`` score a model of these shapes (CPU tensors will do):
+    "grid" -- projected tables, folded head, then ``ctr_ncf_grid_scores`` -- where the library has that kernel,
+    else "forward": the per-sample forward over ids generated chunk by chunk"""
+    return "grid" if ops.ncf_grid_supported(tables, hidden, proj) else "forward"
+
+
+_FORWARD_CHUNK = 1 << 20     # pairs per forward call of the "forward" path
+
+
+def _excluded_rows(observed, users):
+    """the rows ``users`` of an ``ObservedPairs`` as the CSR ``ops.rank_mask`` takes: (offsets (len + 1), ids) int64"""
+    lo = observed.indptr[users]
+    lens = observed.indptr[users + 1] - lo
+    off = torch.zeros(users.numel() + 1, dtype=torch.int64, device=users.device)
+    torch.cumsum(lens, 0, out=off[1:])
+    row = torch.repeat_interleave(torch.arange(users.numel(), device=users.device), lens)
+    at = torch.arange(row.numel(), device=users.device) - off[row] + lo[row]
+    return off, observed.indices[at].to(torch.int64)
+
+
+class _GridScorer:
+    """score rows of the user x item grid of one model: what does not depend on the rows -- the projected tables and the
+    folded head of the "grid" path -- is made once, here, and not once per chunk"""
+
+    def __init__(self, model: NeuralCF):
+        self.model = model
+        p = model._params()
+        self.tables = tuple(t.detach() for t in p.tables)
+        model._need_device(self.tables[0])
+        self.path = grid_path(p.tables, p.hidden, p.proj)
+        if self.path == "grid":
+            gmf_u, gmf_i, mlp_u, mlp_i = self.tables
+            half = mlp_u.shape[1]
+            w0, b0 = p.hidden[0].weight.detach(), p.hidden[0].bias.detach()
+            self.p_u = ops.linear_fwd(mlp_u, w0[:, :half], None)
+            self.p_i = ops.linear_fwd(mlp_i, w0[:, half:], b0)
+            self.layers = [Layer(layer.weight.detach(), layer.bias.detach(), layer.act) for layer in p.hidden[1:]]
+            self.wfold, self.cfold = ops.fold_head_fwd(p.head[0].detach(), gmf_u.shape[1], p.proj[0].detach(),
+                                                       p.proj[1].detach(), p.head[1].detach())
+
+    def __call__(self, users=None, start=0, stop=None) -> torch.Tensor:
+        """(rows, num_items) float32, fresh: the rows of ``users`` (validated 1-D int64 device tensor) or of the users
+        [start, stop)"""
+        gmf_u, gmf_i = self.tables[:2]
+        rows, ni = (users.numel() if users is not None else stop - start), gmf_i.shape[0]
+        if self.path == "grid":
+            return ops.ncf_grid_scores(self.p_u, self.p_i, gmf_u, gmf_i, self.layers, self.wfold, self.cfold,
+                                       users=users, user0=start, rows=rows, act=ACT_SIGMOID)
+        out = torch.empty((rows, ni), dtype=torch.float32, device=gmf_u.device)
+        flat = out.view(-1)
+        for lo in range(0, rows * ni, _FORWARD_CHUNK):
+            k = torch.arange(lo, min(lo + _FORWARD_CHUNK, rows * ni), device=gmf_u.device)
+            r = torch.div(k, ni, rounding_mode="floor")
+            flat[lo:lo + k.numel()] = self.model.forward(users[r] if users is not None else r + start, k - r * ni).view(-1)
+        return out

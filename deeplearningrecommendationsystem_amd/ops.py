@@ -846,6 +846,68 @@ class NcfProj:
 
 
 # ---------------------------------------------------------------------------
+# NeuralCF over the user x item grid (csrc/ncf_grid.hip)
+# ---------------------------------------------------------------------------
+def ncf_grid_supported(tables, hidden, proj) -> bool:
+    """whether ``ctr_ncf_grid_scores`` takes the model: the shape test of ``NcfProj.supported`` without the batch and
+    without the row cap (both belong to the training plan).  A function of shapes alone: CPU or meta tensors will do."""
+    gmf_u, gmf_i, mlp_u, mlp_i = tables
+    dims = [tuple(layer.weight.shape) for layer in hidden]
+    return (dims == [(64, 128), (32, 64), (16, 32), (8, 16)] and gmf_u.shape[1] == 64 and mlp_u.shape[1] == 64 and
+            tuple(proj[0].shape) == (64, 8) and all(layer.bias is not None for layer in hidden) and
+            1 <= gmf_u.shape[0] < 2 ** 31 and 1 <= gmf_i.shape[0] < 2 ** 31)
+
+
+def ncf_grid_scores(p_u: torch.Tensor, p_i: torch.Tensor, gmf_u: torch.Tensor, gmf_i: torch.Tensor,
+                    layers: Sequence[Layer], wfold: torch.Tensor, cfold: torch.Tensor,
+                    users: Optional[torch.Tensor] = None, user0: int = 0, rows: Optional[int] = None,
+                    act: int = ACT_SIGMOID, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows, num_items) float32: ``act([gmf_u[u] * gmf_i[i] | tower(relu(p_u[u] + p_i[i]))] . wfold + cfold)`` for the
+    users ``users`` (1-D int64, validated by the caller) or ``user0 .. user0 + rows`` against every item
+    (ctr_ncf_grid_scores).  ``p_u`` / ``p_i``: the first tower layer applied to the table rows, ``layers`` the remaining
+    ones, ``wfold`` / ``cfold`` from ``fold_head_fwd``.  A shape the kernel is not built for raises: there is no
+    other path behind this call (``ncf_grid_supported`` says beforehand)."""
+    p_u, p_i, gmf_u, gmf_i = (_mat(t, w).contiguous() for t, w in ((p_u, "p_u"), (p_i, "p_i"), (gmf_u, "gmf_u"),
+                                                                    (gmf_i, "gmf_i")))
+    _lib.require_device(wfold, cfold)
+    nu, ni = gmf_u.shape[0], gmf_i.shape[0]
+    if p_u.shape[0] != nu or p_i.shape[0] != ni:
+        raise ValueError("ncf_grid_scores: the projected tables and the GMF tables differ in rows")
+    if users is not None:
+        _i64(users)
+        if users.dim() != 1:
+            raise ValueError("ncf_grid_scores: users must be 1-D")
+        rows, user0 = users.numel(), 0
+    elif rows is None:
+        rows = nu - user0
+    if out is None:
+        out = torch.empty((rows, ni), dtype=torch.float32, device=gmf_u.device)
+    out = _mat(out, "out")
+    if out.shape != (rows, ni):
+        raise ValueError(f"ncf_grid_scores: out must be ({rows}, {ni})")
+    arr = (_lib.MlpLayer * len(layers))()
+    for k, layer in enumerate(layers):
+        w = layer.weight
+        if not w.is_contiguous():
+            raise ValueError("ncf_grid_scores: tower weights must be contiguous")
+        arr[k].w, arr[k].b, arr[k].n, arr[k].k, arr[k].act = w.data_ptr(), _lib.ptr(layer.bias), w.shape[0], w.shape[1], layer.act
+    tower = sum(layer.weight.numel() for layer in layers)
+    mf, width = gmf_u.shape[1], p_u.shape[1]
+    fold_k = wfold.numel() - mf
+    # algorithmic: every table row of the call read once (the user tiles re-read item rows from cache), the scores
+    # written; per pair the tower, the relu'd sum of the projected rows and the mf + fold_k term dot
+    rc = _timed("ncf_grid_scores",
+                lambda: (4 * ((rows + ni) * (width + mf) + rows * ni) + (8 * rows if users is not None else 0),
+                         rows * ni * (2 * tower + 2 * (mf + fold_k) + width)),
+                _lib.load().ctr_ncf_grid_scores, p_u.data_ptr(), p_i.data_ptr(), gmf_u.data_ptr(), gmf_i.data_ptr(),
+                nu, ni, mf, width, arr, len(layers), wfold.data_ptr(), cfold.data_ptr(), fold_k,
+                _lib.ptr(users) if users is not None and rows else None, user0, rows, act,
+                _lib.ptr(out) if out.numel() else None, _ld(out) if rows else ni, _lib.stream_ptr())
+    _lib.check(rc, "ctr_ncf_grid_scores")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # feature interactions
 # ---------------------------------------------------------------------------
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112

@@ -523,6 +523,27 @@ int ctr_ncf_proj_workspace_floats(int64_t batch, int64_t num_users, int64_t num_
 int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream);
 int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad_t* g, void* stream);
 
+/* NeuralCF over the user x item grid (csrc/ncf_grid.hip): the scores of `rows` users against EVERY item in one launch,
+ * with no id tensor:
+ *   out[r * ldo + i] = act([gmf_user[u_r] * gmf_item[i] | tower(relu(p_user[u_r] + p_item[i]))] . wfold + cfold[0])
+ *   u_r = users[r] (users set: any order, repeats allowed) or user0 + r (users NULL; user0 + rows <= num_users)
+ * p_user (num_users, width) / p_item (num_items, width) are the first tower layer applied to the table rows
+ * (MLP_U W0a^T and MLP_I W0b^T + b0: two ctr_linear_fwd), `layers` the nlayers REMAINING tower layers (w, b, n, k, act
+ * read; rows of w contiguous), wfold (mf_dim + fold_k) / cfold (1) what ctr_fold_head_fwd writes.
+ * Pattern, the one of ctr_ncf_proj_fwd (anything else: CTR_ELIMIT, nothing enqueued): mf_dim == width == 64, layers
+ * 64->32, 32->16, 16->8 all ReLU with biases, fold_k == 8; num_users, num_items < 2^31.  There is NO cap on the table
+ * rows (CTR_NCF_PROJ_MAX_ROWS belongs to the training plan).  Tables and weights 16-byte aligned (CTR_EALIGN).
+ * out is (rows, num_items) float32 with row stride ldo >= num_items; columns past num_items are not touched.
+ * A null table, layer array, wfold or cfold, ldo < num_items, a negative count or a row range outside the user table
+ * is CTR_EINVAL before anything is enqueued; rows == 0 or num_items == 0 enqueues nothing and returns CTR_OK.  The
+ * caller validates `users`: an id outside [0, num_users) is clamped into the table, not reported.  No atomics; a
+ * pair's score is a function of its two table rows and the weights alone, bitwise, whatever the rows or their order. */
+int ctr_ncf_grid_scores(const float* p_user, const float* p_item, const float* gmf_user, const float* gmf_item,
+                        int64_t num_users, int64_t num_items, int mf_dim, int width,
+                        const ctr_mlp_layer_t* layers, int nlayers, const float* wfold, const float* cfold, int fold_k,
+                        const int64_t* users /*nullable*/, int64_t user0, int64_t rows, int act,
+                        float* out, int64_t ldo, void* stream);
+
 /* gy: gradient of the LAST layer's output; gx (nullable): gradient of x.  workspace is
  * required: (number of workgroups <= 256) * sum_i (n_i*k_i + n_i) floats. */
 int ctr_mlp_bwd(const float* x, int64_t ldx, int64_t m, const ctr_mlp_layer_t* layers, int nlayers,
