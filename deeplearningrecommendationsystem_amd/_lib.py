@@ -199,6 +199,7 @@ SIGNATURES = {
     "ctr_ncf_proj_bwd": (_i, [C.POINTER(NcfProj), C.POINTER(NcfProjGrad), _p]),
     "ctr_ncf_grid_scores": (_i, [_p, _p, _p, _p, _l, _l, _i, _i, C.POINTER(MlpLayer), _i, _p, _p, _i, _p, _l, _l, _i,
                                  _p, _l, _p]),
+    "ctr_din_grid_pool": (_i, [_p, _l, _i, _p, _p, _i, _p, _p, _p, _i, _i, _p, _l, _i, _p, _l, _p, _p]),
     "ctr_mlp_bwd": (_i, [_p, _l, _l, C.POINTER(MlpLayer), _i, _p, _l, _p, _l, _p, _l, _p]),
     "ctr_negative_sample": (_i, [_p, _l, _l, _l, _i, C.c_uint64, _p, _p, _p, _p]),
     "ctr_assemble_features": (_i, [_p, _p, _l, _p, _i, _l, _p, _i, _l, _p, _l, _p, _p]),

@@ -10,8 +10,9 @@ from torch.nn.init import xavier_normal_
 
 from .. import ops
 from .._lib import FIELD_ID_I64
+from ..cf import _MAX_BATCH, _SCORE_CHUNK_FLOATS
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
-from ._base import CtrModule, Params
+from ._base import CtrModule, Params, _excluded_rows
 
 # the history gradient of the E-wide attention leaves the first layer's dX GEMM as atomics on the table gradient
 # (ctr_linear_dx_scatter); CTR_DIN_FUSED_SCATTER=0 keeps the two-pass form (dX to memory, seq_scatter) for A/B
@@ -269,3 +270,171 @@ class DIN(SequenceModel):
 
     def recommendation(self, num_users, num_items, hist_list, k):
         return self._rank_histories(num_users, num_items, hist_list, k)
+
+    # ---- the history x item grid: a row scorer and a bounded-workspace ranker (no gradients, training paths untouched)
+    def _grid_table(self):
+        if self.sharded:
+            raise ValueError("the history x item grid wants the whole item table on one device: sharded=True models "
+                             "are not scored this way")
+        return self.item_embedding.weight
+
+    @torch.no_grad()
+    def score_histories(self, hist: torch.Tensor) -> torch.Tensor:
+        """(R, num_items) float32 device tensor, fresh and row-major: the probability of every item after each of the
+        R history rows of ``hist`` (R, L) int64.  The whole matrix is returned -- the caller chose the rows -- while
+        the workspace beyond it is bounded: the rows are walked ``_PAIR_CHUNK`` pairs at a time.  An id outside the
+        table raises IndexError."""
+        self._grid_table()
+        _check_hist(hist)
+        out = _HistoryScorer(self)(hist)
+        self.check_bad_index()
+        return out
+
+    def history_scorer(self, history: torch.Tensor):
+        """``scores(start, stop)`` -> ``score_histories(history[start:stop])``, the callable ``ranking_metrics`` takes;
+        ``history`` (U, L): one row per user (what ``DeviceLoader.sequences`` takes).  What does not depend on the
+        rows is made once per call of the returned function, not once per chunk."""
+        self._grid_table()
+        _check_hist(history)
+
+        def scores(start, stop):
+            start, stop = int(start), int(stop)
+            if not 0 <= start <= stop <= history.shape[0]:
+                raise IndexError(f"rows [{start}, {stop}) are outside [0, {history.shape[0]})")
+            return self.score_histories(history[start:stop])
+        return scores
+
+    @torch.no_grad()
+    def recommend(self, hist: torch.Tensor, n: int = 20, exclude=None, users=None) -> torch.Tensor:
+        """(R, n) int64: the items with the highest probability after each history row, best first, ties by ascending
+        item id.  ``exclude``: an ``ObservedPairs`` whose pairs are left out (``ops.rank_mask``), or None; ``users``
+        (R,): the user of every row of ``hist`` in it (default ``arange(R)``, which then must equal
+        ``exclude.num_users``).  Rows with fewer than ``n`` items left end in -1.  Rows are scored in chunks, so the
+        workspace stays bounded."""
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        table = self._grid_table()
+        _check_hist(hist)
+        rows, num_items = hist.shape[0], table.shape[0]
+        dev = table.device
+        if users is not None:
+            users = torch.as_tensor(users, dtype=torch.int64, device=dev)
+            if users.dim() != 1 or users.numel() != rows:
+                raise ValueError(f"users must name the user of each of the {rows} history rows, got {tuple(users.shape)}")
+        if exclude is not None:
+            if exclude.num_items != num_items:
+                raise ValueError(f"exclude was built for {exclude.num_items} items, the model has {num_items}")
+            if users is None:
+                if exclude.num_users != rows:
+                    raise ValueError(f"exclude was built for {exclude.num_users} users, hist has {rows} rows: say "
+                                     "which user each row belongs to (users=)")
+                users = torch.arange(rows, device=dev)
+            elif rows and bool(((users < 0) | (users >= exclude.num_users)).any()):
+                raise ValueError(f"users outside the {exclude.num_users} users exclude was built for")
+        out = torch.full((rows, n), -1, dtype=torch.int64, device=dev)
+        take = min(n, num_items)
+        chunk = max(1, min(_MAX_BATCH, _SCORE_CHUNK_FLOATS // num_items))
+        scorer = _HistoryScorer(self)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        place = torch.arange(take, device=dev)
+        for s in range(0, rows, chunk):
+            scores = scorer(hist[s:s + chunk])
+            if exclude is not None:
+                off, ids = _excluded_rows(exclude, users[s:s + chunk])
+                ops.rank_mask(scores, off, ids, err)
+            idx = ops.topk_rows(scores, take)
+            if exclude is not None:     # the masked items rank last: what lies past a row's survivors is padding
+                idx = idx.masked_fill(place[None, :] >= (num_items - off.diff())[:, None], -1)
+            out[s:s + chunk, :take] = idx
+        self.check_bad_index()
+        if exclude is not None and int(err.item()):
+            raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
+        return out
+
+
+def grid_path(embed_size, attention_dims=ops.DIN_GRID_ATTENTION) -> str:
+    """how ``score_histories`` / ``recommend`` score a DIN of this embedding width: "grid" -- the split first attention
+    layer on the table rows, then ``ctr_din_grid_pool`` and the fc stack -- where the library has that kernel, else
+    "forward": the per-sample forward over ids generated chunk by chunk"""
+    return "grid" if ops.din_grid_supported(embed_size, attention_dims) else "forward"
+
+
+# pairs per chunk of the grid walk (at least one history row): beyond the scores a chunk holds the fc operand and the
+# activations ``mlp_fwd`` keeps, 4 * (2E + 256 + 128) B = 2 KiB a pair at E = 64 -- 256 MiB
+_PAIR_CHUNK = 1 << 17
+
+
+def _check_hist(hist):
+    if not isinstance(hist, torch.Tensor) or hist.dim() != 2 or hist.dtype != torch.int64 or not hist.is_cuda:
+        raise ValueError("expected hist (R, L) as an int64 tensor on the device, got "
+                         f"{tuple(hist.shape)} {hist.dtype} on {hist.device}" if isinstance(hist, torch.Tensor)
+                         else f"expected hist (R, L) as an int64 tensor on the device, got {type(hist).__name__}")
+    if hist.shape[1] == 0:
+        raise ValueError("expected hist (R, L) with L >= 1: an empty history has no attention")
+
+
+class _HistoryScorer:
+    """score history rows against every item of one DIN: what does not depend on the rows -- the two halves of the
+    split first attention layer and the item part AT, and the history part AH where the table is the smaller row set
+    -- is made once, here, and not once per chunk"""
+
+    def __init__(self, model: DIN):
+        self.model = model
+        p = model._params()
+        self.table = p.table.detach()
+        model._need_device(self.table)
+        num_items, dim = self.table.shape
+        self.flag = model._err_flag(self.table.device)
+        self.fc = [Layer(layer.weight.detach(), layer.bias.detach(), layer.act) for layer in p.fc]
+        self.path = grid_path(dim, [tuple(layer.weight.shape) for layer in p.att])
+        self.ah_table = None
+        if self.path == "grid":
+            att1, att2, att3 = p.att
+            w1 = att1.weight.detach()
+            self.wf = torch.empty((2, w1.shape[0], dim), dtype=torch.float32, device=self.table.device)
+            torch.add(w1[:, :dim], w1[:, dim:2 * dim], out=self.wf[0])        # Wa + Wb: the history part
+            torch.sub(w1[:, 2 * dim:], w1[:, dim:2 * dim], out=self.wf[1])    # Wc - Wb: the item part
+            self.at = ops.linear_fwd(self.table, self.wf[1], att1.bias.detach())
+            self.w2, self.b2 = att2.weight.detach().contiguous(), att2.bias.detach()
+            self.w3 = att3.weight.detach().reshape(-1)
+
+    def _ah(self, hist, positions):
+        """(AH, by position?) for the rows ``hist`` of a call over ``positions`` history positions: the projected table
+        where it has no more rows than that (made once), else the projection of the gathered history rows"""
+        num_items, dim = self.table.shape
+        if self.ah_table is None and num_items <= positions:
+            self.ah_table = ops.linear_fwd(self.table, self.wf[0], None)
+        if self.ah_table is not None:
+            return self.ah_table, False
+        hrows = torch.empty((hist.numel(), dim), dtype=torch.float32, device=hist.device)
+        ops.din_concat_fwd(self.table, hist, torch.zeros(hist.shape[0], dtype=torch.int64, device=hist.device), hrows,
+                           None, self.flag, h_only=True)
+        return ops.linear_fwd(hrows, self.wf[0], None), True
+
+    def __call__(self, hist) -> torch.Tensor:
+        """(R, num_items) float32, fresh: the rows of ``hist`` (validated (R, L) int64 device tensor)"""
+        hist = hist.contiguous()
+        rows, length = hist.shape
+        num_items, dim = self.table.shape
+        dev = self.table.device
+        out = torch.empty((rows, num_items), dtype=torch.float32, device=dev)
+        if rows == 0:
+            return out
+        if self.path == "grid":
+            per = max(1, _PAIR_CHUNK // num_items)
+            for s in range(0, rows, per):
+                part = hist[s:s + per]
+                fcin = torch.empty((part.shape[0] * num_items, 2 * dim), dtype=torch.float32, device=dev)
+                fcin.view(part.shape[0], num_items, 2 * dim)[:, :, dim:] = self.table
+                ah, by_position = self._ah(part, hist.numel())
+                ops.din_grid_pool(self.table, self.at, ah, self.w2, self.b2, self.w3, part, out=fcin[:, :dim],
+                                  ah_by_position=by_position, err_flag=self.flag)
+                # the stage a fused kernel would take over: the fc stack on the (pairs, 2E) operand
+                ops.mlp_fwd(fcin, self.fc, last_out=out[s:s + per].view(-1, 1))
+            return out
+        flat = out.view(-1)
+        for lo in range(0, rows * num_items, _PAIR_CHUNK):
+            k = torch.arange(lo, min(lo + _PAIR_CHUNK, rows * num_items), device=dev)
+            r = torch.div(k, num_items, rounding_mode="floor")
+            flat[lo:lo + k.numel()] = self.model.forward(hist[r], k - r * num_items).view(-1)
+        return out

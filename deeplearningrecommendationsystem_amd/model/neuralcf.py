@@ -13,7 +13,7 @@ from .. import ops
 from ..cf import _MAX_BATCH, _SCORE_CHUNK_FLOATS, _users_tensor
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
 from .._lib import FIELD_ID_I64, FIELD_PROD_I64, CtrHipError
-from ._base import CtrModule
+from ._base import CtrModule, _excluded_rows
 
 # Vocabularies much smaller than the batch (BASELINE configs[1]: 943 + 1682 rows, batch 65536): the first tower layer
 # and its backward on the TABLE ROWS instead of the samples (csrc/ncf_proj.hip, ops.NcfProj).  CTR_NCF_PROJ=0 keeps the
@@ -422,17 +422,6 @@ def grid_path(tables, hidden, proj) -> str:
 
 
 _FORWARD_CHUNK = 1 << 20     # pairs per forward call of the "forward" path
-
-
-def _excluded_rows(observed, users):
-    """the rows ``users`` of an ``ObservedPairs`` as the CSR ``ops.rank_mask`` takes: (offsets (len + 1), ids) int64"""
-    lo = observed.indptr[users]
-    lens = observed.indptr[users + 1] - lo
-    off = torch.zeros(users.numel() + 1, dtype=torch.int64, device=users.device)
-    torch.cumsum(lens, 0, out=off[1:])
-    row = torch.repeat_interleave(torch.arange(users.numel(), device=users.device), lens)
-    at = torch.arange(row.numel(), device=users.device) - off[row] + lo[row]
-    return off, observed.indices[at].to(torch.int64)
 
 
 class _GridScorer:

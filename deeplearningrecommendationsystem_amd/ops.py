@@ -908,6 +908,64 @@ def ncf_grid_scores(p_u: torch.Tensor, p_i: torch.Tensor, gmf_u: torch.Tensor, g
 
 
 # ---------------------------------------------------------------------------
+# DIN over the history x item grid (csrc/din_grid.hip)
+# ---------------------------------------------------------------------------
+DIN_GRID_EMBED = 64
+DIN_GRID_ATTENTION = ((128, 3 * DIN_GRID_EMBED), (64, 128), (1, 64))
+
+
+def din_grid_supported(embed_size: int, attention_dims) -> bool:
+    """whether ``ctr_din_grid_pool`` takes a DIN of this embedding width whose attention ``Linear`` weights have the
+    shapes ``attention_dims`` ((out, in) per layer).  A function of shapes alone: CPU or meta tensors will do."""
+    return int(embed_size) == DIN_GRID_EMBED and tuple(tuple(int(v) for v in d) for d in attention_dims) == DIN_GRID_ATTENTION
+
+
+def din_grid_pool(table: torch.Tensor, at: torch.Tensor, ah: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                  w3: torch.Tensor, hist: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  ah_by_position: bool = False, err_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[r * I + i, :E] = sum_l softmax_l(w3 . relu(w2 relu(AH[r, l] + at[i]) + b2))[l] * table[hist[r, l]]`` for every
+    history row r of ``hist`` (R, L) and EVERY item i (ctr_din_grid_pool).  ``at`` (I, 128) is the item part of the first
+    attention layer, ``ah`` its history part: (I, 128) read by history id, or -- ``ah_by_position`` -- (R * L, 128) read
+    by position.  ``out``: (R * I, >= E) with a row stride that is a multiple of 4 floats (a view of the fc operand);
+    columns past E are left alone.  A shape the kernel is not built for raises: there is no other path behind this call
+    (``din_grid_supported`` says beforehand)."""
+    table, at, ah, w2 = (_mat(t, w) for t, w in ((table, "table"), (at, "at"), (ah, "ah"), (w2, "w2")))
+    _lib.require_device(b2, w3, err_flag)
+    _i64(hist)
+    if hist.dim() != 2 or hist.shape[1] < 1:
+        raise ValueError(f"din_grid_pool: hist must be (R, L) with L >= 1, got {tuple(hist.shape)}")
+    rows, length = hist.shape
+    ni, dim = table.shape
+    if not (table.is_contiguous() and at.is_contiguous() and ah.is_contiguous() and w2.is_contiguous()
+            and b2.is_contiguous() and w3.is_contiguous()):
+        raise ValueError("din_grid_pool: table, at, ah and the weights must be contiguous")
+    n2, n1 = w2.shape
+    if at.shape != (ni, n1) or ah.shape != ((rows * length) if ah_by_position else ni, n1):
+        raise ValueError(f"din_grid_pool: at {tuple(at.shape)} / ah {tuple(ah.shape)} do not fit {ni} items, "
+                         f"{rows} x {length} positions")
+    if b2.numel() != n2 or w3.numel() != n2:
+        raise ValueError("din_grid_pool: b2 and w3 must have one element per unit of w2")
+    if out is None:
+        out = torch.empty((rows * ni, dim), dtype=torch.float32, device=table.device)
+    out = _mat(out, "out")
+    if out.shape[0] != rows * ni or out.shape[1] < dim:
+        raise ValueError(f"din_grid_pool: out must be ({rows * ni}, >= {dim})")
+    if rows * ni == 0:
+        return out
+    # algorithmic: the table-side rows of the call read once (the row tiles re-read them from cache), the pooled rows
+    # written; per pair and position the 128 -> 64 layer, the relu'd sum, the score dot and the weighted sum
+    rc = _timed("din_grid_pool",
+                lambda: (4 * (ni * (dim + n1) + rows * length * (2 + n1 + dim) + rows * ni * dim),
+                         rows * ni * length * (2 * n1 * n2 + n1 + 2 * n2 + 2 * dim)),
+                _lib.load().ctr_din_grid_pool, table.data_ptr(), ni, dim, at.data_ptr(), ah.data_ptr(),
+                int(ah_by_position), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), n1, n2,
+                hist.data_ptr() if hist.numel() else None, rows, length, _lib.ptr(out) if out.numel() else None,
+                max(_ld(out), dim) if out.shape[0] else dim, _lib.ptr(err_flag), _lib.stream_ptr())
+    _lib.check(rc, "ctr_din_grid_pool")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # feature interactions
 # ---------------------------------------------------------------------------
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112

@@ -544,6 +544,24 @@ int ctr_ncf_grid_scores(const float* p_user, const float* p_item, const float* g
                         const int64_t* users /*nullable*/, int64_t user0, int64_t rows, int act,
                         float* out, int64_t ldo, void* stream);
 
+/* DIN over the history x item grid (csrc/din_grid.hip): the attention-pooled history of `rows` history rows against
+ * EVERY item in one launch, with no id tensor and nothing written per history position:
+ *   s[l]   = w3 . relu(w2 relu(AH[r, l] + at[i]) + b2)            (n1 = 128 -> n2 = 64 -> 1; the score bias drops out)
+ *   out[(r * num_items + i) * ldo + 0:embed] = sum_l softmax_l(s)[l] table[hist[r * len + l]]      (no padding mask)
+ *   AH[r, l] = ah[hist[r * len + l]] (ah_by_position == 0: ah is (num_items, n1)) or ah[r * len + l] (!= 0: ah is
+ *   (rows * len, n1), the projection of the gathered history rows)
+ * at (num_items, n1) = (Wc - Wb) table^T + b1 and ah = (Wa + Wb) h^T are two ctr_linear_fwd of the caller's; all
+ * matrices are dense row-major.  Admitted: embed == 64, n1 == 128, n2 == 64, len >= 1, num_items < 2^31, ldo >= embed
+ * and a multiple of 4, table / at / ah / w2 / out 16-byte aligned; anything else, or a null pointer, is CTR_EINVAL
+ * before anything is enqueued.  rows == 0 or num_items == 0 enqueues nothing and returns CTR_OK.  Columns past `embed`
+ * of a row of out are not touched.  A history id outside [0, num_items) is read as row 0 and sets *err_flag (nullable)
+ * to 1, the convention of ctr_din_concat_fwd.  No atomics; a pair's row is a function of its history row, its item
+ * and the weights alone, bitwise, whatever the rows, their order or the items' positions. */
+int ctr_din_grid_pool(const float* table, int64_t num_items, int embed, const float* at, const float* ah,
+                      int ah_by_position, const float* w2, const float* b2, const float* w3, int n1, int n2,
+                      const int64_t* hist, int64_t rows, int len, float* out, int64_t ldo, int32_t* err_flag,
+                      void* stream);
+
 /* gy: gradient of the LAST layer's output; gx (nullable): gradient of x.  workspace is
  * required: (number of workgroups <= 256) * sum_i (n_i*k_i + n_i) floats. */
 int ctr_mlp_bwd(const float* x, int64_t ldx, int64_t m, const ctr_mlp_layer_t* layers, int nlayers,
