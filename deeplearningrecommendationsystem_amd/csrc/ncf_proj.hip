@@ -354,12 +354,23 @@ struct Fwd {
 //
 // LDS-DMA and its waits are written by hand (the compiler cannot see which bytes an LDS-DMA writes and would wait for
 // every load in front of every LDS read).  Vector-memory operations retire in issue order; per group a wave issues
-//   [kDma row fetches] [2 id loads] [kStores stores]
+//   [kDma row fetches] [register loads, the forward's GMF rows] [2 id loads] [kStores stores]
 // so `vmcnt(kStores)` at the head of the next group means: its rows are staged and its successor's ids are here, while
-// this group's stores may still be on their way.
-constexpr int kFwdStage = 4 * 16 * 64;   // floats per wave: P_U, P_I, GMF_U, GMF_I rows of sixteen samples
+// this group's stores may still be on their way.  (The compiler counts the register loads itself; it does not see the
+// LDS-DMA fetches, which are older than anything it waits for, so its count can only be too careful, never too lax.)
+//
+// Only rows that become MATRIX OPERANDS go through the stage.  The forward's GMF rows feed the head's scalar
+// sum_k wfold[k] GMF_U[u][k] GMF_I[i][k] alone: they are loaded into registers with the DMA's address pattern (sixteen
+// lanes per row, four rows per instruction), multiplied where they land and summed over the sixteen lanes of their row
+// (row_sum16).  That halves the stage -- per group 8 KB less written into LDS and 8 KB less read back, of the 76 KB a
+// group moved through it (44 KB of weight operands, 16 + 16 KB of rows); the workgroup's LDS is
+// (2816 + 128 + 80 + 4 x 2048) x 4 B = 44.9 KB.  Round 9 measured the forward 1.0-1.3 us faster for it
+// (profiles/r09_ncf_fwd_two_waves.txt, where the geometries that did NOT pay are recorded as well: see kFwdWgs).
+constexpr int kFwdStage = 2 * 16 * 64;   // floats per wave: P_U, P_I rows of sixteen samples
 constexpr int kFwdStores = 5;            // y1 x 2, y2, y3, prob
 
+// Two waves per SIMD: one of a per-sample workgroup and one of a plan workgroup.  The attribute is an ALLOCATION as
+// well as a budget: the compiler pads the kernel (134 registers) to 169 so that a third wave can never join.
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -377,7 +388,7 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   const int64_t groups = (m + 15) / 16;
   const int64_t wave0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6, nwaves = ((int64_t)F.plan.first * kThreads) >> 6;
   const uint32_t nu = (uint32_t)F.ids.nu, ni = (uint32_t)F.ids.ni;
-  const float* tabs[4] = {F.ptab, F.ptab + F.ids.nu * kN0, F.gmf_u, F.gmf_i};
+  const float* tabs[2] = {F.ptab, F.ptab + F.ids.nu * kN0};
   // stage 1: the two ids of this lane's sample (sample n of the group, the same in its four lanes)
   int64_t idu = 0, idi = 0;
   auto issue_ids = [&](int64_t g) {
@@ -386,25 +397,41 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
     idu = F.ids.uidx[row * F.ids.ustride];
     idi = F.ids.iidx[row * F.ids.istride];
   };
-  // stage 2: the four rows of every sample of the group by LDS-DMA.  Instruction k of a table moves
-  // rows 4k .. 4k+3: lane l fetches chunk (l % 16) ^ row of row 4k + l / 16 into slot (row, l % 16).
+  // stage 2: the four rows of every sample of the group.  Instruction k of a table moves rows 4k .. 4k+3, sixteen
+  // lanes per row.  The projected rows by LDS-DMA: lane l fetches chunk (l % 16) ^ row of row 4k + l / 16 into slot
+  // (row, l % 16).  The GMF rows into registers: lane l takes chunk l % 16 (columns 4 (l % 16) ..) of row 4k + l / 16.
+  f32x4 gu[4], gi[4];
   auto issue_rows = [&](int64_t g) {
     const bool live = g * 16 + n < m;
     const bool ubad = (uint64_t)idu >= nu, ibad = (uint64_t)idi >= ni;
     const uint32_t u = ubad ? 0u : (uint32_t)idu, i = ibad ? 0u : (uint32_t)idi;
     if (live && (ubad || ibad) && F.err_flag) *F.err_flag = 1;
+    uint32_t ur[4], ir[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int r = 4 * k + q;                          // the row this lane helps to fetch
       const int src = (lane & 48) | r;                  // a lane of this quarter that holds sample r's ids
-      const uint32_t ur = (uint32_t)__shfl((int)u, src, 64), ir = (uint32_t)__shfl((int)i, src, 64);
+      ur[k] = (uint32_t)__shfl((int)u, src, 64) * 64u;
+      ir[k] = (uint32_t)__shfl((int)i, src, 64) * 64u;
       const uint32_t col = 4u * (uint32_t)(n ^ r);      // swizzled 16-byte chunk of the row
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float* g_ = tabs[t] + ((t & 1) ? ir : ur) * 64u + col;
+      for (int t = 0; t < 2; ++t) {
+        const float* g_ = tabs[t] + (t ? ir[k] : ur[k]) + col;
         ctr_dma16(g_, stage_addr + (uint32_t)((t * 16 + 4 * k) * 256));
       }
     }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      gu[k] = ldg4(F.gmf_u + ur[k] + 4 * n);
+      gi[k] = ldg4(F.gmf_i + ir[k] + 4 * n);
+    }
+  };
+  // behind a hand-placed wait: the ids and the GMF rows are "used" here, so that the compiler places ITS wait for them
+  // in straight-line code where it can count the stores behind them, instead of a vmcnt(0) at the loop header (which
+  // is reached from two paths with different stores in flight)
+  auto arrived = [&]() {
+    asm volatile("" : "+v"(idu), "+v"(idi), "+v"(gu[0]), "+v"(gu[1]), "+v"(gu[2]), "+v"(gu[3]), "+v"(gi[0]), "+v"(gi[1]),
+                      "+v"(gi[2]), "+v"(gi[3]));
   };
   // operand of table t, input block j: row n, chunk (4j + q) ^ n
   auto staged = [&](int t, int j) {
@@ -430,27 +457,33 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   STAMP(0, stamp++);
   const float hc = s_hw[kHeadW];
   if (wave0 >= groups) return;
-  // the first group's rows: everything issued so far (no stores yet).  The ids are "used" right behind every hand-placed
-  // wait: the compiler then places ITS wait for them there, in straight-line code where it can count the stores behind
-  // them, instead of a vmcnt(0) at the loop header (which is reached from two paths with different stores in flight)
+  const f32x4 hwn = *reinterpret_cast<const f32x4*>(s_hw + 4 * n);   // head weights of this lane's GMF columns
+  // the first group's rows: everything issued so far (no stores yet)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("" : "+v"(idu), "+v"(idi));
+  arrived();
   for (int64_t g = wave0; g < groups; g += nwaves) {
     const int64_t row = g * 16 + n;
     const int64_t srow = row < m ? row : m;             // lanes without a sample store to the spare row m
     // staged rows of g -> operands
-    f32x4 a0[4], xe[4];
+    f32x4 a0[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const f32x4 z = staged(0, j) + staged(1, j);
 #pragma unroll
       for (int r = 0; r < 4; ++r) a0[j][r] = fmaxf(z[r], 0.0f);
     }
-    // the head's extra columns 16q .. 16q+15 of this sample: chunks 4q + i
+    // the head's GMF term: this lane's four columns of samples 4k + q, summed over the sixteen lanes of the row; the
+    // sum of sample n is load n / 4 of quarter n % 4, and goes to the sample's four lanes by one shuffle
+    float gdot = 0.0f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      xe[i] = *reinterpret_cast<const f32x4*>(stage + (2 * 16 + n) * 64 + 4 * ((4 * q + i) ^ n)) *
-              *reinterpret_cast<const f32x4*>(stage + (3 * 16 + n) * 64 + 4 * ((4 * q + i) ^ n));
+    for (int k = 0; k < 4; ++k) {
+      const f32x4 p = gu[k] * gi[k];
+      float part = p[0] * hwn[0];
+      part = fmaf(p[1], hwn[1], part); part = fmaf(p[2], hwn[2], part); part = fmaf(p[3], hwn[3], part);
+      part = row_sum16(part);
+      gdot = (n >> 2) == k ? part : gdot;
+    }
+    gdot = __shfl(gdot, ((n & 3) << 4) | n, 64);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the stage is read: it may be overwritten
     STAMP(0, stamp++);
     issue_rows(g + nwaves);
@@ -465,27 +498,21 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
     for (int b = 0; b < 2; ++b) stg4(T.y[0] + srow * T.ldy[0] + 16 * b + 4 * q, y1[b]);
     stg4(T.y[1] + srow * T.ldy[1] + 4 * q, y2[0]);
     stg4(T.y[2] + (q < 2 ? srow : m) * T.ldy[2] + 4 * (q & 1), y3[0]);
-    // head: prob = act([gmf | h] . wfold + cfold); the four lanes of a sample hold 16 + (q < 2 ? 4 : 0) terms each
-    float dot = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(s_hw + 16 * q + 4 * i);
-      dot = fmaf(xe[i][0], wv[0], dot); dot = fmaf(xe[i][1], wv[1], dot);
-      dot = fmaf(xe[i][2], wv[2], dot); dot = fmaf(xe[i][3], wv[3], dot);
-    }
+    // head: prob = act([gmf | h] . wfold + cfold); lanes q < 2 of a sample hold four terms of h each
+    float dot;
     {
       const f32x4 wv = *reinterpret_cast<const f32x4*>(s_hw + kP + 4 * (q & 1));
       float d2 = y3[0][0] * wv[0];
       d2 = fmaf(y3[0][1], wv[1], d2); d2 = fmaf(y3[0][2], wv[2], d2); d2 = fmaf(y3[0][3], wv[3], d2);
-      dot += q < 2 ? d2 : 0.0f;
+      dot = q < 2 ? d2 : 0.0f;
     }
     dot += __shfl_xor(dot, 16, 64);
     dot += __shfl_xor(dot, 32, 64);
-    F.out[srow * F.ldout] = ctr_act(dot + hc, F.act);   // (the four lanes of a sample agree)
+    F.out[srow * F.ldout] = ctr_act(gdot + dot + hc, F.act);   // (the four lanes of a sample agree)
     STAMP(0, stamp++);
     // the next group's rows and its successor's ids are older than this group's kFwdStores stores
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kFwdStores) : "memory");
-    asm volatile("" : "+v"(idu), "+v"(idi));
+    arrived();
   }
 }
 
@@ -1350,7 +1377,7 @@ extern "C" __attribute__((visibility("default"))) int ctr_ncfp_debug_stamps(unsi
 #endif
 
 // launch geometry (the round-3 sweeps that chose these values are in git history)
-constexpr int kFwdWgs = 256;        // per-sample workgroups of the forward, at most
+constexpr int kFwdWgs = 256;        // per-sample workgroups of the forward, at most: one per CU (round 9 measured 512)
 constexpr int kBwdWgs = 256;        // per-sample workgroups of the backward, at most: one slab each
 constexpr int kSlabsMax = 768;      // workspace_floats() reserves slabs for this many backward workgroups
 static_assert(kBwdWgs <= kSlabsMax, "the backward's slabs must fit the workspace");
@@ -1408,13 +1435,21 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   if (rc != CTR_OK || d->batch == 0 || !(phases & 2)) return rc;
   const int64_t groups = ctr_ceil_div(d->batch, 16);
   int64_t grid = ctr_ceil_div(groups, kWaves);
-  // one workgroup per CU, every wave walks several groups: 25.6 us at batch 65536 against 28 us with two per CU
+  // one workgroup per CU, every wave walks several groups (four at batch 65536).  Two per CU -- a second wave per SIMD
+  // under whose matrix instructions a wave's row requests and head arithmetic could run -- were measured in round 9 and
+  // lost: a workgroup's prologue (ids -> rows -> staged weights, ~4800 of a wave's ~16500 cycles at two groups per
+  // wave) is paid twice as often, the launch grew by more than the waves' own lives shrank (supposed: twice the
+  // workgroups to launch), and in a training step the forward came to 13.4-13.8 us against 12.7-13.0 us this way
+  // (profiles/r09_ncf_fwd_two_waves.txt)
   if (grid > kFwdWgs) grid = kFwdWgs;
   // plan workgroups (training): a thread per table row, behind the per-sample ones
   const int64_t plan_blocks = ranks ? ctr_ceil_div(nu + ni, kThreads) : 0;
   const Fwd F{ids, d->ptab, d->gmf_user, d->gmf_item, d->wfold, d->prob, d->ldprob, d->head_act, d->err_flag,
               PlanJob{plan, (int)grid}};
   constexpr size_t fwd_lds = sizeof(float) * (kWFloats + kBFloats + 80 + kWaves * kFwdStage);
+  // the plan workgroups get the launch's dynamic LDS size like everyone else: a CU's 160 KB must hold one of them
+  // beside a per-sample workgroup, or the plan would wait for a per-sample workgroup to retire
+  static_assert(2 * fwd_lds <= 160 * 1024, "ncfp_fwd: a per-sample workgroup and a plan workgroup share a CU's LDS");
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)fwd_lds) != hipSuccess)
     return CTR_ELAUNCH;
