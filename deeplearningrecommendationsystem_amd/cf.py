@@ -24,13 +24,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, topn
 
 __all__ = ["ImplicitMatrix", "implicit_matrix", "UserCF", "ItemCF", "recall_precision_f1"]
-
-# recommend() scores users in chunks of at most this many float32 predictions (512 MB)
-_SCORE_CHUNK_FLOATS = 1 << 27
-_MAX_BATCH = 65535
 
 
 def _pad64(n: int) -> int:
@@ -88,15 +84,6 @@ def _knn(x: torch.Tensor, k: int):
     return idx[:, 1:].contiguous(), sim[:, 1:].contiguous()
 
 
-def _users_tensor(users, num_users: int, device) -> torch.Tensor:
-    if users is None:
-        return torch.arange(num_users, device=device)
-    u = torch.as_tensor(users, dtype=torch.int64).reshape(-1).to(device)
-    if u.numel() and (int(u.min()) < 0 or int(u.max()) >= num_users):
-        raise IndexError("a user id is outside [0, num_users)")
-    return u
-
-
 class _NeighbourCF:
     _scores = None   # ops.usercf_scores / ops.itemcf_scores
 
@@ -105,7 +92,7 @@ class _NeighbourCF:
             raise ValueError(f"k = {k}: the neighbour kernel keeps k + 1 <= {ops.CF_KNN_MAX_K} entries per row")
         self.k = k
         self.matrix: Optional[ImplicitMatrix] = None
-        self.neighbors = self.neighbor_sims = None
+        self.neighbors = self.neighbor_sims = self._unrated = None
 
     def _rows(self, matrix: ImplicitMatrix) -> torch.Tensor:
         raise NotImplementedError
@@ -113,6 +100,7 @@ class _NeighbourCF:
     def fit(self, matrix: ImplicitMatrix):
         self.matrix = matrix
         self.neighbors, self.neighbor_sims = _knn(self._rows(matrix), self.k)
+        self._unrated = matrix.num_items - matrix.counts.to(torch.int64)   # per user: the scores that are not -inf
         return self
 
     def _check_fitted(self):
@@ -123,9 +111,9 @@ class _NeighbourCF:
         """(len(users), num_items) float32 predictions, -inf on the items a user has rated"""
         self._check_fitted()
         m = self.matrix
-        u = _users_tensor(users, m.num_users, m.data.device)
-        outs = [type(self)._scores(m.data, m.num_items, self.neighbors, self.neighbor_sims, u[s:s + _MAX_BATCH])
-                for s in range(0, max(1, u.numel()), _MAX_BATCH)]
+        u = topn.users_tensor(users, m.num_users, m.data.device)
+        outs = [type(self)._scores(m.data, m.num_items, self.neighbors, self.neighbor_sims, u[s:s + topn.MAX_ROWS])
+                for s in range(0, max(1, u.numel()), topn.MAX_ROWS)]
         return outs[0] if len(outs) == 1 else torch.cat(outs)
 
     def recommend(self, users=None, n: int = 20) -> torch.Tensor:
@@ -135,16 +123,12 @@ class _NeighbourCF:
         if n < 1:
             raise ValueError("n must be at least 1")
         m = self.matrix
-        u = _users_tensor(users, m.num_users, m.data.device)
-        out = torch.full((u.numel(), n), -1, dtype=torch.int64, device=m.data.device)
-        take = min(n, m.num_items)
-        chunk = max(1, min(_MAX_BATCH, _SCORE_CHUNK_FLOATS // m.num_items))
-        for s in range(0, u.numel(), chunk):
-            scores = type(self)._scores(m.data, m.num_items, self.neighbors, self.neighbor_sims, u[s:s + chunk])
-            idx = ops.topk_rows(scores, take)
-            rated = torch.isneginf(scores.gather(1, idx))
-            out[s:s + chunk, :take] = idx.masked_fill(rated, -1)
-        return out
+        u = topn.users_tensor(users, m.num_users, m.data.device)
+
+        def chunk_scores(s, e):     # -inf on the rated items and on nothing else (csrc/knn_cf.hip)
+            scores = type(self)._scores(m.data, m.num_items, self.neighbors, self.neighbor_sims, u[s:e])
+            return scores, self._unrated[u[s:e]]
+        return topn.top_n(u.numel(), m.num_items, n, chunk_scores, m.data.device)
 
 
 class UserCF(_NeighbourCF):

@@ -22,6 +22,8 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from .. import ops, topn
+
 __all__ = ["Ranking", "remove_itemid", "itemid_matrix", "ranking_metrics", "ranking_partials", "RankingMetrics",
            "PARTIALS_COLUMNS"]
 
@@ -30,13 +32,6 @@ PARTIALS_COLUMNS = ("same", "rec", "real", "ap", "dcg", "idcg", "rr")   # the co
 
 _I64_MAX = torch.iinfo(torch.int64).max
 _I64_MIN = torch.iinfo(torch.int64).min
-_SCORE_CHUNK_FLOATS = 1 << 27   # ranking_metrics scores users in chunks of at most this many floats (512 MB)
-_MAX_CHUNK = 65535
-
-
-def _ops():
-    from .. import ops   # loads the HIP library; the module itself imports without a GPU
-    return ops
 
 
 def _device():
@@ -112,7 +107,6 @@ def _rows_of(x, device, num_rows=None) -> _Rows:
 
 
 def _check_err(err: torch.Tensor) -> None:
-    ops = _ops()
     e = int(err.item())
     if e & ops.RANK_ERR_SURVIVOR:
         raise ValueError("a score that survives the exclusions is NaN or -inf: it cannot be ranked against the "
@@ -152,7 +146,6 @@ def remove_itemid(recommendation_matrix, other_matrix):
     row ends up empty the result is a (rows, 0) float64 array, as the reference's.  The dtype is the reference's too:
     the ranking's own integer dtype when no row is padded, int64 (numpy's promotion with the -1 pads) when one is.  A
     device tensor in gives a device tensor out, anything else a numpy array."""
-    ops = _ops()
     dev = _device()
     on_device = isinstance(recommendation_matrix, torch.Tensor) and recommendation_matrix.is_cuda
     given = recommendation_matrix if isinstance(recommendation_matrix, torch.Tensor) else np.asarray(recommendation_matrix)
@@ -218,7 +211,6 @@ class Ranking:
 
     def _partials(self):
         if self._parts is None:
-            ops = _ops()
             dev = _device()
             if int(self.k) < 1:
                 raise ValueError(f"k = {self.k}: the evaluation needs k >= 1")
@@ -355,8 +347,7 @@ def ranking_partials(scores, real, k: int, exclude=(), chunk=None, num_users=Non
     ``(users, items)`` pairs (row u = user u's items).  The scores of items a user keeps must be finite or +inf: a
     NaN or -inf survivor raises ValueError (CF's ``predict()`` gives -inf only on rated items, which belong in an
     exclusion stage).  An empty actual row raises ZeroDivisionError, as its AP is undefined.  ``chunk`` users
-    are scored at a time (default: 512 MB of scores), so the workspace stays bounded."""
-    ops = _ops()
+    are scored at a time (default: ``topn.chunk_rows``, 512 MB of scores), so the workspace stays bounded."""
     dev = _device()
     if int(k) < 1:
         raise ValueError(f"k = {k}: the evaluation needs k >= 1")
@@ -385,7 +376,7 @@ def ranking_partials(scores, real, k: int, exclude=(), chunk=None, num_users=Non
     off_a, ids_a = act.csr()
     alen = act.lens.contiguous()
     kt = min(k, n)
-    chunk = chunk or max(1, min(_MAX_CHUNK, _SCORE_CHUNK_FLOATS // n))
+    chunk = chunk or topn.chunk_rows(n)
     buf = torch.empty((min(chunk, max(rows, 1)), n), dtype=torch.float32, device=dev) if table is not None else None
     parts = torch.empty((rows, 7), dtype=torch.float64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)

@@ -22,6 +22,8 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from .. import ops
+
 __all__ = ["GroupRankingMetrics", "group_ranks", "group_histogram", "group_ranking_metrics", "metrics_from_histogram"]
 
 
@@ -38,11 +40,6 @@ class GroupRankingMetrics(namedtuple("GroupRankingMetrics", "hr ndcg mrr_at mrr 
             lines.append(f"          - MRR@{c}: {self.mrr_at[c]}")
         lines.append(f"          - MRR: {self.mrr}")
         return "\n".join(lines)
-
-
-def _ops():
-    from .. import ops   # loads the HIP library; the module itself imports without a GPU
-    return ops
 
 
 def _groups(scores: torch.Tensor, negatives: int) -> torch.Tensor:
@@ -68,7 +65,7 @@ def _rank(scores, negatives, hist, want_ranks):
     if hist is None:
         hist = torch.zeros(k + 1, dtype=torch.int64, device=rows.device)
     ranks = torch.empty(rows.shape[0], dtype=torch.int32, device=rows.device) if want_ranks else None
-    _ops().group_rank(rows, k, hist, ranks)
+    ops.group_rank(rows, k, hist, ranks)
     return ranks, hist
 
 

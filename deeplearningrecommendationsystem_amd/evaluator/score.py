@@ -26,17 +26,12 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, ops
 from .evaluator import Evaluator
 
 __all__ = ["UserGroups", "GaucResult", "ScoreMetrics", "user_auc_counts", "gauc_from_counts", "score_metrics"]
 
 SMALL, SLAB, CHUNK = _lib.CTR_GAUC_SMALL, _lib.CTR_GAUC_SLAB, _lib.CTR_SCORE_CHUNK
-
-
-def _ops():
-    from .. import ops   # loads the HIP library; the module itself imports without a GPU
-    return ops
 
 
 class UserGroups:
@@ -135,7 +130,7 @@ def user_auc_counts(groups: UserGroups, y_true: torch.Tensor, y_pred: torch.Tens
     counts = torch.zeros((2, g), dtype=torch.int32, device=dev)
     u2 = torch.zeros(g, dtype=torch.int64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _ops().gauc_groups(p, y, groups.order, groups.offsets, groups.small_groups, groups.slab_group, groups.slab_first,
+    ops.gauc_groups(p, y, groups.order, groups.offsets, groups.small_groups, groups.slab_group, groups.slab_first,
                        counts[0], counts[1], u2, err)
     return counts[0], counts[1], u2
 
@@ -178,7 +173,7 @@ def score_metrics(y_true: torch.Tensor, y_pred: torch.Tensor, groups: UserGroups
         raise ValueError(f"groups must be the UserGroups of these {n} samples")
     counts = torch.zeros(8, dtype=torch.int64, device=p.device)
     sums = torch.empty((-(-n // CHUNK), 4), dtype=torch.float64, device=p.device)
-    _ops().score_counts(p, y, counts, sums)
+    ops.score_counts(p, y, counts, sums)
     gauc = gauc_from_counts(*user_auc_counts(groups, y, p)) if groups is not None else GaucResult(None, None, None, None)
     auc = Evaluator.score_auc(y, p)
     positives, negatives, tp, fp, fn, tn, bad, _ = (int(v) for v in counts.cpu().numpy())

@@ -20,8 +20,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import ops
-from .cf import _MAX_BATCH, _SCORE_CHUNK_FLOATS, ImplicitMatrix, _users_tensor
+from . import ops, topn
+from .cf import ImplicitMatrix
 
 __all__ = ["GDCF"]
 
@@ -81,17 +81,12 @@ class GDCF(torch.nn.Module):
         num_items = Q.shape[0]
         if exclude_rated and self.matrix is None:
             raise RuntimeError("exclude_rated needs the interaction matrix: call the model on it first")
-        u = _users_tensor(users, P.shape[0], P.device)
-        out = torch.full((u.numel(), n), -1, dtype=torch.int64, device=P.device)
-        take = min(n, num_items)
-        chunk = max(1, min(_MAX_BATCH, _SCORE_CHUNK_FLOATS // num_items))
-        for s in range(0, u.numel(), chunk):
-            rows = u[s:s + chunk]
-            scores = ops.linear_fwd(P.index_select(0, rows), Q, None)
-            if exclude_rated:
-                scores.masked_fill_(self.matrix.data.index_select(0, rows)[:, :num_items] != 0, float("-inf"))
-            idx = ops.topk_rows(scores, take)
-            if exclude_rated:
-                idx = idx.masked_fill(torch.isneginf(scores.gather(1, idx)), -1)
-            out[s:s + chunk, :take] = idx
-        return out
+        u = topn.users_tensor(users, P.shape[0], P.device)
+
+        def chunk_scores(s, e):
+            scores = ops.linear_fwd(P.index_select(0, u[s:e]), Q, None)
+            if not exclude_rated:
+                return scores, None
+            scores.masked_fill_(self.matrix.data.index_select(0, u[s:e])[:, :num_items] != 0, float("-inf"))
+            return scores, num_items - torch.isneginf(scores).sum(1)
+        return topn.top_n(u.numel(), num_items, n, chunk_scores, P.device)

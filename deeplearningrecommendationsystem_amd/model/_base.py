@@ -105,17 +105,6 @@ def topk_rows(scores: torch.Tensor, k: int) -> np.ndarray:
     return ops.topk_rows(scores, k).cpu().numpy()
 
 
-def _excluded_rows(observed, users):
-    """the rows ``users`` of an ``ObservedPairs`` as the CSR ``ops.rank_mask`` takes: (offsets (len + 1), ids) int64"""
-    lo = observed.indptr[users]
-    lens = observed.indptr[users + 1] - lo
-    off = torch.zeros(users.numel() + 1, dtype=torch.int64, device=users.device)
-    torch.cumsum(lens, 0, out=off[1:])
-    row = torch.repeat_interleave(torch.arange(users.numel(), device=users.device), lens)
-    at = torch.arange(row.numel(), device=users.device) - off[row] + lo[row]
-    return off, observed.indices[at].to(torch.int64)
-
-
 def _flatten(p):
     """named parameters -> (the tensors in the order autograd sees them, what ``_rebuild`` needs besides them).  An
     entry of ``p`` is a tensor, an ``ops.Layer`` (weight, then bias) or a list of entries."""

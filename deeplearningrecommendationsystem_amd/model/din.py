@@ -8,11 +8,10 @@ import torch
 import torch.nn as nn
 from torch.nn.init import xavier_normal_
 
-from .. import ops
+from .. import ops, topn
 from .._lib import FIELD_ID_I64
-from ..cf import _MAX_BATCH, _SCORE_CHUNK_FLOATS
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
-from ._base import CtrModule, Params, _excluded_rows
+from ._base import CtrModule, Params
 
 # the history gradient of the E-wide attention leaves the first layer's dX GEMM as atomics on the table gradient
 # (ctr_linear_dx_scatter); CTR_DIN_FUSED_SCATTER=0 keeps the two-pass form (dX to memory, seq_scatter) for A/B
@@ -331,21 +330,17 @@ class DIN(SequenceModel):
                 users = torch.arange(rows, device=dev)
             elif rows and bool(((users < 0) | (users >= exclude.num_users)).any()):
                 raise ValueError(f"users outside the {exclude.num_users} users exclude was built for")
-        out = torch.full((rows, n), -1, dtype=torch.int64, device=dev)
-        take = min(n, num_items)
-        chunk = max(1, min(_MAX_BATCH, _SCORE_CHUNK_FLOATS // num_items))
         scorer = _HistoryScorer(self)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        place = torch.arange(take, device=dev)
-        for s in range(0, rows, chunk):
-            scores = scorer(hist[s:s + chunk])
-            if exclude is not None:
-                off, ids = _excluded_rows(exclude, users[s:s + chunk])
-                ops.rank_mask(scores, off, ids, err)
-            idx = ops.topk_rows(scores, take)
-            if exclude is not None:     # the masked items rank last: what lies past a row's survivors is padding
-                idx = idx.masked_fill(place[None, :] >= (num_items - off.diff())[:, None], -1)
-            out[s:s + chunk, :take] = idx
+
+        def chunk_scores(s, e):
+            scores = scorer(hist[s:e])
+            if exclude is None:
+                return scores, None
+            off, ids = topn.excluded_rows(exclude, users[s:e])
+            ops.rank_mask(scores, off, ids, err)
+            return scores, num_items - off.diff()
+        out = topn.top_n(rows, num_items, n, chunk_scores, dev)
         self.check_bad_index()
         if exclude is not None and int(err.item()):
             raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
@@ -432,9 +427,5 @@ class _HistoryScorer:
                 # the stage a fused kernel would take over: the fc stack on the (pairs, 2E) operand
                 ops.mlp_fwd(fcin, self.fc, last_out=out[s:s + per].view(-1, 1))
             return out
-        flat = out.view(-1)
-        for lo in range(0, rows * num_items, _PAIR_CHUNK):
-            k = torch.arange(lo, min(lo + _PAIR_CHUNK, rows * num_items), device=dev)
-            r = torch.div(k, num_items, rounding_mode="floor")
-            flat[lo:lo + k.numel()] = self.model.forward(hist[r], k - r * num_items).view(-1)
+        topn.forward_grid(out, _PAIR_CHUNK, lambda r, i: self.model.forward(hist[r], i))
         return out

@@ -9,11 +9,10 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import loss as _loss
-from .. import ops
-from ..cf import _MAX_BATCH, _SCORE_CHUNK_FLOATS, _users_tensor
+from .. import ops, topn
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
 from .._lib import FIELD_ID_I64, FIELD_PROD_I64, CtrHipError
-from ._base import CtrModule, _excluded_rows
+from ._base import CtrModule
 
 # Vocabularies much smaller than the batch (BASELINE configs[1]: 943 + 1682 rows, batch 65536): the first tower layer
 # and its backward on the TABLE ROWS instead of the samples (csrc/ncf_proj.hip, ops.NcfProj).  CTR_NCF_PROJ=0 keeps the
@@ -348,13 +347,10 @@ class NeuralCF(CtrModule):
         (model/neuralcf.py:61-72; 943 forward calls of 1682 samples) from a few forward calls over
         the whole user x item grid, ``chunk`` pairs at a time, ranked on the device"""
         dev = self.GMF_Embedding_User.weight.device
-        users = torch.arange(num_users, device=dev).repeat_interleave(num_items)
-        items = torch.arange(num_items, device=dev).repeat(num_users)
-        scores = torch.empty(num_users * num_items, dtype=torch.float32, device=dev)
+        scores = torch.empty((num_users, num_items), dtype=torch.float32, device=dev)
         with torch.no_grad():
-            for lo in range(0, users.numel(), chunk):
-                scores[lo:lo + chunk] = self.forward(users[lo:lo + chunk], items[lo:lo + chunk]).view(-1)
-        return ops.topk_rows(scores.view(num_users, num_items), num_items).cpu().numpy()
+            topn.forward_grid(scores, chunk, self.forward)
+        return ops.topk_rows(scores, num_items).cpu().numpy()
 
     # ---- the user x item grid: row scorers and a bounded-workspace ranker (no gradients, training paths untouched)
     def _table_sizes(self):
@@ -378,7 +374,7 @@ class NeuralCF(CtrModule):
         num_users, _ = self._table_sizes()
         if users is None:
             return _GridScorer(self)(start=0, stop=num_users)
-        return _GridScorer(self)(users=_users_tensor(users, num_users, self.GMF_Embedding_User.weight.device))
+        return _GridScorer(self)(users=topn.users_tensor(users, num_users, self.GMF_Embedding_User.weight.device))
 
     @torch.no_grad()
     def recommend(self, users=None, n: int = 20, exclude=None) -> torch.Tensor:
@@ -392,23 +388,18 @@ class NeuralCF(CtrModule):
             raise ValueError(f"exclude was built for {exclude.num_users} x {exclude.num_items}, the model is "
                              f"{num_users} x {num_items}")
         dev = self.GMF_Embedding_User.weight.device
-        u = _users_tensor(users, num_users, dev)
-        out = torch.full((u.numel(), n), -1, dtype=torch.int64, device=dev)
-        take = min(n, num_items)
-        chunk = max(1, min(_MAX_BATCH, _SCORE_CHUNK_FLOATS // num_items))
+        u = topn.users_tensor(users, num_users, dev)
         scorer = _GridScorer(self)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        place = torch.arange(take, device=dev)
-        for s in range(0, u.numel(), chunk):
-            rows = u[s:s + chunk]
-            scores = scorer(users=rows)
-            if exclude is not None:
-                off, ids = _excluded_rows(exclude, rows)
-                ops.rank_mask(scores, off, ids, err)
-            idx = ops.topk_rows(scores, take)
-            if exclude is not None:     # the masked items rank last: what lies past a row's survivors is padding
-                idx = idx.masked_fill(place[None, :] >= (num_items - off.diff())[:, None], -1)
-            out[s:s + chunk, :take] = idx
+
+        def chunk_scores(s, e):
+            scores = scorer(users=u[s:e])
+            if exclude is None:
+                return scores, None
+            off, ids = topn.excluded_rows(exclude, u[s:e])
+            ops.rank_mask(scores, off, ids, err)
+            return scores, num_items - off.diff()
+        out = topn.top_n(u.numel(), num_items, n, chunk_scores, dev)
         if exclude is not None and int(err.item()):
             raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
         return out
@@ -453,9 +444,6 @@ class _GridScorer:
             return ops.ncf_grid_scores(self.p_u, self.p_i, gmf_u, gmf_i, self.layers, self.wfold, self.cfold,
                                        users=users, user0=start, rows=rows, act=ACT_SIGMOID)
         out = torch.empty((rows, ni), dtype=torch.float32, device=gmf_u.device)
-        flat = out.view(-1)
-        for lo in range(0, rows * ni, _FORWARD_CHUNK):
-            k = torch.arange(lo, min(lo + _FORWARD_CHUNK, rows * ni), device=gmf_u.device)
-            r = torch.div(k, ni, rounding_mode="floor")
-            flat[lo:lo + k.numel()] = self.model.forward(users[r] if users is not None else r + start, k - r * ni).view(-1)
+        topn.forward_grid(out, _FORWARD_CHUNK,
+                          lambda r, i: self.model.forward(users[r] if users is not None else r + start, i))
         return out

@@ -161,11 +161,12 @@ def _observed(nu, ni, seed=3):
 def _own_ranking(model, users, n, observed):
     """topk_rows of the kernel's own scores after rank_mask, -1 where the survivors run out"""
     from deeplearningrecommendationsystem_amd import ops
+    from deeplearningrecommendationsystem_amd.topn import excluded_rows
     ni = model.GMF_Embedding_Item.weight.shape[0]
     scores = model.score_grid(users)
     left = torch.full((scores.shape[0],), ni, dtype=torch.int64, device=DEV)
     if observed is not None:
-        off, ids = _neuralcf()._excluded_rows(observed, users)
+        off, ids = excluded_rows(observed, users)
         err = torch.zeros(1, dtype=torch.int32, device=DEV)
         ops.rank_mask(scores, off, ids, err)
         assert int(err.item()) == 0
@@ -205,7 +206,8 @@ def test_recommend_for_a_user_list_in_chunks(monkeypatch):
     users = torch.tensor([129, 0, 7, 7, 128, 1, 64] + list(range(100, 120)))
     whole = model.recommend(users, n=6, exclude=observed)
     assert torch.equal(whole, model.recommend(n=6, exclude=observed)[users.to(DEV)])
-    monkeypatch.setattr(_neuralcf(), "_SCORE_CHUNK_FLOATS", 5 * ni)          # five users at a time
+    from deeplearningrecommendationsystem_amd import topn
+    monkeypatch.setattr(topn, "SCORE_CHUNK_FLOATS", 5 * ni)                  # five users at a time
     assert torch.equal(model.recommend(users, n=6, exclude=observed), whole)
     assert torch.equal(model.recommend(users.tolist(), n=6, exclude=None), model.recommend(users, n=6))
 
