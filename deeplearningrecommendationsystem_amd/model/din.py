@@ -119,6 +119,87 @@ class SequenceModel(CtrModule):
                     out[part] = ops.topk_rows(scores, k).cpu().numpy()
         return out
 
+    # ---- the history x item grid: a row scorer and a bounded-workspace ranker (no gradients, training paths untouched);
+    # a model supplies its table through ``_params`` and its scorer through ``_grid_scorer``
+    def _grid_table(self):
+        if self.sharded:
+            raise ValueError("the history x item grid wants the whole item table on one device: sharded=True models "
+                             "are not scored this way")
+        return self._params().table
+
+    def _grid_scorer(self):
+        """the model's ``_HistoryScorer``: rows of histories (R, L) -> fresh (R, num_items) scores"""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def score_histories(self, hist: torch.Tensor) -> torch.Tensor:
+        """(R, num_items) float32 device tensor, fresh and row-major: the probability of every item after each of the
+        R history rows of ``hist`` (R, L) int64.  The whole matrix is returned -- the caller chose the rows -- while
+        the workspace beyond it is bounded: the rows are walked ``_PAIR_CHUNK`` pairs at a time.  An id outside the
+        table raises IndexError."""
+        self._grid_table()
+        _check_hist(hist)
+        out = self._grid_scorer()(hist)
+        self.check_bad_index()
+        return out
+
+    def history_scorer(self, history: torch.Tensor):
+        """``scores(start, stop)`` -> ``score_histories(history[start:stop])``, the callable ``ranking_metrics`` takes;
+        ``history`` (U, L): one row per user (what ``DeviceLoader.sequences`` takes).  What does not depend on the
+        rows is made once per call of the returned function, not once per chunk."""
+        self._grid_table()
+        _check_hist(history)
+
+        def scores(start, stop):
+            start, stop = int(start), int(stop)
+            if not 0 <= start <= stop <= history.shape[0]:
+                raise IndexError(f"rows [{start}, {stop}) are outside [0, {history.shape[0]})")
+            return self.score_histories(history[start:stop])
+        return scores
+
+    @torch.no_grad()
+    def recommend(self, hist: torch.Tensor, n: int = 20, exclude=None, users=None) -> torch.Tensor:
+        """(R, n) int64: the items with the highest probability after each history row, best first, ties by ascending
+        item id.  ``exclude``: an ``ObservedPairs`` whose pairs are left out (``ops.rank_mask``), or None; ``users``
+        (R,): the user of every row of ``hist`` in it (default ``arange(R)``, which then must equal
+        ``exclude.num_users``).  Rows with fewer than ``n`` items left end in -1.  Rows are scored in chunks, so the
+        workspace stays bounded."""
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        table = self._grid_table()
+        _check_hist(hist)
+        rows, num_items = hist.shape[0], table.shape[0]
+        dev = table.device
+        if users is not None:
+            users = torch.as_tensor(users, dtype=torch.int64, device=dev)
+            if users.dim() != 1 or users.numel() != rows:
+                raise ValueError(f"users must name the user of each of the {rows} history rows, got {tuple(users.shape)}")
+        if exclude is not None:
+            if exclude.num_items != num_items:
+                raise ValueError(f"exclude was built for {exclude.num_items} items, the model has {num_items}")
+            if users is None:
+                if exclude.num_users != rows:
+                    raise ValueError(f"exclude was built for {exclude.num_users} users, hist has {rows} rows: say "
+                                     "which user each row belongs to (users=)")
+                users = torch.arange(rows, device=dev)
+            elif rows and bool(((users < 0) | (users >= exclude.num_users)).any()):
+                raise ValueError(f"users outside the {exclude.num_users} users exclude was built for")
+        scorer = self._grid_scorer()
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+        def chunk_scores(s, e):
+            scores = scorer(hist[s:e])
+            if exclude is None:
+                return scores, None
+            off, ids = topn.excluded_rows(exclude, users[s:e])
+            ops.rank_mask(scores, off, ids, err)
+            return scores, num_items - off.diff()
+        out = topn.top_n(rows, num_items, n, chunk_scores, dev)
+        self.check_bad_index()
+        if exclude is not None and int(err.item()):
+            raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
+        return out
+
 
 class DIN(SequenceModel):
     """``DIN(num_items, embed_size)``; ``forward(hist (B,L) int64, target_item (B,) int64) -> (B,1)``.
@@ -270,81 +351,8 @@ class DIN(SequenceModel):
     def recommendation(self, num_users, num_items, hist_list, k):
         return self._rank_histories(num_users, num_items, hist_list, k)
 
-    # ---- the history x item grid: a row scorer and a bounded-workspace ranker (no gradients, training paths untouched)
-    def _grid_table(self):
-        if self.sharded:
-            raise ValueError("the history x item grid wants the whole item table on one device: sharded=True models "
-                             "are not scored this way")
-        return self.item_embedding.weight
-
-    @torch.no_grad()
-    def score_histories(self, hist: torch.Tensor) -> torch.Tensor:
-        """(R, num_items) float32 device tensor, fresh and row-major: the probability of every item after each of the
-        R history rows of ``hist`` (R, L) int64.  The whole matrix is returned -- the caller chose the rows -- while
-        the workspace beyond it is bounded: the rows are walked ``_PAIR_CHUNK`` pairs at a time.  An id outside the
-        table raises IndexError."""
-        self._grid_table()
-        _check_hist(hist)
-        out = _HistoryScorer(self)(hist)
-        self.check_bad_index()
-        return out
-
-    def history_scorer(self, history: torch.Tensor):
-        """``scores(start, stop)`` -> ``score_histories(history[start:stop])``, the callable ``ranking_metrics`` takes;
-        ``history`` (U, L): one row per user (what ``DeviceLoader.sequences`` takes).  What does not depend on the
-        rows is made once per call of the returned function, not once per chunk."""
-        self._grid_table()
-        _check_hist(history)
-
-        def scores(start, stop):
-            start, stop = int(start), int(stop)
-            if not 0 <= start <= stop <= history.shape[0]:
-                raise IndexError(f"rows [{start}, {stop}) are outside [0, {history.shape[0]})")
-            return self.score_histories(history[start:stop])
-        return scores
-
-    @torch.no_grad()
-    def recommend(self, hist: torch.Tensor, n: int = 20, exclude=None, users=None) -> torch.Tensor:
-        """(R, n) int64: the items with the highest probability after each history row, best first, ties by ascending
-        item id.  ``exclude``: an ``ObservedPairs`` whose pairs are left out (``ops.rank_mask``), or None; ``users``
-        (R,): the user of every row of ``hist`` in it (default ``arange(R)``, which then must equal
-        ``exclude.num_users``).  Rows with fewer than ``n`` items left end in -1.  Rows are scored in chunks, so the
-        workspace stays bounded."""
-        if n < 1:
-            raise ValueError("n must be at least 1")
-        table = self._grid_table()
-        _check_hist(hist)
-        rows, num_items = hist.shape[0], table.shape[0]
-        dev = table.device
-        if users is not None:
-            users = torch.as_tensor(users, dtype=torch.int64, device=dev)
-            if users.dim() != 1 or users.numel() != rows:
-                raise ValueError(f"users must name the user of each of the {rows} history rows, got {tuple(users.shape)}")
-        if exclude is not None:
-            if exclude.num_items != num_items:
-                raise ValueError(f"exclude was built for {exclude.num_items} items, the model has {num_items}")
-            if users is None:
-                if exclude.num_users != rows:
-                    raise ValueError(f"exclude was built for {exclude.num_users} users, hist has {rows} rows: say "
-                                     "which user each row belongs to (users=)")
-                users = torch.arange(rows, device=dev)
-            elif rows and bool(((users < 0) | (users >= exclude.num_users)).any()):
-                raise ValueError(f"users outside the {exclude.num_users} users exclude was built for")
-        scorer = _HistoryScorer(self)
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def chunk_scores(s, e):
-            scores = scorer(hist[s:e])
-            if exclude is None:
-                return scores, None
-            off, ids = topn.excluded_rows(exclude, users[s:e])
-            ops.rank_mask(scores, off, ids, err)
-            return scores, num_items - off.diff()
-        out = topn.top_n(rows, num_items, n, chunk_scores, dev)
-        self.check_bad_index()
-        if exclude is not None and int(err.item()):
-            raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
-        return out
+    def _grid_scorer(self):
+        return _HistoryScorer(self)
 
 
 def grid_path(embed_size, attention_dims=ops.DIN_GRID_ATTENTION) -> str:

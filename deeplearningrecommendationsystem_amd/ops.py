@@ -966,6 +966,68 @@ def din_grid_pool(table: torch.Tensor, at: torch.Tensor, ah: torch.Tensor, w2: t
 
 
 # ---------------------------------------------------------------------------
+# DIEN over the history x item grid (csrc/dien_grid.hip)
+# ---------------------------------------------------------------------------
+DIEN_GRID_EMBED = 16
+DIEN_GRID_ATTENTION = ((64, 3 * DIEN_GRID_EMBED), (32, 64), (1, 32))
+DIEN_GRID_KEEP = _lib.CTR_DIEN_GRID_KEEP     # history positions whose score waits in LDS; later ones are recomputed
+
+
+def dien_grid_supported(embed_size: int, attention_dims) -> bool:
+    """whether ``ctr_dien_grid_hidden`` takes a DIEN of this embedding (= GRU) width whose attention ``Linear`` weights
+    have the shapes ``attention_dims`` ((out, in) per layer).  A function of shapes alone: CPU or meta tensors will do."""
+    return (int(embed_size) == DIEN_GRID_EMBED
+            and tuple(tuple(int(v) for v in d) for d in attention_dims) == DIEN_GRID_ATTENTION)
+
+
+def dien_grid_hidden(at: torch.Tensor, hp: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                     b_ih: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor, hist: torch.Tensor,
+                     out: Optional[torch.Tensor] = None, hp_by_position: bool = False,
+                     err_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[r * I + i, :E]`` = the last state of DIEN's GRU (h_0 = 0) over the attention-weighted history row r of
+    ``hist`` (R, L) against EVERY item i (ctr_dien_grid_hidden).  ``at`` (I, 64) is the item part of the first attention
+    layer; ``hp`` = [AH | GX] (112 wide) its history part next to the GRU's input projection without bias: (I, 112)
+    read by history id, or -- ``hp_by_position`` -- (R * L, 112) read by position.  ``out``: (R * I, >= E) with a row
+    stride that is a multiple of 4 floats (a view of the fc operand); columns past E are left alone.  A shape the
+    kernel is not built for raises: there is no other path behind this call (``dien_grid_supported`` says beforehand)."""
+    at, hp, w2, w_hh = (_mat(t, w) for t, w in ((at, "at"), (hp, "hp"), (w2, "w2"), (w_hh, "w_hh")))
+    _lib.require_device(b2, w3, b_ih, b_hh, err_flag)
+    if any(t.dtype != torch.float32 for t in (b2, w3, b_ih, b_hh)):
+        raise ValueError("dien_grid_hidden: b2, w3, b_ih and b_hh must be float32")
+    _i64(hist)
+    if hist.dim() != 2 or hist.shape[1] < 1:
+        raise ValueError(f"dien_grid_hidden: hist must be (R, L) with L >= 1, got {tuple(hist.shape)}")
+    rows, length = hist.shape
+    if not all(t.is_contiguous() for t in (at, hp, w2, b2, w3, b_ih, w_hh, b_hh)):
+        raise ValueError("dien_grid_hidden: at, hp and the weights must be contiguous")
+    ni, (n2, n1) = at.shape[0], w2.shape
+    gates, dim = w_hh.shape
+    if gates != 3 * dim or at.shape[1] != n1 or hp.shape != ((rows * length) if hp_by_position else ni, n1 + gates):
+        raise ValueError(f"dien_grid_hidden: at {tuple(at.shape)} / hp {tuple(hp.shape)} / w_hh {tuple(w_hh.shape)} do "
+                         f"not fit {ni} items, {rows} x {length} positions")
+    if b2.numel() != n2 or w3.numel() != n2 or b_ih.numel() != gates or b_hh.numel() != gates:
+        raise ValueError("dien_grid_hidden: b2 and w3 must have one element per unit of w2, b_ih and b_hh one per row "
+                         "of w_hh")
+    if out is None:
+        out = torch.empty((rows * ni, dim), dtype=torch.float32, device=at.device)
+    out = _mat(out, "out")
+    if out.shape[0] != rows * ni or out.shape[1] < dim:
+        raise ValueError(f"dien_grid_hidden: out must be ({rows * ni}, >= {dim})")
+    if rows * ni == 0:
+        return out
+    # algorithmic: the table-side rows of the call read once (the row tiles re-read them from cache), the states
+    # written; per pair and position the 64 -> 32 layer, the relu'd sum, the score dot, the recurrent product and gates
+    rc = _timed("dien_grid_hidden",
+                lambda: (4 * (ni * n1 + rows * length * (2 + n1 + gates) + rows * ni * dim),
+                         rows * ni * length * (2 * n1 * n2 + n1 + 2 * n2 + 2 * dim * gates + 4 * gates)),
+                _lib.load().ctr_dien_grid_hidden, at.data_ptr(), hp.data_ptr(), int(hp_by_position), ni, dim,
+                w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), n1, n2, b_ih.data_ptr(), w_hh.data_ptr(), b_hh.data_ptr(),
+                hist.data_ptr(), rows, length, _lib.ptr(out), max(_ld(out), dim), _lib.ptr(err_flag), _lib.stream_ptr())
+    _lib.check(rc, "ctr_dien_grid_hidden")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # feature interactions
 # ---------------------------------------------------------------------------
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112

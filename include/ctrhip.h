@@ -562,6 +562,29 @@ int ctr_din_grid_pool(const float* table, int64_t num_items, int embed, const fl
                       const int64_t* hist, int64_t rows, int len, float* out, int64_t ldo, int32_t* err_flag,
                       void* stream);
 
+/* DIEN over the history x item grid (csrc/dien_grid.hip): the last GRU state of `rows` history rows against EVERY item
+ * in one launch, with no id tensor and nothing written per history position:
+ *   s[l]  = w3 . relu(w2 relu(AH[r, l] + at[i]) + b2)             (n1 = 64 -> n2 = 32 -> 1; the score bias drops out)
+ *   a     = softmax_l(s);   gi_l = a[l] GX[r, l] + b_ih;   gh = w_hh h + b_hh            (gate order r, z, n; h_0 = 0)
+ *   r = sig(gi_r + gh_r);  z = sig(gi_z + gh_z);  n = tanh(gi_n + r gh_n);  h <- (1 - z) n + z h
+ *   out[(r * num_items + i) * ldo + 0:embed] = h after the row's last position           (no padding mask)
+ *   [AH | GX][r, l] = hp[hist[r * len + l]] (hp_by_position == 0: hp is (num_items, n1 + 3 embed)) or hp[r * len + l]
+ *   (!= 0: hp is (rows * len, n1 + 3 embed), the projection of the gathered history rows)
+ * at (num_items, n1) = (Wc - Wb) table^T + b1 and hp = [Wa + Wb ; W_ih] h^T (no bias) are two ctr_linear_fwd of the
+ * caller's; all matrices are dense row-major.  The scores of the first CTR_DIEN_GRID_KEEP positions of a row wait in
+ * LDS for the recurrence, later ones are computed a second time (same instructions, same bits): any len >= 1 is taken.
+ * Admitted: embed == 16, n1 == 64, n2 == 32, num_items < 2^31, anything else is CTR_ELIMIT; a null pointer, a negative
+ * count, len < 1 or ldo < embed is CTR_EINVAL; at / hp / w2 / out not 16-byte aligned or ldo not a multiple of 4 is
+ * CTR_EALIGN -- all before anything is enqueued.  rows == 0 or num_items == 0 enqueues nothing and returns CTR_OK.
+ * Columns past `embed` of a row of out are not touched.  A history id outside [0, num_items) is read as row 0 and sets
+ * *err_flag (nullable) to 1, the convention of ctr_din_concat_fwd.  No atomics; a pair's row is a function of its
+ * history row, its item and the weights alone, bitwise, whatever the rows, their order or the items' positions. */
+#define CTR_DIEN_GRID_KEEP 128
+int ctr_dien_grid_hidden(const float* at, const float* hp, int hp_by_position, int64_t num_items, int embed,
+                         const float* w2, const float* b2, const float* w3, int n1, int n2, const float* b_ih,
+                         const float* w_hh, const float* b_hh, const int64_t* hist, int64_t rows, int len, float* out,
+                         int64_t ldo, int32_t* err_flag, void* stream);
+
 /* gy: gradient of the LAST layer's output; gx (nullable): gradient of x.  workspace is
  * required: (number of workgroups <= 256) * sum_i (n_i*k_i + n_i) floats. */
 int ctr_mlp_bwd(const float* x, int64_t ldx, int64_t m, const ctr_mlp_layer_t* layers, int nlayers,
