@@ -1028,6 +1028,71 @@ def dien_grid_hidden(at: torch.Tensor, hp: torch.Tensor, w2: torch.Tensor, b2: t
 
 
 # ---------------------------------------------------------------------------
+# DeepFM over the user x item grid (csrc/deepfm_grid.hip)
+# ---------------------------------------------------------------------------
+DEEPFM_GRID_HIDDEN = (256, 128, 1)          # hidden_units[1:]; hidden_units[0] is free (it is folded into the table rows)
+DEEPFM_GRID_ITEM_TILE = _lib.CTR_DEEPFM_GRID_ITEM_TILE     # items of a workgroup
+DEEPFM_GRID_USER_TILE = _lib.CTR_DEEPFM_GRID_USER_TILE     # users staged at a time
+
+
+def deepfm_grid_supported(hidden_units, embedding_dim) -> bool:
+    """whether ``ctr_deepfm_grid_scores`` takes a six-field DeepFM of these ``hidden_units`` and this embedding width.
+    A function of the two shapes alone."""
+    hidden = tuple(int(h) for h in hidden_units)
+    dim = int(embedding_dim)
+    return len(hidden) == 4 and hidden[0] >= 1 and hidden[1:] == DEEPFM_GRID_HIDDEN and 16 <= dim <= 128 and dim % 16 == 0
+
+
+def deepfm_grid_scores(zu: torch.Tensor, zi: torch.Tensor, su: torch.Tensor, si: torch.Tensor, a: torch.Tensor,
+                       b: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
+                       out_w: torch.Tensor, out_b: torch.Tensor, users: Optional[torch.Tensor] = None, user0: int = 0,
+                       rows: Optional[int] = None, out: Optional[torch.Tensor] = None, row_blocks: int = 0) -> torch.Tensor:
+    """(rows, num_items) float32: ``sigmoid(out_w[0] (a[u] + b[i] + <su[u], si[i]>) + out_w[1] relu(w3 . relu(w2
+    relu(zu[u] + zi[i]) + b2) + b3) + out_b)`` for the users ``users`` (1-D int64, validated by the caller) or ``user0 ..
+    user0 + rows`` against every item (ctr_deepfm_grid_scores).  ``row_blocks``: workgroups that share an item tile's
+    user tiles, 0 for the launch's own choice; the scores do not depend on it.  A shape the kernel is not built for
+    raises: there is no other path behind this call (``deepfm_grid_supported`` says beforehand)."""
+    zu, zi, su, si, w2 = (_mat(t, w).contiguous() for t, w in ((zu, "zu"), (zi, "zi"), (su, "su"), (si, "si"), (w2, "w2")))
+    vecs = [t.detach().reshape(-1).contiguous() for t in (a, b, b2, w3, b3, out_w, out_b)]
+    _lib.require_device(*vecs)
+    if any(t.dtype != torch.float32 for t in vecs):
+        raise ValueError("deepfm_grid_scores: a, b and the weights must be float32")
+    a, b, b2, w3, b3, out_w, out_b = vecs
+    nu, ni, dim = zu.shape[0], zi.shape[0], su.shape[1]
+    n2, n1 = w2.shape
+    if su.shape[0] != nu or a.numel() != nu or si.shape != (ni, dim) or b.numel() != ni:
+        raise ValueError("deepfm_grid_scores: the rows of a side differ in number, or su and si in width")
+    if zu.shape[1] != n1 or zi.shape[1] != n1 or b2.numel() != n2 or w3.numel() != n2:
+        raise ValueError("deepfm_grid_scores: zu / zi must be as wide as a row of w2, b2 and w3 one element per unit of w2")
+    if b3.numel() != 1 or out_w.numel() != 2 or out_b.numel() != 1:
+        raise ValueError("deepfm_grid_scores: b3 and out_b hold one element, out_w two")
+    if users is not None:
+        _i64(users)
+        if users.dim() != 1:
+            raise ValueError("deepfm_grid_scores: users must be 1-D")
+        rows, user0 = users.numel(), 0
+    elif rows is None:
+        rows = nu - user0
+    if out is None:
+        out = torch.empty((rows, ni), dtype=torch.float32, device=zu.device)
+    out = _mat(out, "out")
+    if out.shape != (rows, ni):
+        raise ValueError(f"deepfm_grid_scores: out must be ({rows}, {ni})")
+    # algorithmic: every table row of the call read once (the user tiles re-read item rows from cache), the scores
+    # written; per pair the 256 -> 128 layer, the relu'd sum of the rows, the w3 dot and the FM dot
+    rc = _timed("deepfm_grid_scores",
+                lambda: (4 * ((rows + ni) * (n1 + dim + 1) + rows * ni) + (8 * rows if users is not None else 0),
+                         rows * ni * (2 * n1 * n2 + n1 + 2 * n2 + 2 * dim)),
+                _lib.load().ctr_deepfm_grid_scores, zu.data_ptr(), zi.data_ptr(), su.data_ptr(), si.data_ptr(),
+                a.data_ptr(), b.data_ptr(), nu, ni, dim, n1, n2, w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
+                b3.data_ptr(), out_w.data_ptr(), out_b.data_ptr(),
+                _lib.ptr(users) if users is not None and rows else None, user0, rows,
+                _lib.ptr(out) if out.numel() else None, _ld(out) if rows else ni, int(row_blocks), _lib.stream_ptr())
+    _lib.check(rc, "ctr_deepfm_grid_scores")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # feature interactions
 # ---------------------------------------------------------------------------
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112

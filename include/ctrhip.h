@@ -585,6 +585,34 @@ int ctr_dien_grid_hidden(const float* at, const float* hp, int hp_by_position, i
                          const float* w_hh, const float* b_hh, const int64_t* hist, int64_t rows, int len, float* out,
                          int64_t ldo, int32_t* err_flag, void* stream);
 
+/* DeepFM over the user x item grid (csrc/deepfm_grid.hip): the scores of `rows` users against EVERY item in one launch,
+ * with no feature matrix.  Every column of the (B, 45) feature row belongs to the user or to the item and the first
+ * deep layer has no activation, so the model splits into table rows the caller makes with ctr_embed_fwd and
+ * ctr_linear_fwd:
+ *   h2 = relu(w2 relu(zu[u_r] + zi[i]) + b2)                                     (n1 = 256 -> n2 = 128)
+ *   out[r * ldo + i] = sigmoid(out_w[0] (a[u_r] + b[i] + <su[u_r], si[i]>) + out_w[1] relu(w3 . h2 + b3[0]) + out_b[0])
+ *   u_r = users[r] (users set: any order, repeats allowed) or user0 + r (users NULL; user0 + rows <= num_users)
+ * zu (num_users, n1) / zi (num_items, n1): the deep layers in front of w2 applied to a side's columns of the embedding
+ * row (the biases on the item side); su (num_users, embed) / si (num_items, embed): the sums of a side's field vectors;
+ * a / b: the side's first-order, wide and 0.5 (|sum|^2 - sum |f|^2) terms.  All dense row-major; w2 is (n2, n1) with
+ * contiguous rows, w3 has n2 elements.
+ * Admitted: n1 == 256, n2 == 128, embed a multiple of 16 in 16 .. 128, num_users, num_items < 2^31; anything else is
+ * CTR_ELIMIT.  A null pointer, a negative count, ldo < num_items, row_blocks < 0 or a row range outside the user table
+ * is CTR_EINVAL; zu / zi / su / si / w2 not 16-byte aligned is CTR_EALIGN -- all before anything is enqueued.
+ * rows == 0 or num_items == 0 enqueues nothing and returns CTR_OK.  Columns past num_items of a row of out are not
+ * touched.  A workgroup takes CTR_DEEPFM_GRID_ITEM_TILE items and walks user tiles of CTR_DEEPFM_GRID_USER_TILE rows;
+ * row_blocks > 0 is the number of workgroups that share an item tile's user tiles, 0 leaves it to the launch (a small
+ * multiple of the CU count in all).  The caller validates `users`: an id outside [0, num_users) is clamped into the
+ * table, not reported.  No atomics; a pair's score is a function of its user's rows, its item's rows and the weights
+ * alone, bitwise, whatever the rows, their order, the items' positions or row_blocks. */
+#define CTR_DEEPFM_GRID_ITEM_TILE 128
+#define CTR_DEEPFM_GRID_USER_TILE 16
+int ctr_deepfm_grid_scores(const float* zu, const float* zi, const float* su, const float* si, const float* a,
+                           const float* b, int64_t num_users, int64_t num_items, int embed, int n1, int n2,
+                           const float* w2, const float* b2, const float* w3, const float* b3, const float* out_w,
+                           const float* out_b, const int64_t* users /*nullable*/, int64_t user0, int64_t rows,
+                           float* out, int64_t ldo, int row_blocks, void* stream);
+
 /* gy: gradient of the LAST layer's output; gx (nullable): gradient of x.  workspace is
  * required: (number of workgroups <= 256) * sum_i (n_i*k_i + n_i) floats. */
 int ctr_mlp_bwd(const float* x, int64_t ldx, int64_t m, const ctr_mlp_layer_t* layers, int nlayers,
