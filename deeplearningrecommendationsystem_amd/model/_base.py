@@ -10,6 +10,7 @@ from torch import nn
 
 from .. import _lib, ops, sparse, topn
 from ..ops import Layer
+from ._grid import UserGridScorer
 
 
 class CtrModule(nn.Module):
@@ -99,10 +100,6 @@ class CtrModule(nn.Module):
     def zero_grad(self, set_to_none: bool = True):
         super().zero_grad(set_to_none)
         sparse.discard(self.parameters())
-
-
-def topk_rows(scores: torch.Tensor, k: int) -> np.ndarray:
-    return ops.topk_rows(scores, k).cpu().numpy()
 
 
 def _flatten(p):
@@ -245,7 +242,7 @@ class FeatureModel(CtrModule):
 FORWARD_GRID_PAIRS = 1 << 18     # pairs per forward call of the "forward" path: 47 MB of features
 
 
-class CatalogueScorer:
+class CatalogueScorer(UserGridScorer):
     """Scores of users against EVERY item for a model fed by the (B, 45) feature matrix.  The model does not own the
     side features, so the scorer holds the model and the assembler; it keeps no copy of a weight: every call reads
     the model's parameters as they are then, so a scorer is never stale after an optimizer step.
@@ -256,7 +253,7 @@ class CatalogueScorer:
     path = "forward"
 
     def __init__(self, model: FeatureModel, assembler):
-        self.num_users, self.num_items = model._table_sizes()
+        super().__init__(*model._table_sizes(), assembler.user_features.device)
         users, items = tuple(assembler.user_features.shape), tuple(assembler.item_features.shape)
         if len(users) != 2 or len(items) != 2 or 2 + users[1] + items[1] != 45:
             raise ValueError(f"the assembler's features are {users} and {items}: expected (U, 24) and (I, 19)")
@@ -266,66 +263,13 @@ class CatalogueScorer:
         self.model, self.assembler = model, assembler
 
     def _device(self):
-        return self.assembler.user_features.device
+        return self.device
 
     def _scores(self, users, start, stop, shared=None) -> torch.Tensor:
-        """(rows, num_items) float32, fresh: the rows of ``users`` (validated 1-D int64 device tensor) or of the users
-        [start, stop).  ``shared``: what ``_shared()`` returned for this public call."""
-        dev = self._device()
         rows = users.numel() if users is not None else stop - start
-        out = torch.empty((rows, self.num_items), dtype=torch.float32, device=dev)
+        out = torch.empty((rows, self.num_items), dtype=torch.float32, device=self.device)
         topn.forward_grid(out, FORWARD_GRID_PAIRS, lambda r, i: self.model.forward(
             self.assembler.feature(users[r] if users is not None else r + start, i)))
-        return out
-
-    def _shared(self):
-        """what the chunks of one public call share (nothing on the forward path)"""
-        return None
-
-    @torch.no_grad()
-    def score_rows(self, start: int, stop: int) -> torch.Tensor:
-        """(stop - start, num_items) float32 device tensor, fresh and row-major: the probabilities of users
-        [start, stop) against every item.  Not chunked: the caller chose the rows."""
-        start, stop = int(start), int(stop)
-        if not 0 <= start <= stop <= self.num_users:
-            raise IndexError(f"users [{start}, {stop}) are outside [0, {self.num_users})")
-        return self._scores(None, start, stop, self._shared())
-
-    __call__ = score_rows       # the ``scores(start, stop)`` callable ``ranking_metrics`` takes
-
-    @torch.no_grad()
-    def score_grid(self, users=None) -> torch.Tensor:
-        """(len(users), num_items) float32 probabilities for any 1-D list of user ids (repeats and any order allowed;
-        an id outside the table raises IndexError); ``None``: every user.  Not chunked: the caller chose the rows."""
-        if users is None:
-            return self._scores(None, 0, self.num_users, self._shared())
-        return self._scores(topn.users_tensor(users, self.num_users, self._device()), 0, None, self._shared())
-
-    @torch.no_grad()
-    def recommend(self, users=None, n: int = 20, exclude=None) -> torch.Tensor:
-        """(len(users), n) int64: the items with the highest probability, best first, ties by ascending item id.
-        ``exclude``: an ``ObservedPairs`` whose pairs are left out (``ops.rank_mask``), or None; rows with fewer than
-        ``n`` items left end in -1.  Users are scored in chunks, so the workspace stays bounded."""
-        if n < 1:
-            raise ValueError("n must be at least 1")
-        if exclude is not None and (exclude.num_users, exclude.num_items) != (self.num_users, self.num_items):
-            raise ValueError(f"exclude was built for {exclude.num_users} x {exclude.num_items}, the model is "
-                             f"{self.num_users} x {self.num_items}")
-        dev = self._device()
-        u = topn.users_tensor(users, self.num_users, dev)
-        shared = self._shared()
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def chunk_scores(s, e):
-            scores = self._scores(u[s:e], 0, None, shared)
-            if exclude is None:
-                return scores, None
-            off, ids = topn.excluded_rows(exclude, u[s:e])
-            ops.rank_mask(scores, off, ids, err)
-            return scores, self.num_items - off.diff()
-        out = topn.top_n(u.numel(), self.num_items, n, chunk_scores, dev)
-        if exclude is not None and int(err.item()):
-            raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
         return out
 
 

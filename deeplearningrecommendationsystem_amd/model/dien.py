@@ -7,9 +7,10 @@ import torch
 import torch.nn as nn
 from torch.nn.init import xavier_normal_
 
-from .. import ops, topn
-from ..ops import ACT_NONE, ACT_SIGMOID, Layer
+from .. import ops
+from ..ops import ACT_NONE, ACT_SIGMOID
 from ._base import Params
+from ._grid import HistoryGridScorer
 from .din import SequenceModel, folded_attention, mlp_layers, unfold_attention_grad
 
 # the GRU kernels form the input projection themselves (ctr_gru_fused_fwd / _bwd); CTR_DIEN_FUSED_GRU=0 keeps the
@@ -127,72 +128,21 @@ def grid_path(embed_size, attention_dims=ops.DIEN_GRID_ATTENTION) -> str:
     return "grid" if ops.dien_grid_supported(embed_size, attention_dims) else "forward"
 
 
-# pairs per chunk of the grid walk (at least one history row): beyond the scores a chunk holds the fc operand and the
-# activations ``mlp_fwd`` keeps, 4 * (2E + 128 + 64) B = 896 B a pair at E = 16 -- 112 MiB
-_PAIR_CHUNK = 1 << 17
+class _HistoryScorer(HistoryGridScorer):
+    """DIEN on the history x item grid: the history part HP is the table under the stacked weight ``wh`` =
+    [Wa + Wb ; W_ih] (attention and the GRU's input projection in one product), the kernel runs attention and GRU"""
 
+    def _grid_path(self, embed_size, attention_dims):
+        return grid_path(embed_size, attention_dims)
 
-class _HistoryScorer:
-    """score history rows against every item of one DIEN: what does not depend on the rows -- the item part AT of the
-    split first attention layer, the stacked weight [Wa + Wb ; W_ih] of the history part, and its product HP with the
-    table where the table is the smaller row set -- is made once, here, and not once per chunk"""
+    def _operands(self, p, w1):
+        dim, n1 = self.table.shape[1], w1.shape[0]
+        self.wh = torch.empty((n1 + 3 * dim, dim), dtype=torch.float32, device=self.table.device)
+        torch.add(w1[:, :dim], w1[:, dim:2 * dim], out=self.wh[:n1])     # Wa + Wb: the history part, over
+        self.wh[n1:] = p.w_ih.detach()                                   # W_ih: the GRU's input projection
+        self.b_ih, self.w_hh, self.b_hh = p.b_ih.detach(), p.w_hh.detach().contiguous(), p.b_hh.detach()
+        return self.wh, torch.sub(w1[:, 2 * dim:], w1[:, dim:2 * dim])   # Wc - Wb: the item part
 
-    def __init__(self, model: DIEN):
-        self.model = model
-        p = model._params()
-        self.table = p.table.detach()
-        model._need_device(self.table)
-        dim, dev = self.table.shape[1], self.table.device
-        self.flag = model._err_flag(dev)
-        self.fc = [Layer(layer.weight.detach(), layer.bias.detach(), layer.act) for layer in p.fc]
-        self.path = grid_path(dim, [tuple(layer.weight.shape) for layer in p.att])
-        self.hp_table = None
-        if self.path == "grid":
-            att1, att2, att3 = p.att
-            w1 = att1.weight.detach()
-            n1 = w1.shape[0]
-            self.wh = torch.empty((n1 + 3 * dim, dim), dtype=torch.float32, device=dev)
-            torch.add(w1[:, :dim], w1[:, dim:2 * dim], out=self.wh[:n1])     # Wa + Wb: the history part, over
-            self.wh[n1:] = p.w_ih.detach()                                   # W_ih: the GRU's input projection
-            wt = torch.sub(w1[:, 2 * dim:], w1[:, dim:2 * dim])              # Wc - Wb: the item part
-            self.at = ops.linear_fwd(self.table, wt, att1.bias.detach())
-            self.w2, self.b2 = att2.weight.detach().contiguous(), att2.bias.detach()
-            self.w3 = att3.weight.detach().reshape(-1)
-            self.b_ih, self.w_hh, self.b_hh = p.b_ih.detach(), p.w_hh.detach().contiguous(), p.b_hh.detach()
-
-    def _hp(self, hist, positions):
-        """(HP, by position?) for the rows ``hist`` of a call over ``positions`` history positions: the projected table
-        where it has no more rows than that (made once), else the projection of the gathered history rows"""
-        num_items, dim = self.table.shape
-        if self.hp_table is None and num_items <= positions:
-            self.hp_table = ops.linear_fwd(self.table, self.wh, None)
-        if self.hp_table is not None:
-            return self.hp_table, False
-        hrows = torch.empty((hist.numel(), dim), dtype=torch.float32, device=hist.device)
-        ops.din_concat_fwd(self.table, hist, torch.zeros(hist.shape[0], dtype=torch.int64, device=hist.device), hrows,
-                           None, self.flag, h_only=True)
-        return ops.linear_fwd(hrows, self.wh, None), True
-
-    def __call__(self, hist) -> torch.Tensor:
-        """(R, num_items) float32, fresh: the rows of ``hist`` (validated (R, L) int64 device tensor)"""
-        hist = hist.contiguous()
-        rows = hist.shape[0]
-        num_items, dim = self.table.shape
-        dev = self.table.device
-        out = torch.empty((rows, num_items), dtype=torch.float32, device=dev)
-        if rows == 0:
-            return out
-        if self.path == "grid":
-            per = max(1, _PAIR_CHUNK // num_items)
-            for s in range(0, rows, per):
-                part = hist[s:s + per]
-                fcin = torch.empty((part.shape[0] * num_items, 2 * dim), dtype=torch.float32, device=dev)
-                fcin.view(part.shape[0], num_items, 2 * dim)[:, :, dim:] = self.table
-                hp, by_position = self._hp(part, hist.numel())
-                ops.dien_grid_hidden(self.at, hp, self.w2, self.b2, self.w3, self.b_ih, self.w_hh, self.b_hh, part,
-                                     out=fcin[:, :dim], hp_by_position=by_position, err_flag=self.flag)
-                # the stage a fused kernel would take over: the fc stack on the (pairs, 2E) operand
-                ops.mlp_fwd(fcin, self.fc, last_out=out[s:s + per].view(-1, 1))
-            return out
-        topn.forward_grid(out, _PAIR_CHUNK, lambda r, i: self.model.forward(hist[r], i))
-        return out
+    def _fill(self, hist, hp, by_position, out):
+        ops.dien_grid_hidden(self.at, hp, self.w2, self.b2, self.w3, self.b_ih, self.w_hh, self.b_hh, hist, out=out,
+                             hp_by_position=by_position, err_flag=self.flag)

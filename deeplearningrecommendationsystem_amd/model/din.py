@@ -8,10 +8,11 @@ import torch
 import torch.nn as nn
 from torch.nn.init import xavier_normal_
 
-from .. import ops, topn
+from .. import ops
 from .._lib import FIELD_ID_I64
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
 from ._base import CtrModule, Params
+from ._grid import HistoryGridScorer, rank_rows
 
 # the history gradient of the E-wide attention leaves the first layer's dX GEMM as atomics on the table gradient
 # (ctr_linear_dx_scatter); CTR_DIN_FUSED_SCATTER=0 keeps the two-pass form (dX to memory, seq_scatter) for A/B
@@ -128,14 +129,14 @@ class SequenceModel(CtrModule):
         return self._params().table
 
     def _grid_scorer(self):
-        """the model's ``_HistoryScorer``: rows of histories (R, L) -> fresh (R, num_items) scores"""
+        """the model's ``HistoryGridScorer``: rows of histories (R, L) -> fresh (R, num_items) scores"""
         raise NotImplementedError
 
     @torch.no_grad()
     def score_histories(self, hist: torch.Tensor) -> torch.Tensor:
         """(R, num_items) float32 device tensor, fresh and row-major: the probability of every item after each of the
         R history rows of ``hist`` (R, L) int64.  The whole matrix is returned -- the caller chose the rows -- while
-        the workspace beyond it is bounded: the rows are walked ``_PAIR_CHUNK`` pairs at a time.  An id outside the
+        the workspace beyond it is bounded: the rows are walked ``_grid.PAIR_CHUNK`` pairs at a time.  An id outside the
         table raises IndexError."""
         self._grid_table()
         _check_hist(hist)
@@ -185,20 +186,7 @@ class SequenceModel(CtrModule):
             elif rows and bool(((users < 0) | (users >= exclude.num_users)).any()):
                 raise ValueError(f"users outside the {exclude.num_users} users exclude was built for")
         scorer = self._grid_scorer()
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def chunk_scores(s, e):
-            scores = scorer(hist[s:e])
-            if exclude is None:
-                return scores, None
-            off, ids = topn.excluded_rows(exclude, users[s:e])
-            ops.rank_mask(scores, off, ids, err)
-            return scores, num_items - off.diff()
-        out = topn.top_n(rows, num_items, n, chunk_scores, dev)
-        self.check_bad_index()
-        if exclude is not None and int(err.item()):
-            raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
-        return out
+        return rank_rows(lambda s, e: scorer(hist[s:e]), rows, num_items, n, exclude, users, dev, self.check_bad_index)
 
 
 class DIN(SequenceModel):
@@ -362,11 +350,6 @@ def grid_path(embed_size, attention_dims=ops.DIN_GRID_ATTENTION) -> str:
     return "grid" if ops.din_grid_supported(embed_size, attention_dims) else "forward"
 
 
-# pairs per chunk of the grid walk (at least one history row): beyond the scores a chunk holds the fc operand and the
-# activations ``mlp_fwd`` keeps, 4 * (2E + 256 + 128) B = 2 KiB a pair at E = 64 -- 256 MiB
-_PAIR_CHUNK = 1 << 17
-
-
 def _check_hist(hist):
     if not isinstance(hist, torch.Tensor) or hist.dim() != 2 or hist.dtype != torch.int64 or not hist.is_cuda:
         raise ValueError("expected hist (R, L) as an int64 tensor on the device, got "
@@ -376,64 +359,20 @@ def _check_hist(hist):
         raise ValueError("expected hist (R, L) with L >= 1: an empty history has no attention")
 
 
-class _HistoryScorer:
-    """score history rows against every item of one DIN: what does not depend on the rows -- the two halves of the
-    split first attention layer and the item part AT, and the history part AH where the table is the smaller row set
-    -- is made once, here, and not once per chunk"""
+class _HistoryScorer(HistoryGridScorer):
+    """DIN on the history x item grid: the two halves ``wf`` of the split first attention layer are made once; the
+    history part is AH, the kernel pools the attention"""
 
-    def __init__(self, model: DIN):
-        self.model = model
-        p = model._params()
-        self.table = p.table.detach()
-        model._need_device(self.table)
-        num_items, dim = self.table.shape
-        self.flag = model._err_flag(self.table.device)
-        self.fc = [Layer(layer.weight.detach(), layer.bias.detach(), layer.act) for layer in p.fc]
-        self.path = grid_path(dim, [tuple(layer.weight.shape) for layer in p.att])
-        self.ah_table = None
-        if self.path == "grid":
-            att1, att2, att3 = p.att
-            w1 = att1.weight.detach()
-            self.wf = torch.empty((2, w1.shape[0], dim), dtype=torch.float32, device=self.table.device)
-            torch.add(w1[:, :dim], w1[:, dim:2 * dim], out=self.wf[0])        # Wa + Wb: the history part
-            torch.sub(w1[:, 2 * dim:], w1[:, dim:2 * dim], out=self.wf[1])    # Wc - Wb: the item part
-            self.at = ops.linear_fwd(self.table, self.wf[1], att1.bias.detach())
-            self.w2, self.b2 = att2.weight.detach().contiguous(), att2.bias.detach()
-            self.w3 = att3.weight.detach().reshape(-1)
+    def _grid_path(self, embed_size, attention_dims):
+        return grid_path(embed_size, attention_dims)
 
-    def _ah(self, hist, positions):
-        """(AH, by position?) for the rows ``hist`` of a call over ``positions`` history positions: the projected table
-        where it has no more rows than that (made once), else the projection of the gathered history rows"""
-        num_items, dim = self.table.shape
-        if self.ah_table is None and num_items <= positions:
-            self.ah_table = ops.linear_fwd(self.table, self.wf[0], None)
-        if self.ah_table is not None:
-            return self.ah_table, False
-        hrows = torch.empty((hist.numel(), dim), dtype=torch.float32, device=hist.device)
-        ops.din_concat_fwd(self.table, hist, torch.zeros(hist.shape[0], dtype=torch.int64, device=hist.device), hrows,
-                           None, self.flag, h_only=True)
-        return ops.linear_fwd(hrows, self.wf[0], None), True
+    def _operands(self, p, w1):
+        dim = self.table.shape[1]
+        self.wf = torch.empty((2, w1.shape[0], dim), dtype=torch.float32, device=self.table.device)
+        torch.add(w1[:, :dim], w1[:, dim:2 * dim], out=self.wf[0])        # Wa + Wb: the history part
+        torch.sub(w1[:, 2 * dim:], w1[:, dim:2 * dim], out=self.wf[1])    # Wc - Wb: the item part
+        return self.wf[0], self.wf[1]
 
-    def __call__(self, hist) -> torch.Tensor:
-        """(R, num_items) float32, fresh: the rows of ``hist`` (validated (R, L) int64 device tensor)"""
-        hist = hist.contiguous()
-        rows, length = hist.shape
-        num_items, dim = self.table.shape
-        dev = self.table.device
-        out = torch.empty((rows, num_items), dtype=torch.float32, device=dev)
-        if rows == 0:
-            return out
-        if self.path == "grid":
-            per = max(1, _PAIR_CHUNK // num_items)
-            for s in range(0, rows, per):
-                part = hist[s:s + per]
-                fcin = torch.empty((part.shape[0] * num_items, 2 * dim), dtype=torch.float32, device=dev)
-                fcin.view(part.shape[0], num_items, 2 * dim)[:, :, dim:] = self.table
-                ah, by_position = self._ah(part, hist.numel())
-                ops.din_grid_pool(self.table, self.at, ah, self.w2, self.b2, self.w3, part, out=fcin[:, :dim],
-                                  ah_by_position=by_position, err_flag=self.flag)
-                # the stage a fused kernel would take over: the fc stack on the (pairs, 2E) operand
-                ops.mlp_fwd(fcin, self.fc, last_out=out[s:s + per].view(-1, 1))
-            return out
-        topn.forward_grid(out, _PAIR_CHUNK, lambda r, i: self.model.forward(hist[r], i))
-        return out
+    def _fill(self, hist, ah, by_position, out):
+        ops.din_grid_pool(self.table, self.at, ah, self.w2, self.b2, self.w3, hist, out=out,
+                          ah_by_position=by_position, err_flag=self.flag)

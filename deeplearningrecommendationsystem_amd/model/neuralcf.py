@@ -12,7 +12,8 @@ from .. import loss as _loss
 from .. import ops, topn
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
 from .._lib import FIELD_ID_I64, FIELD_PROD_I64, CtrHipError
-from ._base import CtrModule
+from ._base import CtrModule, Params
+from ._grid import UserGridScorer
 
 # Vocabularies much smaller than the batch (BASELINE configs[1]: 943 + 1682 rows, batch 65536): the first tower layer
 # and its backward on the TABLE ROWS instead of the samples (csrc/ncf_proj.hip, ops.NcfProj).  CTR_NCF_PROJ=0 keeps the
@@ -356,53 +357,22 @@ class NeuralCF(CtrModule):
     def _table_sizes(self):
         return self.GMF_Embedding_User.weight.shape[0], self.GMF_Embedding_Item.weight.shape[0]
 
-    @torch.no_grad()
     def score_rows(self, start: int, stop: int) -> torch.Tensor:
         """(stop - start, num_items) float32 device tensor, fresh and row-major: the probabilities of users
         [start, stop) against every item -- the ``scores(start, stop)`` callable ``ranking_metrics`` takes.  Not
         chunked: the caller chose the rows."""
-        num_users, _ = self._table_sizes()
-        start, stop = int(start), int(stop)
-        if not 0 <= start <= stop <= num_users:
-            raise IndexError(f"users [{start}, {stop}) are outside [0, {num_users})")
-        return _GridScorer(self)(start=start, stop=stop)
+        return _GridScorer(self).score_rows(start, stop)
 
-    @torch.no_grad()
     def score_grid(self, users=None) -> torch.Tensor:
         """(len(users), num_items) float32 probabilities for any 1-D list of user ids (repeats and any order allowed;
         an id outside the table raises IndexError); ``None``: every user.  Not chunked: the caller chose the rows."""
-        num_users, _ = self._table_sizes()
-        if users is None:
-            return _GridScorer(self)(start=0, stop=num_users)
-        return _GridScorer(self)(users=topn.users_tensor(users, num_users, self.GMF_Embedding_User.weight.device))
+        return _GridScorer(self).score_grid(users)
 
-    @torch.no_grad()
     def recommend(self, users=None, n: int = 20, exclude=None) -> torch.Tensor:
         """(len(users), n) int64: the items with the highest probability, best first, ties by ascending item id.
         ``exclude``: an ``ObservedPairs`` whose pairs are left out (``ops.rank_mask``), or None; rows with fewer than
         ``n`` items left end in -1.  Users are scored in chunks, so the workspace stays bounded."""
-        if n < 1:
-            raise ValueError("n must be at least 1")
-        num_users, num_items = self._table_sizes()
-        if exclude is not None and (exclude.num_users, exclude.num_items) != (num_users, num_items):
-            raise ValueError(f"exclude was built for {exclude.num_users} x {exclude.num_items}, the model is "
-                             f"{num_users} x {num_items}")
-        dev = self.GMF_Embedding_User.weight.device
-        u = topn.users_tensor(users, num_users, dev)
-        scorer = _GridScorer(self)
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def chunk_scores(s, e):
-            scores = scorer(users=u[s:e])
-            if exclude is None:
-                return scores, None
-            off, ids = topn.excluded_rows(exclude, u[s:e])
-            ops.rank_mask(scores, off, ids, err)
-            return scores, num_items - off.diff()
-        out = topn.top_n(u.numel(), num_items, n, chunk_scores, dev)
-        if exclude is not None and int(err.item()):
-            raise ValueError(f"exclude: inconsistent id rows (error bits {int(err.item()):#x})")
-        return out
+        return _GridScorer(self).recommend(users, n, exclude)
 
 
 def grid_path(tables, hidden, proj) -> str:
@@ -415,35 +385,39 @@ def grid_path(tables, hidden, proj) -> str:
 _FORWARD_CHUNK = 1 << 20     # pairs per forward call of the "forward" path
 
 
-class _GridScorer:
+class _GridScorer(UserGridScorer):
     """score rows of the user x item grid of one model: what does not depend on the rows -- the projected tables and the
-    folded head of the "grid" path -- is made once, here, and not once per chunk"""
+    folded head of the "grid" path -- is made once per public call (``_shared``), and not once per chunk"""
 
     def __init__(self, model: NeuralCF):
-        self.model = model
         p = model._params()
-        self.tables = tuple(t.detach() for t in p.tables)
-        model._need_device(self.tables[0])
+        super().__init__(*model._table_sizes(), p.tables[0].device)
+        self.model = model
         self.path = grid_path(p.tables, p.hidden, p.proj)
+
+    def _shared(self):
+        """the operands of ``ops.ncf_grid_scores`` by name (the tables alone on the "forward" path)"""
+        p = self.model._params()
+        sh = Params(tables=tuple(t.detach() for t in p.tables))
+        self.model._need_device(sh.tables[0])
         if self.path == "grid":
-            gmf_u, gmf_i, mlp_u, mlp_i = self.tables
+            gmf_u, gmf_i, mlp_u, mlp_i = sh.tables
             half = mlp_u.shape[1]
             w0, b0 = p.hidden[0].weight.detach(), p.hidden[0].bias.detach()
-            self.p_u = ops.linear_fwd(mlp_u, w0[:, :half], None)
-            self.p_i = ops.linear_fwd(mlp_i, w0[:, half:], b0)
-            self.layers = [Layer(layer.weight.detach(), layer.bias.detach(), layer.act) for layer in p.hidden[1:]]
-            self.wfold, self.cfold = ops.fold_head_fwd(p.head[0].detach(), gmf_u.shape[1], p.proj[0].detach(),
-                                                       p.proj[1].detach(), p.head[1].detach())
+            sh.p_u = ops.linear_fwd(mlp_u, w0[:, :half], None)
+            sh.p_i = ops.linear_fwd(mlp_i, w0[:, half:], b0)
+            sh.layers = [Layer(layer.weight.detach(), layer.bias.detach(), layer.act) for layer in p.hidden[1:]]
+            sh.wfold, sh.cfold = ops.fold_head_fwd(p.head[0].detach(), gmf_u.shape[1], p.proj[0].detach(),
+                                                   p.proj[1].detach(), p.head[1].detach())
+        return sh
 
-    def __call__(self, users=None, start=0, stop=None) -> torch.Tensor:
-        """(rows, num_items) float32, fresh: the rows of ``users`` (validated 1-D int64 device tensor) or of the users
-        [start, stop)"""
-        gmf_u, gmf_i = self.tables[:2]
-        rows, ni = (users.numel() if users is not None else stop - start), gmf_i.shape[0]
+    def _scores(self, users, start, stop, sh) -> torch.Tensor:
+        gmf_u, gmf_i = sh.tables[:2]
+        rows = users.numel() if users is not None else stop - start
         if self.path == "grid":
-            return ops.ncf_grid_scores(self.p_u, self.p_i, gmf_u, gmf_i, self.layers, self.wfold, self.cfold,
+            return ops.ncf_grid_scores(sh.p_u, sh.p_i, gmf_u, gmf_i, sh.layers, sh.wfold, sh.cfold,
                                        users=users, user0=start, rows=rows, act=ACT_SIGMOID)
-        out = torch.empty((rows, ni), dtype=torch.float32, device=gmf_u.device)
+        out = torch.empty((rows, self.num_items), dtype=torch.float32, device=self.device)
         topn.forward_grid(out, _FORWARD_CHUNK,
                           lambda r, i: self.model.forward(users[r] if users is not None else r + start, i))
         return out

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""What every grid scorer launches and returns, as a listing two trees can be compared by: run from the root of the tree
+to be measured (a parent checkout beside the change, both loading one library through ``CTRHIP_LIB``), then ``diff``
+the two outputs (``profiles/grid_scorer_refactor.txt``).
+
+At the shapes of tests/test_gpu_ncf_grid.py, test_gpu_din_grid.py, test_gpu_dien_grid.py and test_gpu_deepfm_grid.py,
+with ``topn.SCORE_CHUNK_FLOATS`` lowered to five rows a chunk and an ``ops.KernelProfiler`` installed, public names only:
+
+  NeuralCF  33 x 130 at 64 / [128, 64, 32, 16, 8] ("grid") and 50 x 60 at 12 / [24, 12, 6] ("forward"):
+            ``score_rows``, ``score_grid`` with a repeated list, ``recommend``
+  DIN       33 rows x 130 items, L = 33 at E = 64 ("grid") and 9 x 60, L = 5 at E = 8 ("forward"); DIEN the same at
+            E = 16 and E = 8: ``score_histories``, ``history_scorer``, ``recommend`` with ``users=``
+  DeepFM    33 x 258 at E = 16 / [512, 256, 128, 1] ("grid") and 21 x 30 at E = 8 / [32, 16, 1] ("forward"):
+            the three ``catalogue_scorer`` calls
+
+``recommend`` runs with n = 6 and with n = num_items + 3 plus ``exclude``.  Every entry prints the shape and the first 16
+hex digits of the SHA-256 of the result, then the recorded (label, bytes, flops) in call order."""
+import hashlib
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.getcwd())
+from deeplearningrecommendationsystem_amd import model as zoo  # noqa: E402
+from deeplearningrecommendationsystem_amd import ops, topn  # noqa: E402
+from deeplearningrecommendationsystem_amd.data import FeatureAssembler, ObservedPairs  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def observed(nu, ni, seed=3):
+    """user 0 has seen everything, user 1 all but two items, the others a random third"""
+    seen = torch.rand((nu, ni), generator=torch.Generator().manual_seed(seed)) < 0.33
+    seen[0] = True
+    seen[1] = True
+    seen[1, [2, ni - 1]] = False
+    u, i = seen.nonzero(as_tuple=True)
+    return ObservedPairs(u.to(DEV), i.to(DEV), nu, ni)
+
+
+def entry(what, call):
+    profiler = ops.KernelProfiler()
+    ops.set_profiler(profiler)
+    try:
+        out = call()
+        torch.cuda.synchronize()
+    finally:
+        ops.set_profiler(None)
+    digest = hashlib.sha256(out.cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
+    print(f"== {what}: result {tuple(out.shape)} {str(out.dtype).replace('torch.', '')} sha256 {digest}")
+    for label, nbytes, flops, _, _ in profiler.records:
+        print(f"   {label} {nbytes} {flops}")
+
+
+def user_grid(name, scorer, nu, ni):
+    topn.SCORE_CHUNK_FLOATS = 5 * ni
+    seen = observed(nu, ni)
+    entry(f"{name} score_rows(5, 20)", lambda: scorer.score_rows(5, 20))
+    entry(f"{name} score_grid([3, 1, 3, 0])", lambda: scorer.score_grid([3, 1, 3, 0]))
+    entry(f"{name} recommend(n=6)", lambda: scorer.recommend(n=6))
+    entry(f"{name} recommend(n=ni+3, exclude)", lambda: scorer.recommend(n=ni + 3, exclude=seen))
+
+
+def history_grid(name, model, rows, ni, length):
+    topn.SCORE_CHUNK_FLOATS = 5 * ni
+    hist = torch.randint(0, ni, (rows, length), generator=torch.Generator().manual_seed(rows + length)).to(DEV)
+    seen = observed(rows, ni)
+    users = torch.tensor([rows - 1, 0, 7, 7, 1, 4] + list(range(2, rows)), device=DEV)
+    entry(f"{name} score_histories", lambda: model.score_histories(hist))
+    entry(f"{name} history_scorer(2, {rows - 1})", lambda: model.history_scorer(hist)(2, rows - 1))
+    entry(f"{name} recommend(n=6, users=)", lambda: model.recommend(hist[users], n=6, users=users))
+    entry(f"{name} recommend(n=ni+3, exclude, users=)",
+          lambda: model.recommend(hist[users], n=ni + 3, exclude=seen, users=users))
+
+
+def spread(model, seed):
+    """tables and biases drawn wide, so that scores differ in more than their last bits"""
+    gen = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if "mbed" in name or name.endswith("bias"):
+                p.copy_(torch.randn(p.shape, generator=gen))
+    return model.to(DEV).eval()
+
+
+def main():
+    for nu, ni, args in ((33, 130, (64, [128, 64, 32, 16, 8])), (50, 60, (12, [24, 12, 6]))):
+        torch.manual_seed(nu)
+        model = spread(zoo.NeuralCF(nu, ni, *args), ni)
+        user_grid(f"NeuralCF {nu} x {ni} mf {args[0]}", model, nu, ni)
+    for cls in (zoo.DIN, zoo.DIEN):
+        for rows, ni, length, embed in ((33, 130, 33, 64 if cls is zoo.DIN else 16), (9, 60, 5, 8)):
+            torch.manual_seed(rows)
+            model = spread(cls(ni, embed), ni)
+            history_grid(f"{cls.__name__} {rows} x {ni} L {length} E {embed}", model, rows, ni, length)
+    for nu, ni, embed, hidden in ((33, 258, 16, [512, 256, 128, 1]), (21, 30, 8, [32, 16, 1])):
+        torch.manual_seed(nu)
+        model = spread(zoo.DeepFM(nu, ni, hidden, embed), ni)
+        gen = torch.Generator().manual_seed(nu + ni)
+        uf = torch.zeros((nu, 24))                           # age, gender and occupation one-hot; genres Bernoulli
+        uf[:, 0] = torch.rand(nu, generator=gen)
+        uf[torch.arange(nu), 1 + torch.randint(0, 2, (nu,), generator=gen)] = 1.0
+        uf[torch.arange(nu), 3 + torch.randint(0, 21, (nu,), generator=gen)] = 1.0
+        itf = (torch.rand((ni, 19), generator=gen) < 0.09).float()
+        scorer = model.catalogue_scorer(FeatureAssembler(uf.to(DEV), itf.to(DEV)))
+        user_grid(f"DeepFM[{scorer.path}] {nu} x {ni} E {embed}", scorer, nu, ni)
+
+
+if __name__ == "__main__":
+    main()

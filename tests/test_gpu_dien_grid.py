@@ -43,6 +43,11 @@ WEIGHT_SCALE = 3.0
 GRU = "interest_evolution."
 
 
+def _grid():
+    from deeplearningrecommendationsystem_amd.model import _grid
+    return _grid
+
+
 def _dien():
     from deeplearningrecommendationsystem_amd.model import dien
     return dien
@@ -230,7 +235,7 @@ def test_score_histories_matches_the_per_sample_forward_in_any_chunking(rows, ni
           f"forward, max |difference| {float((got - want).abs().max()):.3e}")
     torch.testing.assert_close(got, want, rtol=RTOL, atol=ATOL)
     for pairs in (ni, 2 * ni + 1):                 # one row per chunk; two rows: a chunk boundary inside the row list
-        monkeypatch.setattr(_dien(), "_PAIR_CHUNK", pairs)
+        monkeypatch.setattr(_grid(), "PAIR_CHUNK", pairs)
         torch.testing.assert_close(model.score_histories(hist), got, rtol=RTOL, atol=ATOL)
 
 
@@ -316,7 +321,7 @@ def test_other_embed_sizes_take_the_forward_path(monkeypatch):
     print(f"forward path: max error / (atol + rtol |ref|) {_frac(got.cpu(), scores64, ATOL):.3f}")
     torch.testing.assert_close(got.cpu().double(), torch.from_numpy(scores64), rtol=RTOL, atol=ATOL)
     gu.assert_same_ranking(model.recommend(hist, n=20).cpu().numpy(), topk64, scores64, tol=1e-5)
-    monkeypatch.setattr(_dien(), "_PAIR_CHUNK", 100)                         # chunks that end inside a row
+    monkeypatch.setattr(_grid(), "PAIR_CHUNK", 100)                         # chunks that end inside a row
     torch.testing.assert_close(model.score_histories(hist), got, rtol=RTOL, atol=ATOL)
     observed, _ = _observed(rows, ni)
     rec = model.recommend(hist, n=ni + 3, exclude=observed)

@@ -1,0 +1,249 @@
+"""GPU: the frame of ``model/_grid.py`` on stubs, so that it is the frame under test and not a kernel.
+
+``rank_rows`` ranks scores of a fixed generator (one tied pair of items per row) and is compared, exactly, with a plain
+torch reference: left-out items to -inf, stable descending sort, -1 past the survivors.  33 rows x 130 items with the
+chunk lowered to five rows (seven chunks, the last of three rows), and 5 x 17 as one whole chunk.
+
+``HistoryGridScorer`` runs with a stub "kernel" that writes 1000 * (first id of the history row) + item into column 0 of
+the left half of the fc operand, and one fc layer that reads that column and adds 0.5: every score is an integer plus a
+half, exact in float32, so the chunk walk is checked with equality.  The stub's table and weights are small integers, so
+the history part is exact too whatever order the GEMM sums in.
+
+``rank_mask``'s error bits are not provoked here: the CSR ``rank_rows`` hands it comes from ``topn.excluded_rows``,
+which builds consistent offsets out of any ``ObservedPairs``; a tampered ``indptr`` fails in torch's own indexing before
+the kernel runs, and tests/test_gpu_ranking.py shows a safe construction for ``rank_filter`` only."""
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SHAPES = [(33, 130, 5), (5, 17, None)]          # rows, items, rows per chunk (None: the default, one whole chunk)
+
+
+def _grid():
+    from deeplearningrecommendationsystem_amd.model import _grid
+    return _grid
+
+
+# ------------------------------------------------------------------ 1. rank_rows
+def _scores(rows, ni):
+    """(rows, ni) float32 on the CPU, distinct within a row but for one tied pair"""
+    gen = torch.Generator().manual_seed(100 * rows + ni)
+    scores = torch.rand((rows, ni), generator=gen)
+    for r in range(rows):
+        a, b = torch.randperm(ni, generator=gen)[:2].tolist()
+        scores[r, a] = scores[r, b]
+    return scores
+
+
+def _observed(nu, ni, seed=3):
+    """an ObservedPairs with user 0 having seen everything, user 1 all but two items, the others a random third"""
+    from deeplearningrecommendationsystem_amd.data import ObservedPairs
+    seen = torch.rand((nu, ni), generator=torch.Generator().manual_seed(seed)) < 0.33
+    seen[0] = True
+    seen[1] = True
+    seen[1, [2, ni - 1]] = False
+    u, i = seen.nonzero(as_tuple=True)
+    return ObservedPairs(u.to(DEV), i.to(DEV), nu, ni), seen
+
+
+def _reference(scores, n, seen_rows):
+    """plain torch on the CPU: mask to -inf, stable descending sort, -1 past the survivors"""
+    rows, ni = scores.shape
+    masked = scores.clone()
+    left = torch.full((rows,), ni)
+    if seen_rows is not None:
+        masked[seen_rows] = float("-inf")
+        left = ni - seen_rows.sum(1)
+    order = torch.sort(masked, dim=1, descending=True, stable=True).indices
+    want = torch.full((rows, n), -1, dtype=torch.int64)
+    take = min(n, ni)
+    want[:, :take] = order[:, :take]
+    want[torch.arange(n)[None, :] >= left[:, None]] = -1
+    return want
+
+
+@pytest.mark.parametrize("who", ["no-exclude", "own-rows", "permuted-with-repeats"])
+@pytest.mark.parametrize("rows,ni,per", SHAPES)
+def test_rank_rows_is_the_stable_ranking_of_the_masked_scores(rows, ni, per, who, monkeypatch):
+    from deeplearningrecommendationsystem_amd import topn
+    if per is not None:
+        monkeypatch.setattr(topn, "SCORE_CHUNK_FLOATS", per * ni)
+    scores = _scores(rows, ni)
+    on_device = scores.to(DEV)
+    observed, seen = _observed(rows, ni)
+    if who == "no-exclude":
+        observed = users = seen_rows = None
+    else:
+        users = torch.arange(rows)
+        if who == "permuted-with-repeats":
+            users = torch.randperm(rows, generator=torch.Generator().manual_seed(7))
+            users[[2, rows - 1]] = int(users[0])                                # one user three times
+            users[3], users[4] = 0, 1                                        # the full row and the all-but-two row
+        seen_rows = seen[users]
+        users = users.to(DEV)
+    for n in (6, ni + 3):
+        chunks = []
+
+        def score_chunk(s, e):
+            chunks.append((s, e))
+            return on_device[s:e].clone()
+        got = _grid().rank_rows(score_chunk, rows, ni, n, observed, users, DEV)
+        assert got.shape == (rows, n) and got.dtype == torch.int64 and got.device == torch.device(DEV)
+        step = per if per is not None else rows
+        assert chunks == [(s, min(rows, s + step)) for s in range(0, rows, step)]
+        assert torch.equal(got.cpu(), _reference(scores, n, seen_rows)), (who, n)
+    if per is not None:
+        assert len(chunks) == 7 and chunks[-1] == (30, 33)
+
+
+def test_rank_rows_runs_the_hook_between_the_ranking_and_the_error_check():
+    rows, ni = 5, 17
+    on_device = _scores(rows, ni).to(DEV)
+    events = []
+
+    def score_chunk(s, e):
+        events.append("scores")
+        return on_device[s:e].clone()
+    _grid().rank_rows(score_chunk, rows, ni, 3, None, None, DEV, lambda: events.append("hook"))
+    assert events == ["scores", "hook"]
+
+
+# ------------------------------------------------------------------ 2. the history base
+E, N1, N2 = 16, 8, 4
+
+
+class _StubModel:
+    """what ``HistoryGridScorer`` reads of a model: the table, three attention layers, the fc stack; integers"""
+
+    def __init__(self, ni):
+        from deeplearningrecommendationsystem_amd.ops import ACT_NONE, Layer
+        gen = torch.Generator().manual_seed(ni)
+
+        def ints(*shape):
+            return torch.randint(-3, 4, shape, generator=gen).float().to(DEV)
+        pick = torch.zeros((1, 2 * E), device=DEV)
+        pick[0, 0] = 1.0
+        self.p = SimpleNamespace(table=ints(ni, E), att=[Layer(ints(N1, 3 * E), ints(N1), ACT_NONE),
+                                                         Layer(ints(N2, N1), ints(N2), ACT_NONE),
+                                                         Layer(ints(1, N2), ints(1), ACT_NONE)],
+                                 fc=[Layer(pick, torch.full((1,), 0.5, device=DEV), ACT_NONE)])
+        self.flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+
+    def _params(self):
+        return self.p
+
+    def _need_device(self, *tensors):
+        assert all(t.is_cuda for t in tensors)
+
+    def _err_flag(self, device):
+        return self.flag
+
+    def forward(self, hist, items):
+        return (1000 * hist[:, 0] + items).float().view(-1, 1) + 0.5
+
+
+def _stub_scorer(model, path="grid"):
+    class Stub(_grid().HistoryGridScorer):
+        def _grid_path(self, embed_size, attention_dims):
+            assert embed_size == E and attention_dims == [(N1, 3 * E), (N2, N1), (1, N2)]
+            return path
+
+        def _operands(self, p, w1):
+            self.fills = []
+            return w1[:, :E].contiguous(), w1[:, 2 * E:].contiguous()
+
+        def _fill(self, hist, part, by_position, out):
+            self.fills.append((hist.clone(), part, by_position))
+            ni = self.table.shape[0]
+            assert out.shape == (hist.shape[0] * ni, E) and out.stride(0) == 2 * E
+            out.zero_()
+            out[:, 0] = (1000 * hist[:, :1] + torch.arange(ni, device=hist.device)[None, :]).reshape(-1).float()
+
+    return Stub(model)
+
+
+def _hist(rows, ni, length):
+    """(rows, length) ids below ``ni`` whose first column names the row"""
+    hist = torch.randint(0, ni, (rows, length), generator=torch.Generator().manual_seed(rows))
+    hist[:, 0] = torch.arange(rows)
+    return hist.to(DEV)
+
+
+def _want(hist, ni):
+    return (1000 * hist[:, :1] + torch.arange(ni, device=DEV)[None, :]).float() + 0.5
+
+
+def test_the_operands_made_once():
+    ni = 17
+    model = _StubModel(ni)
+    sc = _stub_scorer(model)
+    att1, att2, att3 = model.p.att
+    table = model.p.table.cpu()
+    assert sc.path == "grid" and sc.flag is model.flag and sc.table.data_ptr() == model.p.table.data_ptr()
+    assert torch.equal(sc.at.cpu(), table @ att1.weight[:, 2 * E:].cpu().t() + att1.bias.cpu())
+    assert torch.equal(sc.w2, att2.weight) and torch.equal(sc.b2, att2.bias) and torch.equal(sc.w3, att3.weight[0])
+    assert _stub_scorer(model, "forward").path == "forward"
+
+
+@pytest.mark.parametrize("rows,ni,length", [(33, 130, 4), (5, 17, 4)])
+def test_the_chunk_walk_covers_every_row_once(rows, ni, length, monkeypatch):
+    """``PAIR_CHUNK`` below one row, ending inside a row, on a row boundary and past the grid; rows * length >= ni, so
+    the history part is the projected table, made once per scorer"""
+    model = _StubModel(ni)
+    hist = _hist(rows, ni, length)
+    part_want = model.p.table.cpu() @ model.p.att[0].weight[:, :E].cpu().t()
+    for pairs, per in ((ni - 1, 1), (2 * ni + ni // 2, 2), (3 * ni, 3), (rows * ni + 7, rows)):
+        monkeypatch.setattr(_grid(), "PAIR_CHUNK", pairs)
+        sc = _stub_scorer(model)
+        got = sc(hist)
+        assert got.shape == (rows, ni) and got.dtype == torch.float32 and got.is_contiguous()
+        assert torch.equal(got, _want(hist, ni)), pairs
+        assert [h.shape[0] for h, _, _ in sc.fills] == [min(per, rows - s) for s in range(0, rows, per)]
+        assert torch.equal(torch.cat([h for h, _, _ in sc.fills]), hist)
+        assert all(not by_position and part is sc.hist_table for _, part, by_position in sc.fills)
+        assert torch.equal(sc.hist_table.cpu(), part_want)
+        sc.fills.clear()
+        assert torch.equal(sc(hist[:1]), _want(hist[:1], ni))               # fewer positions now: the table is kept
+        assert sc.fills[0][1] is sc.hist_table
+
+
+def test_the_history_part_is_made_per_chunk_where_the_table_is_the_larger_row_set(monkeypatch):
+    rows, ni, length = 3, 17, 2                                              # 6 positions, 17 table rows
+    model = _StubModel(ni)
+    hist = _hist(rows, ni, length)
+    w_hist = model.p.att[0].weight[:, :E].cpu()
+    monkeypatch.setattr(_grid(), "PAIR_CHUNK", 2 * ni)
+    sc = _stub_scorer(model)
+    assert torch.equal(sc(hist), _want(hist, ni))
+    assert sc.hist_table is None and [h.shape[0] for h, _, _ in sc.fills] == [2, 1]
+    for h, part, by_position in sc.fills:
+        assert by_position and part.shape == (h.numel(), N1)
+        assert torch.equal(part.cpu(), model.p.table.cpu()[h.reshape(-1).cpu()] @ w_hist.t())
+    assert int(model.flag.item()) == 0
+
+
+def test_no_rows_no_launch():
+    from deeplearningrecommendationsystem_amd import ops
+    ni = 17
+    for path in ("grid", "forward"):
+        sc = _stub_scorer(_StubModel(ni), path)
+        profiler = ops.KernelProfiler()
+        ops.set_profiler(profiler)
+        try:
+            got = sc(torch.empty((0, 4), dtype=torch.int64, device=DEV))
+        finally:
+            ops.set_profiler(None)
+        assert got.shape == (0, ni) and got.dtype == torch.float32
+        assert profiler.records == [] and getattr(sc, "fills", []) == [] and sc.hist_table is None
+
+
+def test_the_forward_path_walks_the_models_forward(monkeypatch):
+    rows, ni, length = 5, 17, 4
+    model = _StubModel(ni)
+    hist = _hist(rows, ni, length)
+    for pairs in (ni + 3, rows * ni + 7):
+        monkeypatch.setattr(_grid(), "PAIR_CHUNK", pairs)
+        assert torch.equal(_stub_scorer(model, "forward")(hist), _want(hist, ni))
