@@ -29,6 +29,22 @@ struct Tower {
 
 __device__ __forceinline__ f32x4 ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void stg4(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
+// The same store written THROUGH the XCD's L2 (sc1): the line leaves for memory while the kernel runs and is dropped
+// from L2, instead of waiting there, dirty, for the write-back that ends the launch.  A buffer store, so that hipcc
+// counts it in vmcnt like stg4 (an inline-asm global_store would be invisible to it, and every wait it places behind
+// one would come out stricter by the stores it cannot see).  A buffer offset has 32 bits: the window begins at a
+// WAVE-UNIFORM address near the stores (the first row of the wave's sample group), the lanes add small offsets.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_window(float* base) {
+  const uint64_t a = reinterpret_cast<uint64_t>(base);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+  // raw buffer (stride 0), 4 GB - 1 bytes, 32-bit data format
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)hi << 32) | lo), 0, -1, 0x00020000);
+}
+__device__ __forceinline__ void stg4_wt(__amdgpu_buffer_rsrc_t w, uint32_t bytes, const f32x4& v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), w, (int)bytes, 0, 16);   // aux 16 = sc1
+}
 
 // forward A operands of every layer into LDS: s_w[wa_off(l) + ((b*J + j)*64 + lane)*4 + c] = W_l[16b + lane%16][16j + 4(lane/16) + c]
 // (rows past n: zero -- their outputs stay relu(0) = 0 and are never stored).  A dwordx4 of a weight row (inputs

@@ -371,6 +371,16 @@ constexpr int kFwdStores = 5;            // y1 x 2, y2, y3, prob
 
 // Two waves per SIMD: one of a per-sample workgroup and one of a plan workgroup.  The attribute is an ALLOCATION as
 // well as a budget: the compiler pads the kernel (134 registers) to 169 so that a third wave can never join.
+//
+// kNear: a group's sixteen rows of y1 and of y2 (and the spare row, behind the last group) lie inside one 4 GB store
+// window (fwd_rows_near): those rows are written through the L2.  A row stride beyond that keeps the plain stores.  Two
+// instantiations, not a branch in the group loop: behind a branch hipcc no longer counts the stores that follow the
+// next group's loads in straight-line code, and its own wait behind the hand-placed one came out as vmcnt(2) -- three
+// of the group's stores waited for, written through or not.
+constexpr int64_t kNearStride = (int64_t)1 << 26;   // floats: fifteen rows of this stride and a row are under 2^32 bytes
+bool fwd_rows_near(const Tower& T) { return T.ldy[0] < kNearStride && T.ldy[1] < kNearStride; }
+
+template <bool kNear>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -494,9 +504,21 @@ ncfp_fwd_kernel(const Tower T, int64_t m, const Fwd F) {
     layer_fwd<1, 2>(s_w, s_b, lane, q, y1, y2);
     layer_fwd<2, 1>(s_w, s_b, lane, q, y2, y3);
     STAMP(0, stamp++);
+    // y1 and y2 (192 of a sample's 224 bytes; 12.6 MB a step at batch 65536) are written THROUGH the L2, as ncfp_bwd
+    // writes its gz0 rows: the forward is 0.4-0.6 us shorter for it and the backward, which fetches them a group ahead
+    // of their use, no longer (profiles/ncf_store_policy.txt).  y3 keeps its plain store: its upper half-wave parks
+    // at the spare row m, which no 32-bit offset from the group's first row reaches.
+    if constexpr (kNear) {
+      const uint32_t lrow = (uint32_t)(srow - g * 16);    // (the spare row: at most fifteen behind the group's first)
+      const auto wy1 = wt_window(T.y[0] + g * 16 * T.ldy[0]), wy2 = wt_window(T.y[1] + g * 16 * T.ldy[1]);
 #pragma unroll
-    for (int b = 0; b < 2; ++b) stg4(T.y[0] + srow * T.ldy[0] + 16 * b + 4 * q, y1[b]);
-    stg4(T.y[1] + srow * T.ldy[1] + 4 * q, y2[0]);
+      for (int b = 0; b < 2; ++b) stg4_wt(wy1, (lrow * (uint32_t)T.ldy[0] + 16 * b + 4 * q) * 4u, y1[b]);
+      stg4_wt(wy2, (lrow * (uint32_t)T.ldy[1] + 4 * q) * 4u, y2[0]);
+    } else {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) stg4(T.y[0] + srow * T.ldy[0] + 16 * b + 4 * q, y1[b]);
+      stg4(T.y[1] + srow * T.ldy[1] + 4 * q, y2[0]);
+    }
     stg4(T.y[2] + (q < 2 ? srow : m) * T.ldy[2] + 4 * (q & 1), y3[0]);
     // head: prob = act([gmf | h] . wfold + cfold); lanes q < 2 of a sample hold four terms of h each
     float dot;
@@ -798,11 +820,16 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
       f32x4 tg[2];
       tiles_get<2>(tA, q, lo, tg);
       // row b of the sample-ordered buffer (a group's sixteen rows are 4 KB in a piece); a padding lane writes the spare row m
+      // (only the last group has padding lanes, so the spare row is at most fifteen rows behind the group's first).
+      // Written THROUGH the L2: 16.8 MB a step at batch 65536 that nothing reads before ncfp_segsum gathers it from
+      // all eight XCDs; left dirty they were written back after the last wave had retired, with nothing running beside
+      // (profiles/ncf_store_policy.txt: the launch 0.9-1.1 us shorter, a wave's own life unchanged)
       const int brow = (int)(live ? g * 16 + lo : m);
-      float* dz = B.gz + (int64_t)brow * kN0 + 4 * q;
+      const auto wz = wt_window(B.gz + g * 16 * kN0);
+      const uint32_t dz = (uint32_t)((brow - (int)(g * 16)) * kN0 + 4 * q) * 4u;
       dx_layer<0, 2>(s_wt, lane, gz1, w0, w1, [&](int j, const f32x4& d0, const f32x4& d1) {
-        stg4(dz + 16 * j, relu_mask(d0, a0d[j]));
-        stg4(dz + 16 * (j + 1), relu_mask(d1, a0d[j + 1]));
+        stg4_wt(wz, dz + 64u * j, relu_mask(d0, a0d[j]));
+        stg4_wt(wz, dz + 64u * (j + 1), relu_mask(d1, a0d[j + 1]));
       });
       // the sample's two slot records name its row; a sample without a slot (bad id, padding lane) writes the spare slot
       // behind the records (the four lanes of a sample write the same record: an unconditional, countable store)
@@ -1450,10 +1477,11 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   // the plan workgroups get the launch's dynamic LDS size like everyone else: a CU's 160 KB must hold one of them
   // beside a per-sample workgroup, or the plan would wait for a per-sample workgroup to retire
   static_assert(2 * fwd_lds <= 160 * 1024, "ncfp_fwd: a per-sample workgroup and a plan workgroup share a CU's LDS");
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncfp_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+  const auto fwd_kernel = fwd_rows_near(T) ? ncfp_fwd_kernel<true> : ncfp_fwd_kernel<false>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)fwd_lds) != hipSuccess)
     return CTR_ELAUNCH;
-  hipLaunchKernelGGL(ncfp_fwd_kernel, dim3((unsigned)(grid + plan_blocks)), dim3(kThreads), fwd_lds, st, T, d->batch, F);
+  hipLaunchKernelGGL(fwd_kernel, dim3((unsigned)(grid + plan_blocks)), dim3(kThreads), fwd_lds, st, T, d->batch, F);
   return ctr_launch_status();
 }
 
