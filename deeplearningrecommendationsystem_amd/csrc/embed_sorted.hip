@@ -58,10 +58,14 @@ struct Streams {
   Stream s[kMaxStreams];
 };
 
-__device__ __forceinline__ int load_row(const SortJob& j, uint32_t b) {
+// Bucket of sample b, and whether its id is in range.  A bad id (flagged by the forward) contributes to no row, as in
+// the scatter kernels of embed.hip; the counting sort still needs every sample in some bucket, so it rides in bucket 0
+// and is stored with key -1, which the reduce pass skips.
+__device__ __forceinline__ int load_row(const SortJob& j, uint32_t b, bool* ok = nullptr) {
   int64_t r = j.idx ? ctr_ldg(j.idx + (int64_t)b * j.idx_stride) : (int64_t)ctr_ldg(j.xcol + (int64_t)b * j.ldx);
-  if (r < 0 || r >= j.vocab) r = 0;  // same clamp as the forward (the flag was raised there)
-  return (int)r;
+  const bool in_range = r >= 0 && r < j.vocab;
+  if (ok) *ok = in_range;
+  return in_range ? (int)r : 0;
 }
 
 // Counting sort without a single global atomic (65536 returning atomics on 943 addresses
@@ -138,12 +142,13 @@ __global__ void __launch_bounds__(kBlock) sort_scatter_kernel(const SortJobs J, 
   __syncthreads();
   const uint32_t lo = blockIdx.x * chunk, hi = lo + chunk < batch ? lo + chunk : batch;
   for (uint32_t b = lo + threadIdx.x; b < hi; b += kBlock) {
-    const int r = load_row(j, b);
+    bool ok;
+    const int r = load_row(j, b, &ok);
     int64_t c = j.cidx ? ctr_ldg(j.cidx + (int64_t)b * j.cidx_stride) : 0;
-    if (c < 0 || c >= j.cvocab) c = 0;
+    if (c < 0 || c >= j.cvocab) c = -1;  // bad partner id: the product's gradient is dropped (seg_reduce_kernel)
     const int pos = atomicAdd(&s_cur[r], 1);
     j.order[pos] = (int)b;
-    j.keys[pos] = r;
+    j.keys[pos] = ok ? r : -1;
     if (j.cidx) j.ckeys[pos] = (int)c;
   }
 }
@@ -156,7 +161,9 @@ __device__ __forceinline__ void flush_run(float* grad, int row, int width, int c
   ctr_atomic_add_global(p + 3, acc.w);
 }
 
-// blockIdx.y = stream.  `lpr` lanes (width / 4 rounded up to a power of two) share a row, each
+// blockIdx.y = stream.  A key of -1 is a sample with a bad id: its run is summed like any other and dropped where a
+// run is flushed (the LDS merge already reads -1 as "none"); a product sample whose partner id is bad adds zero.
+// `lpr` lanes (width / 4 rounded up to a power of two) share a row, each
 // holding one dwordx4; a group owns kRun consecutive sorted positions, all rows in flight.
 // Runs that lie strictly inside a group's chunk are complete rows: one uncontended atomic.
 // The first and the last run of a chunk may continue in the neighbouring groups; those
@@ -206,14 +213,16 @@ seg_reduce_kernel(const SortJobs J, const Streams T, uint32_t batch, const float
         pr[u] = cc[u];
         if (!use_c) {
           pr[u] = ctr_ldg(st.pidx + (int64_t)bb[u] * st.pidx_stride);
-          if (pr[u] < 0 || pr[u] >= st.pvocab) pr[u] = 0;
+          if (pr[u] < 0 || pr[u] >= st.pvocab) pr[u] = -1;
         }
       }
       if (live) {
 #pragma unroll
         for (int u = 0; u < kRun; ++u) {
-          const float4 t = ctr_ldg(reinterpret_cast<const float4*>(st.ptable + pr[u] * st.width + c));
-          g[u].x *= t.x; g[u].y *= t.y; g[u].z *= t.z; g[u].w *= t.w;
+          const bool pok = pr[u] >= 0;  // bad partner id: row 0 is read and the sample's gradient is zero
+          const float4 t = ctr_ldg(reinterpret_cast<const float4*>(st.ptable + (pok ? pr[u] : 0) * st.width + c));
+          g[u].x = pok ? g[u].x * t.x : 0.f; g[u].y = pok ? g[u].y * t.y : 0.f;
+          g[u].z = pok ? g[u].z * t.z : 0.f; g[u].w = pok ? g[u].w * t.w : 0.f;
         }
       }
     }
@@ -227,7 +236,7 @@ seg_reduce_kernel(const SortJobs J, const Streams T, uint32_t batch, const float
             head_key = cur;
             head = acc;
             first = false;
-          } else if (live) {
+          } else if (live && cur >= 0) {
             flush_run(st.grad, cur, st.width, c, acc);
           }
           acc = make_float4(0.f, 0.f, 0.f, 0.f);

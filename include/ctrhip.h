@@ -87,7 +87,8 @@ int ctr_embed_fwd(const ctr_field_t* fields, int nfields, const float* x, int64_
  * wants a fresh gradient.  Id rows: fp32 atomics (order of accumulation not
  * fixed).  Bag tables (every sample hits the same few rows): reduced per
  * workgroup in LDS, then through `workspace` (device scratch, nullable; see
- * ctr_linear_bwd) or, without it, by atomics. */
+ * ctr_linear_bwd) or, without it, by atomics.  A sample whose id is out of
+ * range (either id of a product field) adds to no row, on every path. */
 int ctr_embed_bwd(const ctr_field_t* fields, int nfields, const float* x, int64_t ldx,
                   int64_t batch, const float* gout, int64_t ldo,
                   float* workspace, int64_t workspace_floats, void* stream);
