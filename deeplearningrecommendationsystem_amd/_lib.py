@@ -30,6 +30,8 @@ CTR_GAUC_SLAB = 1024
 CTR_DIEN_GRID_KEEP = 128
 CTR_DEEPFM_GRID_ITEM_TILE = 128
 CTR_DEEPFM_GRID_USER_TILE = 16
+CTR_PNN_GRID_ITEM_TILE = 128
+CTR_PNN_GRID_USER_TILE = 16
 FIELD_ID_I64, FIELD_ID_F32, FIELD_BAG, FIELD_DENSE, FIELD_PROD_I64 = range(5)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = range(3)
 
@@ -206,6 +208,8 @@ SIGNATURES = {
     "ctr_dien_grid_hidden": (_i, [_p, _p, _i, _l, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _l, _i, _p, _l, _p, _p]),
     "ctr_deepfm_grid_scores": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _l, _p, _l,
                                     _i, _p]),
+    "ctr_pnn_grid_scores": (_i, [_p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _l, _p, _l,
+                                 _i, _p]),
     "ctr_mlp_bwd": (_i, [_p, _l, _l, C.POINTER(MlpLayer), _i, _p, _l, _p, _l, _p, _l, _p]),
     "ctr_negative_sample": (_i, [_p, _l, _l, _l, _i, C.c_uint64, _p, _p, _p, _p]),
     "ctr_assemble_features": (_i, [_p, _p, _l, _p, _i, _l, _p, _i, _l, _p, _l, _p, _p]),

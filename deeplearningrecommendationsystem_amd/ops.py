@@ -1093,6 +1093,77 @@ def deepfm_grid_scores(zu: torch.Tensor, zi: torch.Tensor, su: torch.Tensor, si:
 
 
 # ---------------------------------------------------------------------------
+# PNN over the user x item grid (csrc/pnn_grid.hip)
+# ---------------------------------------------------------------------------
+PNN_GRID_HIDDEN = (256, 128, 64, 32)       # hidden_units: the product layer's width, then the three DNN layers
+PNN_GRID_MAX_EMBED = 256
+PNN_GRID_CROSS = 8                          # inner products of a user-side with an item-side field vector
+PNN_GRID_ITEM_TILE = _lib.CTR_PNN_GRID_ITEM_TILE     # items of a workgroup
+PNN_GRID_USER_TILE = _lib.CTR_PNN_GRID_USER_TILE     # users staged at a time
+
+
+def pnn_grid_supported(hidden_units, embed_dim, model: str = "in") -> bool:
+    """whether ``ctr_pnn_grid_scores`` takes a six-field PNN of these ``hidden_units``, this embedding width and this
+    product mode.  A function of the shapes alone."""
+    hidden = tuple(int(h) for h in hidden_units)
+    dim = int(embed_dim)
+    return model == "in" and hidden == PNN_GRID_HIDDEN and 16 <= dim <= PNN_GRID_MAX_EMBED and dim % 16 == 0
+
+
+def pnn_grid_scores(zu: torch.Tensor, zi: torch.Tensor, fu: torch.Tensor, fi: torch.Tensor, g: torch.Tensor,
+                    d2_w: torch.Tensor, d2_b: torch.Tensor, d3_w: torch.Tensor, d3_b: torch.Tensor,
+                    out_w: torch.Tensor, out_b: torch.Tensor, users: Optional[torch.Tensor] = None, user0: int = 0,
+                    rows: Optional[int] = None, out: Optional[torch.Tensor] = None, row_blocks: int = 0) -> torch.Tensor:
+    """(rows, num_items) float32: ``sigmoid(out_w . relu(d3 relu(d2 relu(zu[u] + zi[i] + g d(u, i)))) + out_b)`` with
+    ``d`` the eight inner products of a user-side vector of ``fu[u]`` (U, 4E) with an item-side vector of ``fi[i]``
+    (I, 2E), for the users ``users`` (1-D int64, validated by the caller) or ``user0 .. user0 + rows`` against every
+    item (ctr_pnn_grid_scores).  ``row_blocks``: workgroups that share an item tile's user tiles, 0 for the launch's
+    own choice; the scores do not depend on it.  A shape the kernel is not built for raises: there is no other path
+    behind this call (``pnn_grid_supported`` says beforehand)."""
+    zu, zi, fu, fi, g, d2_w, d3_w = (_mat(t.detach(), w).contiguous() for t, w in (
+        (zu, "zu"), (zi, "zi"), (fu, "fu"), (fi, "fi"), (g, "g"), (d2_w, "d2_w"), (d3_w, "d3_w")))
+    vecs = [t.detach().reshape(-1).contiguous() for t in (d2_b, d3_b, out_w, out_b)]
+    _lib.require_device(*vecs)
+    if any(t.dtype != torch.float32 for t in vecs):
+        raise ValueError("pnn_grid_scores: the biases and out_w must be float32")
+    d2_b, d3_b, out_w, out_b = vecs
+    nu, ni = zu.shape[0], zi.shape[0]
+    (n2, n1), n3 = d2_w.shape, d3_w.shape[0]
+    if fu.shape[0] != nu or fi.shape[0] != ni or fu.shape[1] % 4 or fi.shape[1] * 2 != fu.shape[1]:
+        raise ValueError("pnn_grid_scores: fu must be (num_users, 4E) and fi (num_items, 2E)")
+    dim = fu.shape[1] // 4
+    if zu.shape[1] != n1 or zi.shape[1] != n1 or g.shape != (n1, PNN_GRID_CROSS):
+        raise ValueError(f"pnn_grid_scores: zu / zi must be as wide as a row of d2_w and g ({n1}, {PNN_GRID_CROSS})")
+    if d3_w.shape[1] != n2 or d2_b.numel() != n2 or d3_b.numel() != n3 or out_w.numel() != n3 or out_b.numel() != 1:
+        raise ValueError("pnn_grid_scores: d3_w must take d2_w's units, a bias holds one element per unit, out_w one per "
+                         "unit of d3_w and out_b one")
+    if users is not None:
+        _i64(users)
+        if users.dim() != 1:
+            raise ValueError("pnn_grid_scores: users must be 1-D")
+        rows, user0 = users.numel(), 0
+    elif rows is None:
+        rows = nu - user0
+    if out is None:
+        out = torch.empty((rows, ni), dtype=torch.float32, device=zu.device)
+    out = _mat(out, "out")
+    if out.shape != (rows, ni):
+        raise ValueError(f"pnn_grid_scores: out must be ({rows}, {ni})")
+    # algorithmic: every table row of the call read once (the user tiles re-read item rows from cache), the scores
+    # written; per pair the eight dots, the 128 x 8 product on the sum of the rows, the two layers and the output dot
+    rc = _timed("pnn_grid_scores",
+                lambda: (4 * (rows * (n1 + 4 * dim) + ni * (n1 + 2 * dim) + rows * ni) + (8 * rows if users is not None else 0),
+                         rows * ni * 2 * (PNN_GRID_CROSS * dim + n1 * PNN_GRID_CROSS + n1 + n1 * n2 + n2 * n3 + n3)),
+                _lib.load().ctr_pnn_grid_scores, zu.data_ptr(), zi.data_ptr(), fu.data_ptr(), fi.data_ptr(),
+                g.data_ptr(), nu, ni, dim, n1, n2, n3, d2_w.data_ptr(), d2_b.data_ptr(), d3_w.data_ptr(),
+                d3_b.data_ptr(), out_w.data_ptr(), out_b.data_ptr(),
+                _lib.ptr(users) if users is not None and rows else None, user0, rows,
+                _lib.ptr(out) if out.numel() else None, _ld(out) if rows else ni, int(row_blocks), _lib.stream_ptr())
+    _lib.check(rc, "ctr_pnn_grid_scores")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # feature interactions
 # ---------------------------------------------------------------------------
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112

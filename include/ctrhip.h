@@ -614,6 +614,36 @@ int ctr_deepfm_grid_scores(const float* zu, const float* zi, const float* su, co
                            const float* out_b, const int64_t* users /*nullable*/, int64_t user0, int64_t rows,
                            float* out, int64_t ldo, int row_blocks, void* stream);
 
+/* PNN (inner mode, six fields) over the user x item grid (csrc/pnn_grid.hip): the scores of `rows` users against EVERY
+ * item in one launch, with no feature matrix.  Every field vector belongs to the user (fields 0, 2, 3, 4) or to the item
+ * (1, 5) and the product layer's output has no activation, so the model splits into table rows the caller makes with
+ * ctr_embed_fwd, ctr_allpairs_fwd and ctr_linear_fwd:
+ *   z1 = zu[u_r] + zi[i] + g d(u_r, i)                                         (n1 = 128 wide; g is (n1, 8))
+ *   d  = (<U0, I0>, <U0, I1>, <I0, U1>, <I0, U2>, <I0, U3>, <U1, I1>, <U2, I1>, <U3, I1>)   the eight cross products, in
+ *        the column order of ctr_allpairs_fwd; U0..U3 = fu[u_r] (user, age, gender, occupation vectors, `embed` floats
+ *        each), I0, I1 = fi[i] (item, movie vectors)
+ *   out[r * ldo + i] = sigmoid(out_w . relu(d3_w relu(d2_w relu(z1) + d2_b) + d3_b) + out_b[0])    (n1 -> n2 = 64 -> n3 = 32)
+ *   u_r = users[r] (users set: any order, repeats allowed) or user0 + r (users NULL; user0 + rows <= num_users)
+ * zu (num_users, n1) / zi (num_items, n1): the first DNN layer applied to a side's part of the product layer's output
+ * (the biases on the item side); fu (num_users, 4 embed), fi (num_items, 2 embed); g = d1_w W2[:, cross columns].  All
+ * dense row-major; d2_w is (n2, n1), d3_w (n3, n2) with contiguous rows, out_w has n3 elements.
+ * Admitted: n1 == 128, n2 == 64, n3 == 32, embed a multiple of 16 in 16 .. 256, num_users, num_items < 2^31; anything
+ * else is CTR_ELIMIT.  A null pointer, a negative count, ldo < num_items, row_blocks < 0 or a row range outside the user
+ * table is CTR_EINVAL; zu / zi / fu / fi / d2_w / d3_w not 16-byte aligned is CTR_EALIGN -- all before anything is
+ * enqueued.  rows == 0 or num_items == 0 enqueues nothing and returns CTR_OK.  Columns past num_items of a row of out
+ * are not touched.  A workgroup takes CTR_PNN_GRID_ITEM_TILE items and walks user tiles of CTR_PNN_GRID_USER_TILE rows;
+ * row_blocks > 0 is the number of workgroups that share an item tile's user tiles, 0 leaves it to the launch (a small
+ * multiple of the CU count in all).  The caller validates `users`: an id outside [0, num_users) is clamped into the
+ * table, not reported.  No atomics; a pair's score is a function of its user's rows, its item's rows and the weights
+ * alone, bitwise, whatever the rows, their order, the items' positions or row_blocks. */
+#define CTR_PNN_GRID_ITEM_TILE 128
+#define CTR_PNN_GRID_USER_TILE 16
+int ctr_pnn_grid_scores(const float* zu, const float* zi, const float* fu, const float* fi, const float* g,
+                        int64_t num_users, int64_t num_items, int embed, int n1, int n2, int n3, const float* d2_w,
+                        const float* d2_b, const float* d3_w, const float* d3_b, const float* out_w, const float* out_b,
+                        const int64_t* users /*nullable*/, int64_t user0, int64_t rows, float* out, int64_t ldo,
+                        int row_blocks, void* stream);
+
 /* gy: gradient of the LAST layer's output; gx (nullable): gradient of x.  workspace is
  * required: (number of workgroups <= 256) * sum_i (n_i*k_i + n_i) floats. */
 int ctr_mlp_bwd(const float* x, int64_t ldx, int64_t m, const ctr_mlp_layer_t* layers, int nlayers,

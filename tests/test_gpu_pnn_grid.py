@@ -1,0 +1,419 @@
+"""GPU: PNN (inner mode) over the user x item grid -- ``ctr_pnn_grid_scores`` (csrc/pnn_grid.hip) behind
+``PNN.catalogue_scorer``: against the float64 oracle, against the per-sample forward, and against its own geometry: a
+pair's score may not depend on which rows, which order, which tile or which launch grid it came from.
+
+Parameters.  A default-initialised PNN is soft: its tower barely moves the score, so a broken tower would pass.  Every
+case is built on the CPU, seeded: the six embedding tables are ``randn * t`` (t = 0.25 at E = 16, 0.15 at E = 48, 0.1 at
+E = 256), every Linear bias is ``rand - 0.5``, the weights of ``product.linear1`` and ``dnn.dnn_network.*`` are
+multiplied by 3, those of ``product.linear2`` by 6 (the knob of the cross condition below) and those of ``output`` by
+3; then the last DNN layer is calibrated in float64 over the case's own grid: weight and bias scaled by 2 / std(z3),
+then each unit's median of the new z3 taken off its bias (z3: the pre-activation of h3).  Features: age ``rand``, gender
+and occupation one-hot, genres Bernoulli(0.09); item 1 has no genre (an empty bag).  Every case with at least 64 pairs
+asserts on its float64 reference that the scores spread (std >= 0.15), that h3 > 0 for 30-70 % of all (pair, unit)
+entries, and that the cross part of z1 -- G d, doubly centred over users and items -- has a standard deviation of at
+least 0.25 std(z1): so that neither the tower, nor the head, nor the dots and the K = 8 product can go soft.
+
+Shapes (IT = ops.PNN_GRID_ITEM_TILE items a workgroup, UT = ops.PNN_GRID_USER_TILE users a tile): one pair, 15 / 16 / 17
+items (a wave's tile), IT - 1 / IT + 1 (a workgroup's eight tiles), several item workgroups, and one or two users more
+than one and two user tiles; ``row_blocks`` = 1 and 2 are the only way the tile loop and its restaging barrier run at
+these sizes.
+
+Measured on an MI355X, max error / (atol + rtol |ref|) against float64 over the cases of section 1 (the lines this
+file prints under ``pytest -s``): 0.21 at E = 16 and 0.21 at E = 256, both at (33, 258), 0.06 at E = 48; the per-sample
+forward on the same pairs reaches 0.16 and 0.21 at (33, 258)."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import golden_util as gu
+from oracle import ctr_oracle as orc
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+IT, UT = 128, 16             # asserted against ops.PNN_GRID_ITEM_TILE / ops.PNN_GRID_USER_TILE below
+HIDDEN = (256, 128, 64, 32)
+RTOL, ATOL = 1e-5, 1e-6      # the project's tolerance for prob (tests/test_gpu_models.py)
+SHAPES_16 = [(1, 1), (5, 15), (5, 16), (5, 17), (3, IT - 1), (3, IT + 1), (33, 2 * IT + 2), (UT + 2, 37), (UT + 1, 20),
+             (2 * UT + 1, 20)]
+SHAPES_256 = [(5, 16), (3, IT + 1), (33, 2 * IT + 2), (UT + 2, 37)]
+CASES = [(nu, ni, 16) for nu, ni in SHAPES_16] + [(nu, ni, 256) for nu, ni in SHAPES_256] + [(5, 17, 48)]
+TABLE_SCALE = {16: 0.25, 48: 0.15, 256: 0.1}
+W_SCALE, W2_SCALE, OUT_SCALE = 3.0, 6.0, 3.0
+SEEDS = {}                   # cases whose default seed (5) misses a condition of _assert_hard
+FIELDS = ("user_embed", "item_embed", "age_embed", "gender_embed", "occupation_embed", "movie_embed")
+CROSS = ((0, 1), (0, 5), (1, 2), (1, 3), (1, 4), (2, 5), (3, 5), (4, 5))     # allpairs columns 0, 4, 5, 6, 7, 11, 13, 14
+CROSS_COLUMNS = (0, 4, 5, 6, 7, 11, 13, 14)
+
+
+def _pnn():
+    from deeplearningrecommendationsystem_amd.model import pnn
+    return pnn
+
+
+def test_the_tiles_are_the_ones_the_shapes_were_chosen_for():
+    from deeplearningrecommendationsystem_amd import ops
+    assert (ops.PNN_GRID_ITEM_TILE, ops.PNN_GRID_USER_TILE) == (IT, UT)
+    assert tuple(_pnn()._CROSS_PAIRS) == CROSS_COLUMNS
+
+
+# ------------------------------------------------------------------ the cases: CPU only, float64 reference
+def _features(nu, ni, gen):
+    """(user_features (nu, 24), item_features (ni, 19)) float32 of the module docstring"""
+    uf = torch.zeros((nu, 24))
+    uf[:, 0] = torch.rand(nu, generator=gen)
+    uf[torch.arange(nu), 1 + torch.randint(0, 2, (nu,), generator=gen)] = 1.0
+    uf[torch.arange(nu), 3 + torch.randint(0, 21, (nu,), generator=gen)] = 1.0
+    itf = (torch.rand((ni, 19), generator=gen) < 0.09).float()
+    if ni > 1:
+        itf[1] = 0.0
+    return uf, itf
+
+
+def _frame(uf, itf):
+    """the full (nu * ni, 45) feature frame, user-major"""
+    nu, ni = uf.shape[0], itf.shape[0]
+    u = torch.arange(nu).repeat_interleave(ni)
+    i = torch.arange(ni).repeat(nu)
+    return torch.cat([u[:, None].to(uf.dtype), i[:, None].to(uf.dtype), uf[u], itf[i]], dim=1)
+
+
+def _parts64(p64, x64):
+    """float64 (z1 (B, 128), its cross part G d (B, 128), z3 (B, 32)) over the frame"""
+    f = orc.six_field_vectors(p64, x64, FIELDS)
+    prod = orc.pnn_inner_products(f)
+    h0 = (F.linear(torch.cat(f, dim=1), p64["product.linear1.weight"], p64["product.linear1.bias"])
+          + F.linear(prod, p64["product.linear2.weight"], p64["product.linear2.bias"]))
+    d1 = p64["dnn.dnn_network.0.weight"]
+    z1 = F.linear(h0, d1, p64["dnn.dnn_network.0.bias"])
+    g = d1 @ p64["product.linear2.weight"][:, list(CROSS_COLUMNS)]
+    d = torch.stack([(f[a] * f[b]).sum(1) for a, b in CROSS], dim=1)
+    assert torch.equal(d, prod[:, list(CROSS_COLUMNS)])
+    h = torch.relu(z1)
+    h = torch.relu(F.linear(h, p64["dnn.dnn_network.1.weight"], p64["dnn.dnn_network.1.bias"]))
+    z3 = F.linear(h, p64["dnn.dnn_network.2.weight"], p64["dnn.dnn_network.2.bias"])
+    return z1, d @ g.T, z3
+
+
+def _build(nu, ni, dim, seed):
+    """(PNN on the CPU with the parameters of the module docstring, user features, item features)"""
+    torch.manual_seed(seed)
+    model = _pnn().PNN(dim, list(HIDDEN), "in", num_users=nu, num_items=ni)
+    gen = torch.Generator().manual_seed(seed + 1000)
+    with torch.no_grad():
+        for name in FIELDS:
+            w = getattr(model, name).weight
+            w.copy_(torch.randn(w.shape, generator=gen) * TABLE_SCALE[dim])
+        linears = [model.product.linear1, model.product.linear2, model.output] + list(model.dnn.dnn_network)
+        for lin in linears:
+            lin.bias.copy_(torch.rand(lin.bias.shape, generator=gen) - 0.5)
+        for lin in [model.product.linear1] + list(model.dnn.dnn_network):
+            lin.weight.mul_(W_SCALE)
+        model.product.linear2.weight.mul_(W2_SCALE)
+        model.output.weight.mul_(OUT_SCALE)
+        uf, itf = _features(nu, ni, gen)
+        # the last DNN layer, calibrated in float64 over the case's own grid
+        x64 = _frame(uf, itf).double()
+        last = model.dnn.dnn_network[2]
+        p64 = {k: v.detach().double() for k, v in model.state_dict().items()}
+        z3 = _parts64(p64, x64)[2]
+        scale = 2.0 / float(z3.std()) if z3.numel() > 1 and float(z3.std()) > 0 else 1.0
+        last.weight.mul_(scale)
+        last.bias.mul_(scale)
+        p64 = {k: v.detach().double() for k, v in model.state_dict().items()}
+        last.bias.sub_(_parts64(p64, x64)[2].median(dim=0).values.float())
+    return model, uf, itf
+
+
+def _reference(model, uf, itf):
+    """float64 (scores (nu, ni), z3 (nu, ni, 32), std of the doubly centred cross part of z1 / std(z1))"""
+    nu, ni = uf.shape[0], itf.shape[0]
+    p64 = {k: v.detach().double() for k, v in model.state_dict().items()}
+    x64 = _frame(uf, itf).double()
+    with torch.no_grad():
+        scores = orc.pnn_forward(p64, x64).view(nu, ni)
+        z1, cross, z3 = _parts64(p64, x64)
+        cross = cross.view(nu, ni, -1)
+        cross = cross - cross.mean(0, keepdim=True) - cross.mean(1, keepdim=True) + cross.mean((0, 1), keepdim=True)
+        ratio = float(cross.std()) / float(z1.std()) if z1.numel() > 1 else 0.0
+    return scores.numpy(), z3.view(nu, ni, -1).numpy(), ratio
+
+
+def _assert_hard(scores, z3, ratio, what):
+    """the conditions of the module docstring: the case exercises the dots, the K = 8 product, the tower and the head"""
+    if scores.size < 64:
+        return
+    assert scores.std() >= 0.15, f"{what}: soft parameters, the scores' standard deviation is {scores.std():.3f}"
+    assert 0.3 <= (z3 > 0).mean() <= 0.7, f"{what}: h3 > 0 for {(z3 > 0).mean():.2f} of the (pair, unit) entries"
+    assert ratio >= 0.25, f"{what}: the centred cross part of z1 has {ratio:.3f} of z1's standard deviation"
+
+
+@functools.lru_cache(maxsize=None)
+def _cpu_case(nu, ni, dim=16):
+    """(model on the CPU, user features, item features, float64 scores), made once and shared: no test changes it"""
+    model, uf, itf = _build(nu, ni, dim, SEEDS.get((nu, ni, dim), 5) + 31 * nu + ni + dim)
+    scores, z3, ratio = _reference(model, uf, itf)
+    _assert_hard(scores, z3, ratio, f"({nu}, {ni}) E = {dim}")
+    return model, uf, itf, scores
+
+
+def _on_device(cpu, nu, ni, dim):
+    model = _pnn().PNN(dim, list(HIDDEN), "in", num_users=nu, num_items=ni)
+    model.load_state_dict(cpu.state_dict())
+    return model.to(DEV).eval()
+
+
+@functools.lru_cache(maxsize=None)
+def _case(nu, ni, dim=16):
+    """(model on the device, scorer, float64 scores)"""
+    from deeplearningrecommendationsystem_amd.data import FeatureAssembler
+    cpu, uf, itf, scores = _cpu_case(nu, ni, dim)
+    model = _on_device(cpu, nu, ni, dim)
+    return model, model.catalogue_scorer(FeatureAssembler(uf.to(DEV), itf.to(DEV))), scores
+
+
+def _rank64(scores64, allowed=None):
+    """float64 ranking, best first, ties by ascending id; rows of ``allowed`` False rank last"""
+    s = np.where(allowed, scores64, -np.inf) if allowed is not None else scores64
+    return np.argsort(-s, axis=1, kind="stable")
+
+
+def _frac(got, scores64):
+    err = np.abs(got.cpu().numpy().astype(np.float64) - scores64)
+    return err.max(), (err / (ATOL + RTOL * np.abs(scores64))).max()
+
+
+# ------------------------------------------------------------------ 1. against float64
+@pytest.mark.parametrize("nu,ni,dim", CASES)
+def test_score_grid_matches_the_float64_oracle(nu, ni, dim):
+    model, scorer, scores64 = _case(nu, ni, dim)
+    assert scorer.path == "grid" and type(scorer) is _pnn()._GridScorer
+    got = scorer.score_grid()
+    assert got.shape == (nu, ni) and got.dtype == torch.float32 and got.is_contiguous()
+    err, frac = _frac(got, scores64)
+    print(f"({nu}, {ni}) E = {dim}: max |error| {err:.3e}, max error / (atol + rtol |ref|) {frac:.3f}")
+    torch.testing.assert_close(got.cpu().double(), torch.from_numpy(scores64), rtol=RTOL, atol=ATOL)
+
+
+# ------------------------------------------------------------------ 2. geometry independence, bitwise
+@pytest.mark.parametrize("nu,ni,dim", [(33, 2 * IT + 2, 16), (UT + 2, 37, 16), (2 * UT + 1, 20, 16), (UT + 2, 37, 256)])
+def test_a_score_does_not_depend_on_the_rows_asked_for(nu, ni, dim):
+    model, scorer, _ = _case(nu, ni, dim)
+    full = scorer.score_grid()
+    assert torch.equal(scorer.score_grid(), full)                             # run to run
+    assert torch.equal(scorer.score_grid([3, 1, 3, 0]), full[[3, 1, 3, 0]])
+    assert torch.equal(scorer.score_grid(torch.arange(nu - 1, -1, -1)), full.flip(0))
+    ranges = [(0, nu), (0, 1), (2, 2), (nu - 1, nu), (1, nu - 1), (UT - 1, UT + 1), (UT, nu), (1, UT + 1), (UT - 5, nu)]
+    for s, e in ranges:
+        rows = scorer.score_rows(s, e)
+        assert rows.shape == (e - s, ni) and rows.is_contiguous()
+        assert torch.equal(rows, full[s:e]), (s, e)
+        assert torch.equal(scorer(s, e), rows)
+
+
+def test_a_score_does_not_depend_on_the_items_position():
+    from deeplearningrecommendationsystem_amd.data import FeatureAssembler
+    nu, ni = 33, 2 * IT + 2
+    model_a, scorer_a, _ = _case(nu, ni)
+    perm = torch.randperm(ni, generator=torch.Generator().manual_seed(2)).to(DEV)
+    model_b = _on_device(_cpu_case(nu, ni)[0], nu, ni, 16)
+    with torch.no_grad():
+        model_b.item_embed.weight.copy_(model_a.item_embed.weight[perm])
+    asm = scorer_a.assembler
+    scorer_b = model_b.catalogue_scorer(FeatureAssembler(asm.user_features, asm.item_features[perm]))
+    assert torch.equal(scorer_b.score_grid(), scorer_a.score_grid()[:, perm])
+
+
+@pytest.mark.parametrize("nu,ni,dim", [(2 * UT + 1, 20, 16), (UT + 2, 37, 16), (UT + 2, 37, 256)])
+def test_a_score_does_not_depend_on_the_launch_geometry(nu, ni, dim):
+    """row_blocks = 1: one workgroup per item tile walks every user tile (the tile loop and its restaging barrier);
+    2: two workgroups share them; 0: the launch's own choice"""
+    model, scorer, _ = _case(nu, ni, dim)
+    own = scorer.score_grid()
+    users = torch.arange(nu - 1, -1, -1)
+    try:
+        for blocks in (1, 2):
+            scorer.row_blocks = blocks
+            assert torch.equal(scorer.score_grid(), own), blocks
+            assert torch.equal(scorer.score_rows(1, nu), own[1:]), blocks
+            assert torch.equal(scorer.score_grid(users), own.flip(0)), blocks
+    finally:
+        scorer.__dict__.pop("row_blocks", None)
+
+
+@pytest.mark.parametrize("nu,ni", [(5, 17), (UT + 2, 37)])
+def test_columns_past_the_items_are_left_alone(nu, ni):
+    from deeplearningrecommendationsystem_amd import ops
+    model, scorer, _ = _case(nu, ni)
+    with torch.no_grad():
+        p, (zu, fu), (zi, fi), g = scorer._shared()
+        d2, d3 = p.dnn[1], p.dnn[2]
+        sentinel = -12345.5
+        buf = torch.full((nu, ni + 3), sentinel, dtype=torch.float32, device=DEV)
+        out = ops.pnn_grid_scores(zu, zi, fu, fi, g, d2.weight, d2.bias, d3.weight, d3.bias, p.out.weight, p.out.bias,
+                                  out=buf[:, :ni], row_blocks=1)
+    assert out.data_ptr() == buf.data_ptr() and out.stride(0) == ni + 3
+    assert torch.equal(buf[:, :ni], scorer.score_grid())
+    assert bool((buf[:, ni:] == sentinel).all())
+
+
+# ------------------------------------------------------------------ 3. against the per-sample forward
+@pytest.mark.parametrize("nu,ni,dim", [(33, 2 * IT + 2, 16), (UT + 2, 37, 16), (5, 17, 16), (33, 2 * IT + 2, 256)])
+def test_score_grid_matches_the_per_sample_forward(nu, ni, dim):
+    model, scorer, scores64 = _case(nu, ni, dim)
+    users = torch.arange(nu, device=DEV).repeat_interleave(ni)
+    items = torch.arange(ni, device=DEV).repeat(nu)
+    with torch.no_grad():
+        want = model(scorer.assembler.feature(users, items)).view(nu, ni)
+    got = scorer.score_grid()
+    print(f"({nu}, {ni}) E = {dim}: {int((got != want).sum())} of {got.numel()} scores differ bitwise, max |difference| "
+          f"{float((got - want).abs().max()):.3e}; against float64: grid {_frac(got, scores64)[1]:.3f}, forward "
+          f"{_frac(want, scores64)[1]:.3f} of the tolerance")
+    torch.testing.assert_close(got, want, rtol=RTOL, atol=ATOL)
+
+
+# ------------------------------------------------------------------ 4. recommend
+def _observed(nu, ni, seed=3):
+    """an ObservedPairs with user 0 having seen everything, user 1 all but two items, the others a random third"""
+    from deeplearningrecommendationsystem_amd.data import ObservedPairs
+    seen = torch.rand((nu, ni), generator=torch.Generator().manual_seed(seed)) < 0.33
+    seen[0] = True
+    seen[1] = True
+    seen[1, [2, ni - 1]] = False
+    u, i = seen.nonzero(as_tuple=True)
+    return ObservedPairs(u.to(DEV), i.to(DEV), nu, ni), seen.numpy()
+
+
+def _own_ranking(scorer, users, n, observed):
+    """topk_rows of the scorer's own scores after rank_mask, -1 where the survivors run out"""
+    from deeplearningrecommendationsystem_amd import ops
+    from deeplearningrecommendationsystem_amd.topn import excluded_rows
+    ni = scorer.num_items
+    scores = scorer.score_grid(users)
+    left = torch.full((scores.shape[0],), ni, dtype=torch.int64, device=DEV)
+    if observed is not None:
+        off, ids = excluded_rows(observed, users)
+        err = torch.zeros(1, dtype=torch.int32, device=DEV)
+        ops.rank_mask(scores, off, ids, err)
+        assert int(err.item()) == 0
+        left -= off.diff()
+    take = min(n, ni)
+    want = torch.full((scores.shape[0], n), -1, dtype=torch.int64, device=DEV)
+    want[:, :take] = ops.topk_rows(scores, take)
+    want[torch.arange(n, device=DEV)[None, :] >= left[:, None]] = -1
+    return want
+
+
+@pytest.mark.parametrize("excluded", [False, True], ids=["all-items", "observed-left-out"])
+def test_recommend_is_the_ranking_of_the_kernels_scores(excluded):
+    nu, ni = 33, 2 * IT + 2
+    model, scorer, scores64 = _case(nu, ni)
+    observed, seen = _observed(nu, ni) if excluded else (None, np.zeros((nu, ni), dtype=bool))
+    want64 = _rank64(scores64, ~seen)
+    left = (~seen).sum(axis=1)
+    for n in (1, 5, ni, ni + 3):
+        got = scorer.recommend(n=n, exclude=observed)
+        assert got.shape == (nu, n) and got.dtype == torch.int64
+        assert torch.equal(got, _own_ranking(scorer, torch.arange(nu, device=DEV), n, observed)), n
+        got = got.cpu().numpy()
+        for u in range(nu):                     # every user: the columns the row fills, then nothing but -1
+            m = min(n, int(left[u]))
+            assert (got[u, m:] == -1).all() and (got[u, :m] >= 0).all(), (n, u)
+            assert not seen[u, got[u, :m]].any(), f"n = {n}, user {u}: an excluded item is recommended"
+            gu.assert_same_ranking(got[u:u + 1, :m], want64[u:u + 1, :m], scores64[u:u + 1], tol=1e-5)
+        if excluded:
+            assert (got[0] == -1).all() and set(got[1, :min(n, 2)]) <= {2, ni - 1}
+
+
+def test_recommend_for_a_user_list_in_chunks(monkeypatch):
+    nu, ni = 2 * UT + 1, 20
+    model, scorer, scores64 = _case(nu, ni)
+    observed, seen = _observed(nu, ni, seed=9)
+    users = torch.tensor([nu - 1, 0, 7, 7, UT, 1, UT - 1] + list(range(3, nu)))
+    whole = scorer.recommend(users, n=6, exclude=observed)
+    assert torch.equal(whole, scorer.recommend(n=6, exclude=observed)[users.to(DEV)])
+    from deeplearningrecommendationsystem_amd import topn
+    monkeypatch.setattr(topn, "SCORE_CHUNK_FLOATS", 5 * ni)                  # five users at a time
+    assert torch.equal(scorer.recommend(users, n=6, exclude=observed), whole)
+    assert torch.equal(scorer.recommend(users.tolist(), n=6, exclude=None), scorer.recommend(users, n=6))
+
+
+# ------------------------------------------------------------------ 5. ranking_metrics, and nothing is left behind
+def test_ranking_metrics_over_the_scorer_and_the_model_is_untouched():
+    from deeplearningrecommendationsystem_amd.evaluator import ranking
+    nu, ni = 33, 2 * IT + 2
+    model, scorer, _ = _case(nu, ni)
+    before = {k: v.clone() for k, v in model.state_dict().items()}
+    training = model.training
+    gen = torch.Generator().manual_seed(11)
+    kind = torch.rand((nu, ni), generator=gen)
+    train = tuple(t.to(DEV) for t in (kind < 0.3).nonzero(as_tuple=True))
+    held = kind > 0.9
+    held[torch.arange(nu), kind.argmax(dim=1)] = True                             # no empty actual row
+    real = tuple(t.to(DEV) for t in held.nonzero(as_tuple=True))
+    grid = scorer.score_grid()
+    keep = grid.clone()
+    a = ranking.ranking_metrics(scorer, real, 10, exclude=(train,), num_users=nu, chunk=7)
+    b = ranking.ranking_metrics(grid, real, 10, exclude=(train,), num_users=nu, chunk=7)
+    assert np.array_equal(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), equal_nan=True), (a, b)
+    assert 0.0 < a.precision <= 1.0
+    assert torch.equal(grid, keep)
+    observed, _ = _observed(nu, ni)
+    scorer.recommend(n=5, exclude=observed)
+    scorer.score_rows(3, 9)
+    for k, v in model.state_dict().items():
+        assert torch.equal(v, before[k]), f"{k} changed"
+    assert model.training == training
+    assert all(p.grad is None for p in model.parameters())
+
+
+def test_a_scorer_is_never_stale():
+    """the weights are read at every call: a scorer made before a parameter changed scores the new parameters"""
+    nu, ni = 5, 17
+    cpu, uf, itf, _ = _cpu_case(nu, ni)
+    from deeplearningrecommendationsystem_amd.data import FeatureAssembler
+    model = _on_device(cpu, nu, ni, 16)
+    scorer = model.catalogue_scorer(FeatureAssembler(uf.to(DEV), itf.to(DEV)))
+    old = scorer.score_grid()
+    with torch.no_grad():
+        model.movie_embed.weight[3] += 0.5
+        model.product.linear2.weight[:, 4] += 0.25                                # a cross column: G changes
+        model.dnn.dnn_network[2].bias[:] += 0.25
+    new = scorer.score_grid()
+    assert not torch.equal(new, old)
+    assert torch.equal(new, model.catalogue_scorer(scorer.assembler).score_grid())
+    users = torch.arange(nu, device=DEV).repeat_interleave(ni)
+    items = torch.arange(ni, device=DEV).repeat(nu)
+    with torch.no_grad():
+        want = model(scorer.assembler.feature(users, items)).view(nu, ni)
+    torch.testing.assert_close(new, want, rtol=RTOL, atol=ATOL)
+
+
+# ------------------------------------------------------------------ 6. errors
+def test_errors():
+    from deeplearningrecommendationsystem_amd.data import FeatureAssembler, ObservedPairs
+    nu, ni = 5, 17
+    model, scorer, _ = _case(nu, ni)
+    assert scorer.path == "grid"
+    for bad in ([nu], [-1], [0, 1, nu + 3]):
+        with pytest.raises(IndexError):
+            scorer.score_grid(bad)
+        with pytest.raises(IndexError):
+            scorer.recommend(bad, n=3)
+    for s, e in ((-1, 2), (2, nu + 1), (3, 2)):
+        with pytest.raises(IndexError):
+            scorer.score_rows(s, e)
+    with pytest.raises(ValueError):
+        scorer.recommend(n=0)
+    pairs = torch.zeros(1, dtype=torch.int64, device=DEV)
+    for shape in ((nu + 1, ni), (nu, ni - 1)):
+        with pytest.raises(ValueError):
+            scorer.recommend(n=3, exclude=ObservedPairs(pairs, pairs, *shape))
+    asm = scorer.assembler
+    for users, items in ((asm.user_features[:-1], asm.item_features), (asm.user_features, asm.item_features[1:])):
+        with pytest.raises(ValueError):
+            model.catalogue_scorer(FeatureAssembler(users, items))
+    assert scorer.score_grid([]).shape == (0, ni) and scorer.recommend([], n=3).shape == (0, 3)
+    assert scorer.score_rows(2, 2).shape == (0, ni)
