@@ -148,6 +148,12 @@ class LoaderNeg(C.Structure):
                 ("indices", C.c_void_p), ("fail_flag", C.c_void_p)]
 
 
+class LoaderPop(C.Structure):
+    """mirror of ``ctr_loader_pop_t``"""
+    _fields_ = [("table", C.c_void_p), ("pos_items", C.c_void_p), ("log_q", C.c_void_p), ("logq_out", C.c_void_p),
+                ("logq_ldo", C.c_int64)]
+
+
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list every `ctr_*` symbol of include/ctrhip.h
@@ -217,6 +223,9 @@ SIGNATURES = {
     "ctr_loader_indices": (_i, [_l, C.c_uint64, _l, _l, _l, _i, _p, _p]),
     "ctr_load_batch_neg": (_i, [_p, _p, C.c_uint64, _l, _l, _l, _i, _p]),   # _p, _p: host Loader, host LoaderNeg
     "ctr_load_batch_groups": (_i, [_p, _p, C.c_uint64, _l, _l, _l, _i, _p]),   # as ctr_load_batch_neg
+    # _p, _p, _p: host Loader, host LoaderNeg, host LoaderPop
+    "ctr_load_batch_neg_pop": (_i, [_p, _p, _p, C.c_uint64, _l, _l, _l, _i, _p]),
+    "ctr_load_batch_groups_pop": (_i, [_p, _p, _p, C.c_uint64, _l, _l, _l, _i, _p]),
     "ctr_eval_candidates": (_i, [_p, _p, _l, _p, _p, _l, _l, _l, _i, C.c_uint64, _p, _l, _p, _p, _p]),
     "ctr_group_rank": (_i, [_p, _l, _l, _i, _p, _p, _p]),
     "ctr_score_counts": (_i, [_p, _p, _l, _p, _p, _p]),
@@ -244,6 +253,8 @@ SIGNATURES = {
     "ctr_bce_bwd": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p]),
     "ctr_group_loss_fwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _l, _p, _p, _p]),
     "ctr_group_loss_bwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _l, _p]),
+    "ctr_group_loss_logq_fwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _l, _p, _p, _p, _l, _p]),
+    "ctr_group_loss_logq_bwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _l, _p, _l, _p]),
     "ctr_din_scatter_bwd": (_i, [_p, _l, _l, _i, _i, _p, _l, _p, _p, _l, _i, _p, _p]),
     "ctr_linear_group_fwd": (_i, [_p, _l, _p, _l, _p, _p, _l, _i, _p, _l, _p, _l, _l, _i, _i, _i, _p]),
     "ctr_linear_dx_masked": (_i, [_p, _l, _p, _l, _p, _l, _i, _p, _l, _i, _p, _l, _p, _l, _p, _l, _i, _l, _i, _i, _p]),

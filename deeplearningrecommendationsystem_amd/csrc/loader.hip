@@ -54,6 +54,36 @@
 // cuts a group (1 + k seldom divides 64), so every position derives its own g and j.
 // tests/loader_group_numpy.py restates this.
 //
+// Weighted negatives (ctr_load_batch_neg_pop, ctr_load_batch_groups_pop).  The uniform draw makes almost every negative
+// of a long-tailed catalogue an item nobody interacts with; these two arms draw from a distribution q over the items,
+// given as an alias table of num_items 64-bit words built on the host (data/sampler.py):
+//     table[c] = (thresh_c << 32) | alias_c        thresh_c a uint32, alias_c an item id; a column that always keeps
+//                                                  itself has alias_c == c (2^32 does not fit the threshold)
+// Everything above stands, with draw_t replaced by item_t: the same hash stream picks a column with its high half and
+// keeps it or takes its alias with its low half,
+//     h      = mix64(nkey ^ mix64(v * 0x100000001B3 + t))                       nkey as above (round index 4)
+//     col    = ((h >> 32) * num_items) >> 32
+//     word   = table[col]
+//     item_t = (h & 0xffffffff) < (word >> 32) ? col : (int32)word              (alias_col == col: col either way)
+//     item   = item_t for the first t < 2^14 with (u, item_t) not observed
+// and the last try with *fail_flag when all are observed, item 0 with *err_flag for a bad user id, as above.  The table
+// draws item i with probability
+//     q_i = (kept_i + sum over c != i with alias_c == i of (2^32 - thresh_c)) / (num_items * 2^32),
+//     kept_i = 2^32 if alias_i == i, else thresh_i
+// (up to the 2^-32 granularity of the two halves), so user u's negatives follow q_i / (1 - Q_u) over the items u has
+// not observed, Q_u the q-mass of the observed ones; an item with q_i == 0 is never drawn, and a user whose unobserved
+// items all have q == 0 fails like one who has observed everything.  Grouped or not as above: the draw depends on
+// (seed, e, v) only, so the two epochs of one (seed, e) still emit the same multiset.
+// The log-q column.  A sampled softmax over such negatives subtracts log q(item) from every logit (group_loss.hip).
+// When logq_out is set, position b of the batch also writes
+//     logq_out[b * logq_ldo] = log_q[item]        item = pos_items[s] for a positive, the drawn item for a negative
+//                                                 (item 0 for a bad user id)
+// a bitwise copy of the float; an item outside [0, num_items) -- a positive's, or an alias of a corrupt table -- raises
+// *err_flag and writes 0.0f.  The features family has no item column in its batch, which is why the loader writes it.
+// The table is 8 B per item (214 KB at 26 744 items: L2-resident); a try is one more dependent load in front of the
+// binary search.  The uniform arms are compiled without any of this: kernels of their own, as for the grouped arm.
+// tests/loader_pop_numpy.py restates this.
+//
 // The draw is a chain of dependent loads per position: users[s] -> indptr[u], indptr[u + 1] -> about log2(row length)
 // probes per try.  Spreading a tile's 64 chains over the four waves would not shorten any of them, and a batch of
 // 65536 positions is 1024 workgroups of 2 KiB LDS and few registers, all resident at once (4 per CU), so every chain of
@@ -165,14 +195,30 @@ struct LoaderDraw {
   int32_t item_col, rating_col;
 };
 
-// the item of negative slot v of user u (header comment); u inside [0, num_users)
-__device__ __forceinline__ int64_t draw_negative(const LoaderDraw& nd, uint64_t v, int64_t u) {
+// what the weighted arm adds to LoaderDraw (header comment: weighted negatives); the uniform kernels never see it
+struct LoaderPop {
+  const uint64_t* table;     // num_items words (thresh << 32) | alias
+  const int64_t* pos_items;  // item id of each positive
+  const float* log_q;        // num_items
+  float* logq_out;           // nullable
+  int64_t logq_ldo;
+};
+
+// the item of negative slot v of user u (header comment); u inside [0, num_users).  kWeighted: the uniform draw picks
+// a column of `table`, the low half of the same hash keeps it or takes its alias.
+template <bool kWeighted>
+__device__ __forceinline__ int64_t draw_negative(const LoaderDraw& nd, const uint64_t* table, uint64_t v, int64_t u) {
   const int64_t lo = ctr_ldg(nd.indptr + u), hi = ctr_ldg(nd.indptr + u + 1);
   const CTR_GLOBAL int32_t* ind = (const CTR_GLOBAL int32_t*)nd.indices;
   const uint64_t slot = v * 0x100000001B3ull;
   uint64_t item = 0;
   for (int t = 0; t < kMaxTries; ++t) {
-    item = ((mix64(nd.nkey ^ mix64(slot + (uint64_t)t)) >> 32) * nd.num_items) >> 32;
+    const uint64_t h = mix64(nd.nkey ^ mix64(slot + (uint64_t)t));
+    item = ((h >> 32) * nd.num_items) >> 32;
+    if constexpr (kWeighted) {
+      const uint64_t word = ((const CTR_GLOBAL uint64_t*)table)[item];
+      if ((uint32_t)h >= (uint32_t)(word >> 32)) item = (uint32_t)word;
+    }
     int64_t a = lo, b = hi;
     while (a < b) {  // first entry of the row that is >= item
       const int64_t mid = a + ((b - a) >> 1);
@@ -188,10 +234,11 @@ __device__ __forceinline__ int64_t draw_negative(const LoaderDraw& nd, uint64_t 
 // ctr_load_batch_neg / ctr_load_batch_groups: load_batch_kernel over the virtual epoch.  The index stage also decides
 // positive or negative and draws; s_neg holds the drawn item, -1 for a positive.  kGrouped: pm permutes the N groups
 // and the position keeps its slot (header comment); otherwise pm permutes the M positions.  One body, a kernel per
-// arm, so that the plain loader and the ungrouped arm keep their registers.
-template <bool kGrouped>
+// arm, so that the plain loader and the ungrouped arm keep their registers.  kWeighted: the draw goes through the alias
+// table and the index stage also writes the log-q column; pop is null in the uniform arms and never read there.
+template <bool kGrouped, bool kWeighted>
 __device__ __forceinline__ void load_neg_tiles(const ctr_loader_t& d, const LoaderPerm& pm, const LoaderDraw& nd,
-                                               int64_t first, int64_t count, int hist16) {
+                                               const LoaderPop* pop, int64_t first, int64_t count, int hist16) {
   __shared__ int64_t s_idx[kTile], s_fu[kTile], s_fi[kTile], s_hu[kTile], s_neg[kTile];
   const int64_t tiles = (count + kTile - 1) / kTile;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -218,10 +265,18 @@ __device__ __forceinline__ void load_neg_tiles(const ctr_loader_t& d, const Load
           bad = true;
           item = 0;
         } else {
-          item = draw_negative(nd, v, u);
+          if constexpr (kWeighted) item = draw_negative<true>(nd, pop->table, v, u);
+          else item = draw_negative<false>(nd, nullptr, v, u);
         }
       }
       s_neg[threadIdx.x] = item;
+      if constexpr (kWeighted) {
+        const int64_t at = item >= 0 ? item : ctr_ldg(pop->pos_items + idx);
+        const bool inside = at >= 0 && (uint64_t)at < nd.num_items;
+        bad = bad || !inside;
+        if (pop->logq_out)   // a copy, bitwise; 0.0f for an id outside the table
+          ctr_stg(pop->logq_out + (base + threadIdx.x) * pop->logq_ldo, inside ? ctr_ldg(pop->log_q + at) : 0.0f);
+      }
       if (d.feat_out) {
         const int64_t u = ctr_ldg(d.feat_users + idx), i = item >= 0 ? item : ctr_ldg(d.feat_items + idx);
         bad = bad || u < 0 || u >= d.num_users || i < 0 || i >= d.num_items;
@@ -263,13 +318,25 @@ __device__ __forceinline__ void load_neg_tiles(const ctr_loader_t& d, const Load
 __global__ void __launch_bounds__(kBlock)
 load_batch_neg_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, int64_t first, int64_t count,
                       int hist16) {
-  load_neg_tiles<false>(d, pm, nd, first, count, hist16);
+  load_neg_tiles<false, false>(d, pm, nd, nullptr, first, count, hist16);
 }
 
 __global__ void __launch_bounds__(kBlock)
 load_batch_groups_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, int64_t first, int64_t count,
                          int hist16) {
-  load_neg_tiles<true>(d, pm, nd, first, count, hist16);
+  load_neg_tiles<true, false>(d, pm, nd, nullptr, first, count, hist16);
+}
+
+__global__ void __launch_bounds__(kBlock)
+load_batch_neg_pop_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, const LoaderPop pop,
+                          int64_t first, int64_t count, int hist16) {
+  load_neg_tiles<false, true>(d, pm, nd, &pop, first, count, hist16);
+}
+
+__global__ void __launch_bounds__(kBlock)
+load_batch_groups_pop_kernel(const ctr_loader_t d, const LoaderPerm pm, const LoaderDraw nd, const LoaderPop pop,
+                             int64_t first, int64_t count, int hist16) {
+  load_neg_tiles<true, true>(d, pm, nd, &pop, first, count, hist16);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -336,12 +403,12 @@ extern "C" int ctr_load_batch(const ctr_loader_t* loader, uint64_t seed, int64_t
 
 namespace {
 
-// both arms over the virtual epoch: the checks, the draw descriptor and the launch
-int launch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch, int64_t first,
-               int64_t count, int shuffle, bool grouped, hipStream_t st) {
+// every arm over the virtual epoch: the checks, the draw descriptor and the launch; weighted: `pop` is required
+int launch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, const ctr_loader_pop_t* pop, bool weighted,
+               uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle, bool grouped, hipStream_t st) {
   CTR_REQUIRE(count >= 0, CTR_EINVAL);
   if (count == 0) return CTR_OK;
-  CTR_REQUIRE(loader && neg, CTR_EINVAL);
+  CTR_REQUIRE(loader && neg && (pop || !weighted), CTR_EINVAL);
   const ctr_loader_t& d = *loader;
   const ctr_loader_neg_t& g = *neg;
   CTR_REQUIRE(g.negatives >= 1 && d.n >= 1 && d.n <= (1ll << 62) / (1 + (int64_t)g.negatives), CTR_EINVAL);
@@ -368,25 +435,53 @@ int launch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t
   nd.item_col = g.item_col;
   nd.rating_col = g.rating_col;
   const int grid = ctr_stream_grid(count, kTile);
-  if (grouped)
-    hipLaunchKernelGGL(load_batch_groups_kernel, dim3(grid), dim3(kBlock), 0, st, d,
-                       make_perm(d.n, seed, epoch, shuffle != 0), nd, first, count, hist16);
-  else
-    hipLaunchKernelGGL(load_batch_neg_kernel, dim3(grid), dim3(kBlock), 0, st, d,
-                       make_perm(m, seed, epoch, shuffle != 0), nd, first, count, hist16);
+  const LoaderPerm pm = make_perm(grouped ? d.n : m, seed, epoch, shuffle != 0);
+  if (weighted) {
+    const ctr_loader_pop_t& w = *pop;
+    CTR_REQUIRE(w.table && w.pos_items && w.log_q && (!w.logq_out || w.logq_ldo >= 1), CTR_EINVAL);
+    CTR_REQUIRE(aligned_to(w.table, 8) && aligned_to(w.pos_items, 8) && aligned_to(w.log_q, 4) &&
+                    aligned_to(w.logq_out, 4),
+                CTR_EALIGN);
+    LoaderPop lp;
+    lp.table = w.table;
+    lp.pos_items = w.pos_items;
+    lp.log_q = w.log_q;
+    lp.logq_out = w.logq_out;
+    lp.logq_ldo = w.logq_ldo;
+    if (grouped)
+      hipLaunchKernelGGL(load_batch_groups_pop_kernel, dim3(grid), dim3(kBlock), 0, st, d, pm, nd, lp, first, count, hist16);
+    else
+      hipLaunchKernelGGL(load_batch_neg_pop_kernel, dim3(grid), dim3(kBlock), 0, st, d, pm, nd, lp, first, count, hist16);
+  } else if (grouped) {
+    hipLaunchKernelGGL(load_batch_groups_kernel, dim3(grid), dim3(kBlock), 0, st, d, pm, nd, first, count, hist16);
+  } else {
+    hipLaunchKernelGGL(load_batch_neg_kernel, dim3(grid), dim3(kBlock), 0, st, d, pm, nd, first, count, hist16);
+  }
   return ctr_launch_status();
 }
 
 }  // namespace
 
+extern "C" int ctr_load_batch_neg_pop(const ctr_loader_t* loader, const ctr_loader_neg_t* neg,
+                                      const ctr_loader_pop_t* pop, uint64_t seed, int64_t epoch, int64_t first,
+                                      int64_t count, int shuffle, void* stream) {
+  return launch_neg(loader, neg, pop, true, seed, epoch, first, count, shuffle, false, (hipStream_t)stream);
+}
+
+extern "C" int ctr_load_batch_groups_pop(const ctr_loader_t* loader, const ctr_loader_neg_t* neg,
+                                         const ctr_loader_pop_t* pop, uint64_t seed, int64_t epoch, int64_t first,
+                                         int64_t count, int shuffle, void* stream) {
+  return launch_neg(loader, neg, pop, true, seed, epoch, first, count, shuffle, true, (hipStream_t)stream);
+}
+
 extern "C" int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
                                   int64_t first, int64_t count, int shuffle, void* stream) {
-  return launch_neg(loader, neg, seed, epoch, first, count, shuffle, false, (hipStream_t)stream);
+  return launch_neg(loader, neg, nullptr, false, seed, epoch, first, count, shuffle, false, (hipStream_t)stream);
 }
 
 extern "C" int ctr_load_batch_groups(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed,
                                      int64_t epoch, int64_t first, int64_t count, int shuffle, void* stream) {
-  return launch_neg(loader, neg, seed, epoch, first, count, shuffle, true, (hipStream_t)stream);
+  return launch_neg(loader, neg, nullptr, false, seed, epoch, first, count, shuffle, true, (hipStream_t)stream);
 }
 
 extern "C" int ctr_loader_indices(int64_t n, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle,

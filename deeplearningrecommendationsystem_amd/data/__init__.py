@@ -1,5 +1,6 @@
 from .features import FeatureAssembler
 from .leave_one_out import LeaveOneOut
 from .loader import DeviceLoader, ObservedPairs
+from .sampler import ItemSampler
 
-__all__ = ["FeatureAssembler", "DeviceLoader", "LeaveOneOut", "ObservedPairs"]
+__all__ = ["FeatureAssembler", "DeviceLoader", "ItemSampler", "LeaveOneOut", "ObservedPairs"]

@@ -29,6 +29,13 @@ groups of ``1 + k`` samples, the positive first -- what ``loss.BPRLoss`` / ``los
 samples of an epoch are the ungrouped loader's, in another order.  ``batch_size`` must be a multiple of ``1 + k``; the
 batch ranges are those of ``num_positives`` groups in batches of ``batch_size // (1 + k)``, scaled by ``1 + k``, so
 neither a tail piece nor the ``world > 1`` split cuts a group.
+
+Weighted negatives.  With ``item_sampler=ItemSampler(...)`` (``data/sampler.py``) the draws follow the sampler's alias
+table instead of the uniform distribution (``ctr_load_batch_neg_pop`` / ``ctr_load_batch_groups_pop``; kernel file's
+header comment), grouped or not, every family; for user u the drawn items follow ``q_i / (1 - Q_u)``, Q_u the table
+mass of u's observed items.  Every buffer set then owns a log-q column, ``log_q_of(rating)``: ``log q(item)`` of each
+sample of the batch, what ``loss.SampledSoftmaxLoss(log_q=loader)`` subtracts.  ``item_sampler=None`` is the uniform
+path, call for call.
 """
 from __future__ import annotations
 
@@ -145,6 +152,13 @@ class _Buffers:
             d.ld_history = history.stride(0)
             d.hist_out, d.hist_ldo = self.hist.data_ptr(), self.hist.stride(0)
         d.err_flag = loader._err.data_ptr()
+        self.logq = self.pop = None
+        if loader._sampler is not None:                    # the log-q column of these rows and the descriptor that fills it
+            sampler, items = loader._sampler
+            self.logq = torch.empty(rows, dtype=torch.float32, device=dev)
+            self.pop = w = _lib.LoaderPop()
+            w.table, w.pos_items, w.log_q = sampler.table.data_ptr(), items.data_ptr(), sampler.log_q.data_ptr()
+            w.logq_out, w.logq_ldo = self.logq.data_ptr(), 1
 
     def batch(self, family):
         rating = self.cols[-1]
@@ -162,7 +176,7 @@ class DeviceLoader:
     ``rating``.  ``len(loader)`` batches; the full-size ones are views of ``static_batch()``."""
 
     def __init__(self, family, columns, ids, feature, history, batch_size, seed, shuffle, drop_last, rank, world,
-                 negatives=0, observed=None, grouped=False):
+                 negatives=0, observed=None, grouped=False, item_sampler=None):
         if int(batch_size) < 1:
             raise ValueError("DeviceLoader: batch_size must be positive")
         if int(world) < 1 or not 0 <= int(rank) < int(world):
@@ -197,9 +211,11 @@ class DeviceLoader:
         self._feature = None if feature is None else (feature, ids[0], ids[1])
         self._history = None if history is None else (history.contiguous(), ids[0])
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._neg = self._fail = None
+        self._neg = self._fail = self._sampler = None
         if self.negatives:
             self._describe_negatives(observed, ids[0])
+        if item_sampler is not None:
+            self._describe_sampler(item_sampler, observed, ids[1])
         if self.grouped:    # the ranges of the groups, scaled: no batch, tail piece or rank boundary cuts a group
             per = 1 + self.negatives
             groups = batch_ranges(self.num_positives, self.batch_size // per, self.drop_last, self.rank, self.world)
@@ -229,34 +245,50 @@ class DeviceLoader:
         g.indptr, g.indices = observed.indptr.data_ptr(), observed.indices.data_ptr()
         g.fail_flag = self._fail.data_ptr()
 
+    def _describe_sampler(self, sampler, observed, items):
+        """weighted negatives: what every buffer set's ``ctr_loader_pop_t`` points into; ``items``: the positives'"""
+        if self.negatives < 1:
+            raise ValueError("DeviceLoader: item_sampler needs negatives >= 1 (and observed=ObservedPairs(...))")
+        if sampler.num_items != observed.num_items:
+            raise ValueError(f"DeviceLoader: the item_sampler covers {sampler.num_items} items, the observed pairs "
+                             f"{observed.num_items}")
+        _lib.require_device(sampler.table, sampler.log_q)
+        # one gather: a positive the table never draws has log q = -inf, and the corrected loss would see it (an id
+        # outside the table is the kernel's business, as everywhere: *err_flag)
+        inside = (items >= 0) & (items < sampler.num_items)
+        log_q = sampler.log_q[items.clamp(0, sampler.num_items - 1)]
+        if bool((inside & torch.isinf(log_q)).any()):
+            raise ValueError("DeviceLoader: a positive's item has probability 0 under the item_sampler (log q = -inf)")
+        self._sampler = (sampler, items)
+
     # -- constructors ------------------------------------------------------------------------------------------
     @classmethod
     def pairs(cls, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0, world=1,
-              negatives=0, observed=None, grouped=False):
+              negatives=0, observed=None, grouped=False, item_sampler=None):
         """MF / NeuralCF: batches ``(user_idx (B,), item_idx (B,)), rating`` -- rating (N,) or (N, 1) float32.
         ``negatives=k, observed=ObservedPairs(...)`` (every constructor): the samples are positives, and each epoch adds
         k drawn negatives per positive, rating 0; ``grouped=True`` (every constructor) keeps each positive's negatives
         behind it (module docstring)"""
         cols = [("users", users), ("items", items), ("ratings", ratings)]
         return cls("pairs", cols, [users, items], None, None, batch_size, seed, shuffle, drop_last, rank, world,
-                   negatives, observed, grouped)
+                   negatives, observed, grouped, item_sampler)
 
     @classmethod
     def features(cls, assembler, users, items, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
-                 world=1, negatives=0, observed=None, grouped=False):
+                 world=1, negatives=0, observed=None, grouped=False, item_sampler=None):
         """feature models: batches ``(x (B, assembler.width),), rating`` -- x as ``assembler.feature`` builds it (for a
         negative: from the drawn item's row)"""
         return cls("features", [("ratings", ratings)], [users, items], assembler, None, batch_size, seed, shuffle,
-                   drop_last, rank, world, negatives, observed, grouped)
+                   drop_last, rank, world, negatives, observed, grouped, item_sampler)
 
     @classmethod
     def sequences(cls, history, users, targets, ratings, batch_size, seed=0, shuffle=True, drop_last=False, rank=0,
-                  world=1, negatives=0, observed=None, grouped=False):
+                  world=1, negatives=0, observed=None, grouped=False, item_sampler=None):
         """DIN / DIEN: batches ``(hist (B, L), target (B,)), rating`` -- hist row = ``history[users[sample]]``,
         ``history`` one (U, L) int64 row per USER (a negative replaces the target and keeps the row)"""
         cols = [("targets", targets), ("ratings", ratings)]
         return cls("sequences", cols, [users, targets], None, history, batch_size, seed, shuffle, drop_last, rank, world,
-                   negatives, observed, grouped)
+                   negatives, observed, grouped, item_sampler)
 
     # -- batches -----------------------------------------------------------------------------------------------
     def __len__(self):
@@ -277,6 +309,12 @@ class DeviceLoader:
         return None if self._full is None else self._full.batch(self.family)
 
     def _launch(self, buffers, epoch, first, count, shuffle):
+        if self._sampler is not None:
+            name = "ctr_load_batch_groups_pop" if self.grouped else "ctr_load_batch_neg_pop"
+            rc = getattr(_lib.load(), name)(C.addressof(buffers.desc), C.addressof(self._neg), C.addressof(buffers.pop),
+                                            self.seed, epoch, first, count, int(shuffle), _lib.stream_ptr())
+            _lib.check(rc, name)
+            return
         if self._neg is not None:
             name = "ctr_load_batch_groups" if self.grouped else "ctr_load_batch_neg"
             rc = getattr(_lib.load(), name)(C.addressof(buffers.desc), C.addressof(self._neg), self.seed, epoch, first,
@@ -297,6 +335,20 @@ class DeviceLoader:
             buffers = self._full if k < self._num_full else self._tail
             self._launch(buffers, int(epoch), first, count, shuffle)
             yield buffers.batch(self.family)
+
+    def log_q_of(self, rating: torch.Tensor) -> torch.Tensor:
+        """the (rows,) float32 log-q column that belongs to the rating buffer ``rating`` -- what the last batch drawn
+        into that buffer set wrote: ``log q(item)`` of every sample, a positive's own item or a negative's drawn one.
+        The buffer is told by its storage address and length (a tail of ``batch_size`` samples has buffers of its
+        own); any other tensor, or a loader without ``item_sampler``, is a ValueError."""
+        if self._sampler is None:
+            raise ValueError("DeviceLoader.log_q_of(): the loader was built without item_sampler")
+        for buffers in (self._full, self._tail):
+            if buffers is not None and torch.is_tensor(rating) and rating.is_cuda:
+                own = buffers.cols[-1]
+                if rating.data_ptr() == own.data_ptr() and rating.shape[0] == own.shape[0] and rating.numel() == own.numel():
+                    return buffers.logq
+        raise ValueError("DeviceLoader.log_q_of(): not one of this loader's rating buffers")
 
     def indices(self, epoch: int, first: int = 0, count=None, shuffle=None) -> torch.Tensor:
         """sample indices of positions [first, first + count) of epoch ``epoch`` (int64, on the device); with negatives

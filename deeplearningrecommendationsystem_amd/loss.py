@@ -8,7 +8,8 @@ contiguous samples, the positive first: the batches of a ``data.DeviceLoader(...
 model's probabilities like ``BCELoss`` (every model of the package ends in a sigmoid) and go back to the logit; the
 definitions stand in the header comment of csrc/group_loss.hip.  Same launch structure as ``BCELoss``: one forward
 launch that also writes the gradient for an upstream of exactly 1, one backward pass otherwise.  The reference has
-no loss over a group.
+no loss over a group.  ``SampledSoftmaxLoss(negatives, log_q=...)`` is the logQ-corrected form for negatives that a
+``DeviceLoader(item_sampler=...)`` does not draw uniformly (``ctr_group_loss_logq_fwd``, same header comment).
 
 Inside a captured step (``graph.GraphedStep``) ``BCELoss`` on NeuralCF's table-row path launches nothing at all: the
 model's backward launch forms the gradient from (prob, target) itself and its second launch stores the loss
@@ -177,22 +178,32 @@ class BCELoss(torch.nn.Module):
 
 class _GroupLossFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, prob, negatives, kind):
-        _lib.require_device(prob)
+    def forward(ctx, prob, negatives, kind, logq):
+        _lib.require_device(prob, logq)
         p = prob.reshape(-1)
         if p.dtype != torch.float32 or p.numel() == 0 or p.numel() % (1 + negatives):
             raise ValueError(f"the group loss expects float32 input of whole groups of 1 + {negatives} samples")
+        q = None if logq is None else logq.detach().reshape(-1)
+        if q is not None and (q.dtype != torch.float32 or q.numel() != p.numel()):
+            raise ValueError("the group loss expects a float32 log_q of one value per sample")
         groups = p.numel() // (1 + negatives)
         loss = torch.empty((), dtype=torch.float32, device=prob.device)
         ws = torch.empty(256, dtype=torch.float32, device=prob.device)
         # d loss / d prob for an upstream gradient of exactly 1, written by the same launch
         gp1 = torch.empty(p.numel(), dtype=torch.float32, device=prob.device) if ctx.needs_input_grad[0] else None
-        rc = _lib.load().ctr_group_loss_fwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1, groups, negatives, kind,
-                                            loss.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            _ticket(prob.device).data_ptr(), _lib.ptr(gp1), _lib.stream_ptr())
-        _lib.check(rc, "ctr_group_loss_fwd")
+        if q is None:
+            rc = _lib.load().ctr_group_loss_fwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1, groups, negatives, kind,
+                                                loss.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _ticket(prob.device).data_ptr(), _lib.ptr(gp1), _lib.stream_ptr())
+            _lib.check(rc, "ctr_group_loss_fwd")
+        else:
+            rc = _lib.load().ctr_group_loss_logq_fwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1, groups, negatives,
+                                                     kind, loss.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     _ticket(prob.device).data_ptr(), _lib.ptr(gp1), q.data_ptr(),
+                                                     q.stride(0) if q.numel() > 1 else 1, _lib.stream_ptr())
+            _lib.check(rc, "ctr_group_loss_logq_fwd")
         ctx.save_for_backward(p)
-        ctx.shape, ctx.negatives, ctx.kind, ctx.gp1 = prob.shape, negatives, kind, gp1
+        ctx.shape, ctx.negatives, ctx.kind, ctx.gp1, ctx.logq = prob.shape, negatives, kind, gp1, q
         return loss
 
     @staticmethod
@@ -200,14 +211,22 @@ class _GroupLossFunction(torch.autograd.Function):
         p, = ctx.saved_tensors
         unit = _units.get(p.device.index)
         if ctx.gp1 is not None and unit is not None and gloss.data_ptr() == unit.data_ptr():
-            return ctx.gp1.view(ctx.shape), None, None  # upstream gradient is THE 1.0: forward wrote this already
+            return ctx.gp1.view(ctx.shape), None, None, None  # upstream gradient is THE 1.0: forward wrote this already
         gp = torch.empty(p.numel(), dtype=torch.float32, device=p.device)
         g = gloss.contiguous()
-        rc = _lib.load().ctr_group_loss_bwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1,
-                                            p.numel() // (1 + ctx.negatives), ctx.negatives, ctx.kind, g.data_ptr(),
-                                            gp.data_ptr(), 1, _lib.stream_ptr())
-        _lib.check(rc, "ctr_group_loss_bwd")
-        return gp.view(ctx.shape), None, None
+        q = ctx.logq
+        if q is None:
+            rc = _lib.load().ctr_group_loss_bwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1,
+                                                p.numel() // (1 + ctx.negatives), ctx.negatives, ctx.kind, g.data_ptr(),
+                                                gp.data_ptr(), 1, _lib.stream_ptr())
+            _lib.check(rc, "ctr_group_loss_bwd")
+        else:
+            rc = _lib.load().ctr_group_loss_logq_bwd(p.data_ptr(), p.stride(0) if p.numel() > 1 else 1,
+                                                     p.numel() // (1 + ctx.negatives), ctx.negatives, ctx.kind,
+                                                     g.data_ptr(), gp.data_ptr(), 1, q.data_ptr(),
+                                                     q.stride(0) if q.numel() > 1 else 1, _lib.stream_ptr())
+            _lib.check(rc, "ctr_group_loss_logq_bwd")
+        return gp.view(ctx.shape), None, None, None
 
 
 class _GroupLoss(torch.nn.Module):
@@ -224,7 +243,7 @@ class _GroupLoss(torch.nn.Module):
         self.group_size = 1 + self.negatives
 
     def forward(self, input: torch.Tensor, target: torch.Tensor = None) -> torch.Tensor:
-        return _GroupLossFunction.apply(input, self.negatives, self.kind)
+        return _GroupLossFunction.apply(input, self.negatives, self.kind, None)
 
 
 class BPRLoss(_GroupLoss):
@@ -234,5 +253,30 @@ class BPRLoss(_GroupLoss):
 
 
 class SampledSoftmaxLoss(_GroupLoss):
-    """sampled softmax: mean over the groups of the cross entropy of the group's logits against slot 0"""
+    """sampled softmax: mean over the groups of the cross entropy of the group's logits against slot 0.
+
+    ``log_q``: the logQ correction for negatives that are not drawn uniformly (header comment of csrc/group_loss.hip):
+    every sample's logit is lowered by ``log q(its item)`` before the softmax.  Either a ``data.DeviceLoader`` built with
+    ``item_sampler`` -- the loss then reads ``loader.log_q_of(target)``, the static column the loader refills, so a
+    captured step stays valid -- or a float32 device tensor of one value per sample.  With a loader, a ``target`` that is
+    not one of its rating buffers is a ValueError; except under ``torch.no_grad()``, where it is an evaluation batch
+    (``Trainer.rank_epoch`` on held-out candidates, which are drawn uniformly) and gets the uncorrected loss, the right
+    form for a uniform q."""
     kind = 1
+
+    def __init__(self, negatives: int, log_q=None):
+        super().__init__(negatives)
+        if log_q is not None and not torch.is_tensor(log_q) and not hasattr(log_q, "log_q_of"):
+            raise ValueError("SampledSoftmaxLoss: log_q is a DeviceLoader built with item_sampler, or a float32 tensor")
+        self.log_q = log_q
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor = None) -> torch.Tensor:
+        log_q = self.log_q
+        if log_q is not None and not torch.is_tensor(log_q):
+            try:
+                log_q = log_q.log_q_of(target)
+            except ValueError:
+                if torch.is_grad_enabled() or log_q._sampler is None:
+                    raise
+                log_q = None
+        return _GroupLossFunction.apply(input, self.negatives, self.kind, log_q)

@@ -127,6 +127,10 @@ class Trainer:
         A loss over groups (one that has ``group_size``: ``loss.BPRLoss``, ``loss.SampledSoftmaxLoss``) needs a loader
         that delivers whole groups of that size."""
         self._check_groups(loader)
+        held = getattr(self.loss_fn, "log_q", None)
+        if held is not None and not torch.is_tensor(held) and held is not loader:
+            raise ValueError("train_epoch: the loss corrects with the log-q column of another loader than the one it is "
+                             "given")
         self.model.train()
         static = loader.static_batch()
         total = torch.zeros((), dtype=torch.float64, device=loader.device)

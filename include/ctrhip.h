@@ -913,6 +913,28 @@ int ctr_load_batch_neg(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, 
 int ctr_load_batch_groups(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, uint64_t seed, int64_t epoch,
                           int64_t first, int64_t count, int shuffle, void* stream);
 
+/* Weighted negatives: ctr_load_batch_neg_pop / ctr_load_batch_groups_pop are the two entry points above with the draw
+ * taken from an alias table instead of uniformly (header comment of csrc/loader.hip): try t of slot v picks column
+ * col = ((h >> 32) * num_items) >> 32 of the table with the same hash h and keeps it when (h & 0xffffffff) < thresh_col,
+ * else takes alias_col; table[c] = (thresh_c << 32) | alias_c, a column that always keeps itself has alias_c == c.
+ * The observed-set rule, the 2^14 tries, *fail_flag and the bad-user rule are unchanged.  ctr_loader_t and
+ * ctr_loader_neg_t are passed as above.  When logq_out is set every position b also writes
+ *     logq_out[b * logq_ldo] = log_q[item of the position]      (a positive: pos_items[s]; a negative: the drawn item)
+ * a bitwise copy; an item id outside [0, num_items) raises *err_flag and writes 0.0f.  A null table, pos_items or log_q,
+ * or a logq_out with logq_ldo < 1, is CTR_EINVAL; a table or pos_items off 8 bytes is CTR_EALIGN. */
+typedef struct ctr_loader_pop {
+  const uint64_t* table;        /* (num_items,) alias-table words */
+  const int64_t* pos_items;     /* (n,) item id of every positive */
+  const float* log_q;           /* (num_items,) log of the table's distribution */
+  float* logq_out;              /* (count,) elements, stride logq_ldo; nullable */
+  int64_t logq_ldo;
+} ctr_loader_pop_t;
+
+int ctr_load_batch_neg_pop(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, const ctr_loader_pop_t* pop,
+                           uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle, void* stream);
+int ctr_load_batch_groups_pop(const ctr_loader_t* loader, const ctr_loader_neg_t* neg, const ctr_loader_pop_t* pop,
+                              uint64_t seed, int64_t epoch, int64_t first, int64_t count, int shuffle, void* stream);
+
 /* ------------------------------------------------------------------------
  * Sampled leave-one-out evaluation (csrc/group_eval.hip): every held-out positive is ranked against k sampled
  * negatives, "1 positive + 99 negatives, HR@10 / NDCG@10".
@@ -1035,6 +1057,16 @@ int ctr_group_loss_fwd(const float* prob, int64_t ldp, int64_t n, int k, int kin
                        int64_t workspace_floats, unsigned int* ticket, float* gprob_unit, void* stream);
 int ctr_group_loss_bwd(const float* prob, int64_t ldp, int64_t n, int k, int kind, const float* gloss, float* gprob,
                        int64_t ldg, void* stream);
+/* The logQ-corrected softmax: the two entry points above with z'_i = z_i - logq[i * ldq] in place of z_i for every
+ * sample, the positive's included (one fp32 subtraction before the maximum); logq[i * ldq] = log q(item of sample i),
+ * what ctr_load_batch_groups_pop writes to logq_out.  Everything else, launches and bitwise reproducibility included,
+ * is as above; a null logq is the uncorrected loss, and logq == 0 everywhere gives its bits.  kind 0 with a logq, or a
+ * logq with ldq < 1, is CTR_EINVAL.  A NaN in logq is a NaN loss. */
+int ctr_group_loss_logq_fwd(const float* prob, int64_t ldp, int64_t n, int k, int kind, float* loss, float* workspace,
+                            int64_t workspace_floats, unsigned int* ticket, float* gprob_unit, const float* logq,
+                            int64_t ldq, void* stream);
+int ctr_group_loss_logq_bwd(const float* prob, int64_t ldp, int64_t n, int k, int kind, const float* gloss, float* gprob,
+                            int64_t ldg, const float* logq, int64_t ldq, void* stream);
 
 /* history-position part of the DIN / DIEN table gradient for the E-wide operand (CTR_DIN_H):
  *   gtable[hist[b,l], :] += gh[(b*len+l)*ldgh + 0:E] + attn[b*len+l] * gpool[(summed ? b : b*len+l)*ldgp + 0:E]
