@@ -32,7 +32,7 @@
 // inside (row, chunk) follows the LDS atomics, so table gradients are reproducible to rounding, not bitwise.
 //
 // Launches: forward  ncfp_prep (projected tables, head fold, chunk histograms + block sums) -> ncfp_fwd (+ bases, offsets);
-// backward  ncfp_bwd -> ncfp_segsum (+ tower dW partials, head fold chain rule) -> ncfp_finish (the table-row products).
+// backward  ncfp_bwd -> ncfp_segsum -> ncfp_finish (the table-row products + tower dW partials, head fold chain rule).
 #include "ctr_common.h"
 
 #include <stdlib.h>
@@ -285,35 +285,39 @@ ncfp_prep_kernel(const Prep A) {
       A.wfold[kHeadW] = acc;
     }
   }
-  if (wave >= ublocks + iblocks) return;
-  // one wave = sixteen table rows: out^T (64 units x 16 rows) = W0half (64 x 64) . X^T (64 x 16 rows)
-  const bool user = wave < ublocks;
-  const int64_t row = (user ? wave : wave - ublocks) * 16 + n, rows = user ? A.nu : A.ni;
+  // one wave = sixteen table rows x 32 units: out^T (32 units x 16 rows) = W0half (32 x 64) . X^T (64 x 16 rows) -- 32
+  // dependent matrix instructions, not 64; the two waves of a row block take the unit blocks {0, 1} and {2, 3}, and an
+  // output's sum over the inputs keeps its order
+  const int64_t rblk = wave >> 1;
+  const int hb = 2 * (int)(wave & 1);
+  if (rblk >= ublocks + iblocks) return;
+  const bool user = rblk < ublocks;
+  const int64_t row = (user ? rblk : rblk - ublocks) * 16 + n, rows = user ? A.nu : A.ni;
   const float* tab = user ? A.mlp_u : A.mlp_i;
   const int coff = user ? 0 : kH;
   const bool live = row < rows;
-  f32x4 x[4], acc[4];
+  f32x4 x[4], acc[2];
 #pragma unroll
   for (int j = 0; j < 4; ++j) x[j] = ldg4(tab + (live ? row : 0) * kH + 16 * j + 4 * q);
 #pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    if (!user && A.b0) acc[b] = ldg4(A.b0 + 16 * b + 4 * q);
+  for (int b = 0; b < 2; ++b) {
+    if (!user && A.b0) acc[b] = ldg4(A.b0 + 16 * (hb + b) + 4 * q);
     else acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    f32x4 w[4];   // A operands straight from the weight rows: W0[16b + n][coff + 16j + 4q + c]
+    f32x4 w[2];   // A operands straight from the weight rows: W0[16 (hb + b) + n][coff + 16j + 4q + c]
 #pragma unroll
-    for (int b = 0; b < 4; ++b) w[b] = ldg4(A.w0 + (int64_t)(16 * b + n) * A.ldw0 + coff + 16 * j + 4 * q);
+    for (int b = 0; b < 2; ++b) w[b] = ldg4(A.w0 + (int64_t)(16 * (hb + b) + n) * A.ldw0 + coff + 16 * j + 4 * q);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[b][c], x[j][c], acc[b], 0, 0, 0);
+      for (int b = 0; b < 2; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[b][c], x[j][c], acc[b], 0, 0, 0);
   }
   if (live) {
     float* dst = A.ptab + ((user ? 0 : A.nu) + row) * kN0 + 4 * q;
 #pragma unroll
-    for (int b = 0; b < 4; ++b) stg4(dst + 16 * b, acc[b]);
+    for (int b = 0; b < 2; ++b) stg4(dst + 16 * (hb + b), acc[b]);
   }
 }
 
@@ -907,17 +911,23 @@ ncfp_bwd_kernel(const Tower T, int64_t m, const Bwd B) {
 // chains of such runs: a chain inside the workgroup's 256 slots is stored as well, one that reaches its first or last
 // slot is added to ST atomically, a thread per column (sixteen consecutive floats from sixteen lanes are one 64-byte
 // atomic segment).  ncfp_bwd zeroes ST, so a row without a sample stays zero.
-//
-// The same launch carries, on workgroups of their own, the second pass over ncfp_bwd's slabs (tower dW / db: 32
-// outputs x 8 part-lanes per workgroup, fixed order) and the head fold's chain rule from the slabs' head sums
-// (ctr_fold_head_bwd's map without the GMF part): both only depend on ncfp_bwd, and run beside the segment sums
-// instead of in a launch of their own in front of them.
 struct Seg {
   const float* gz; const float* aux; const int32_t* offsets;
   const float* gmf_u; const float* gmf_i;
   int64_t nu, ni, m;
   float* st;                                   // (nu + ni, 128), zeroed
-  int seg_blocks, red_blocks;                  // roles by blockIdx.x: [0, seg) segment sums, [seg, seg + red) slabs, last: fold
+};
+
+// ------------------------------------------------------------------ the second pass over ncfp_bwd's slabs
+// Two roles on workgroups of their own: the slab reduction (tower dW / db: 32 outputs x 8 part-lanes per workgroup,
+// fixed order) and the head fold's chain rule from the slabs' head sums (ctr_fold_head_bwd's map without the GMF
+// part).  Both only depend on ncfp_bwd and need no launch of their own.  They ride in front of ncfp_finish's
+// workgroups: that launch is one short latency chain on fewer workgroups than the chip has CUs, so the 87 role
+// workgroups get CUs of their own.  (They rode with the segment sums before, whose workgroups fill every CU several
+// times over.  Measured, profiles/ncf_step_redeal.txt: segment sums 12.0 -> 10.7 us, ncfp_finish 8.1 -> 8.6 us,
+// first or last in the grid -- and 8.5 with both roles returning at once: the price is the 87 workgroups themselves.)
+struct Roles {
+  int red_blocks;                              // by blockIdx.x: [0, red) slabs, red: fold
   const float* slabs; int parts;
   float* gw[kL]; float* gb[kL];                // tower gradients (+=)
   // head fold chain rule: u = linear2.weight (128), w / b = `linear` (64 x 8)
@@ -940,7 +950,7 @@ __device__ __forceinline__ int slab_raw_of(int e) {
   return (v * 64 + ((row >> 2) & 3) * 16 + (col & 15)) * 4 + (row & 3);
 }
 
-__device__ __forceinline__ void slab_reduce_role(const Seg& A, int blk) {
+__device__ __forceinline__ void slab_reduce_role(const Roles& A, int blk) {
   // outputs [32 blk, 32 blk + 32) of the kSlabHead tower sums: lane (o, pl) adds every 8th partial, 8 loads in flight.
   // The last block has spare outputs: the first of them, e == kSlabHead, is the loss of a loss-fused backward -- the
   // slabs' word kSlabLoss summed in the same fixed order, times 1 / batch, stored (not added) to the caller's word
@@ -981,7 +991,7 @@ __device__ __forceinline__ void slab_reduce_role(const Seg& A, int blk) {
   if (threadIdx.x < 32 && is_loss) A.loss[0] = ((s_part[0][o] + s_part[1][o]) + (s_part[2][o] + s_part[3][o])) * A.inv_n;
 }
 
-__device__ __forceinline__ void head_fold_role(const Seg& A) {
+__device__ __forceinline__ void head_fold_role(const Roles& A) {
   // nine columns (sum gz * h [8], sum gz) x 28 part-lanes: every load of a thread in flight at once
   __shared__ float s_p[28][12];
   __shared__ float s_g[12];
@@ -1037,11 +1047,6 @@ constexpr int kSegOpenL = 1, kSegOpenR = 2;          // a parked run continues i
 
 __global__ void __launch_bounds__(kThreads, 3)
 ncfp_segsum_kernel(const Seg A) {
-  if ((int)blockIdx.x >= A.seg_blocks) {
-    if ((int)blockIdx.x < A.seg_blocks + A.red_blocks) slab_reduce_role(A, (int)blockIdx.x - A.seg_blocks);
-    else head_fold_role(A);
-    return;
-  }
   // The chain of a wave is {total || records} -> rows -> sums: lane lo of a group loads the record of slot s0 + lo (the
   // group's records are 256 contiguous bytes) beside the number of slots in use, the fields of slot k reach the other
   // lanes by a shuffle inside the sixteen, and the 32 row loads (gz0 row + partner row of every slot) are requested back
@@ -1201,16 +1206,23 @@ struct Fin {
   float* g_mlp_u; float* g_mlp_i; float* g_gmf_u; float* g_gmf_i;   // (+=), nullable
   float* g_w0; int64_t ldgw0; float* g_b0;                           // (+=), nullable
   float* g_head;                                                     // g of linear2.weight[:64] (+=), nullable
-  int wgs;                                                           // workgroups of one part: gridDim.x = kFinParts * wgs
+  int wgs;                                                           // workgroups of one part
+  Roles roles;                                 // dispatched first: gridDim.x = roles.red_blocks + 1 + kFinParts * wgs
 };
 constexpr int kFinParts = 4;
 
 __global__ void __launch_bounds__(kThreads)
 ncfp_finish_kernel(const Fin A) {
+  if ((int)blockIdx.x <= A.roles.red_blocks) {
+    if ((int)blockIdx.x < A.roles.red_blocks) slab_reduce_role(A.roles, (int)blockIdx.x);
+    else head_fold_role(A.roles);
+    return;
+  }
   __shared__ __attribute__((aligned(16))) float s_dw[2][8 * 256];
   __shared__ float s_sm[kWaves][2][64];
   const int lane = threadIdx.x & 63, q = lane >> 4, n = lane & 15, wave = threadIdx.x >> 6;
-  const int part = (int)blockIdx.x / A.wgs, wg = (int)blockIdx.x - part * A.wgs, h = part & 1;
+  const int fblk = (int)blockIdx.x - (A.roles.red_blocks + 1);
+  const int part = fblk / A.wgs, wg = fblk - part * A.wgs, h = part & 1;
   const int64_t ublocks = (A.nu + 15) / 16, iblocks = (A.ni + 15) / 16;
   const int64_t uwgs = (ublocks + kWaves - 1) / kWaves;
   const bool user = wg < uwgs;
@@ -1428,9 +1440,9 @@ extern "C" int ctr_ncf_proj_workspace_floats(int64_t batch, int64_t num_users, i
 }
 
 // `phases`: 0 = the whole call; else a mask of its launches (a profiler brackets them one by one): forward 1 = projected
-// tables + head fold (+ chunk histograms), 2 = the per-sample kernel (+ the plan's prefixes and offsets); backward 1 = the per-sample kernel, 2 = segment sums + slab reduction +
-// head fold, 4 = the table-row products.  With a target the backward's launch 1 forms the loss terms and launch 2
-// stores the loss.
+// tables + head fold (+ chunk histograms), 2 = the per-sample kernel (+ the plan's prefixes and offsets); backward 1 =
+// the per-sample kernel, 2 = segment sums, 4 = the table-row products + slab reduction + head fold.  With a target the
+// backward's launch 1 forms the loss terms and launch 4 stores the loss.
 extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   CTR_REQUIRE(d && d->batch >= 0, CTR_EINVAL);
   const int phases = d->phases ? d->phases : 3;
@@ -1448,7 +1460,7 @@ extern "C" int ctr_ncf_proj_fwd(const ctr_ncf_proj_t* d, void* stream) {
   // training: the bucket plan -- a rank workgroup per chunk in this launch, the prefix workgroups in the next
   const bool ranks = d->training && d->batch > 0;
   const Plan plan = plan_of(d->plan, nu + ni, d->batch);
-  const int proj_blocks = (int)ctr_ceil_div(pwaves, kWaves) + 1;
+  const int proj_blocks = (int)ctr_ceil_div(2 * pwaves, kWaves) + 1;   // two waves per row block, and the fold workgroup
   const Prep P{d->mlp_user, d->mlp_item, d->layers[0].w, d->layers[0].k, d->layers[0].b, d->ptab, nu, ni,
                d->head_w, d->proj_w, d->ld_proj_w, d->proj_b, d->head_b, d->wfold,
                RankJob{ids, plan, d->ranks, d->batch, proj_blocks}};
@@ -1526,24 +1538,26 @@ extern "C" int ctr_ncf_proj_bwd(const ctr_ncf_proj_t* d, const ctr_ncf_proj_grad
   if (phases & 1) hipLaunchKernelGGL(bwd_kernel, dim3((unsigned)grid), dim3(kThreads), lds_bytes, st, T, m, B);
   rc = ctr_launch_status();
   if (rc != CTR_OK) return rc;
-  // segment sums over the buckets, and beside them (own workgroups) the tower's dW / db partials and the head fold's
-  // chain rule (its GMF part arrives from ncfp_finish)
-  Seg S{gzb, aux, offs, d->gmf_user, d->gmf_item, nu, ni, m, stt, (int)ctr_ceil_div(2 * m, kSegWgSlots),
-        (kSlabHead + 31) / 32,
-        slabs, (int)grid, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, d->head_w, d->proj_w, d->ld_proj_w,
-        d->proj_b, g->g_head_w, g->g_proj_w, g->ld_g_proj_w, g->g_proj_b, g->g_head_b, g->loss, 1.0f / (float)m};
-  for (int l = 0; l < kL; ++l) {
-    S.gw[l] = g->layers[l + 1].gw;
-    S.gb[l] = g->layers[l + 1].gb;
-  }
+  // segment sums over the buckets
+  const Seg S{gzb, aux, offs, d->gmf_user, d->gmf_item, nu, ni, m, stt};
   if (phases & 2)
-    hipLaunchKernelGGL(ncfp_segsum_kernel, dim3((unsigned)(S.seg_blocks + S.red_blocks + 1)), dim3(kThreads), 0, st, S);
+    hipLaunchKernelGGL(ncfp_segsum_kernel, dim3((unsigned)ctr_ceil_div(2 * m, kSegWgSlots)), dim3(kThreads), 0, st, S);
   rc = ctr_launch_status();
   if (rc != CTR_OK) return rc;
+  // the table-row products, and in front of them (own workgroups) the tower's dW / db partials and the head fold's
+  // chain rule (its GMF part comes from the products)
+  Roles R{(kSlabHead + 31) / 32,
+          slabs, (int)grid, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, d->head_w, d->proj_w, d->ld_proj_w,
+          d->proj_b, g->g_head_w, g->g_proj_w, g->ld_g_proj_w, g->g_proj_b, g->g_head_b, g->loss, 1.0f / (float)m};
+  for (int l = 0; l < kL; ++l) {
+    R.gw[l] = g->layers[l + 1].gw;
+    R.gb[l] = g->layers[l + 1].gb;
+  }
   const int64_t fwgs = ctr_ceil_div(ctr_ceil_div(nu, 16), kWaves) + ctr_ceil_div(ctr_ceil_div(ni, 16), kWaves);
   const Fin N{stt, d->mlp_user, d->mlp_item, d->gmf_user, d->gmf_item, d->layers[0].w, d->layers[0].k, d->wfold, nu, ni,
               g->g_mlp_user, g->g_mlp_item, g->g_gmf_user, g->g_gmf_item, g->layers[0].gw, d->layers[0].k, g->layers[0].gb,
-              g->g_head_w, (int)fwgs};
-  if (phases & 4) hipLaunchKernelGGL(ncfp_finish_kernel, dim3((unsigned)(kFinParts * fwgs)), dim3(kThreads), 0, st, N);
+              g->g_head_w, (int)fwgs, R};
+  if (phases & 4)
+    hipLaunchKernelGGL(ncfp_finish_kernel, dim3((unsigned)(R.red_blocks + 1 + kFinParts * fwgs)), dim3(kThreads), 0, st, N);
   return ctr_launch_status();
 }

@@ -12,7 +12,7 @@ no loss over a group.  ``SampledSoftmaxLoss(negatives, log_q=...)`` is the logQ-
 ``DeviceLoader(item_sampler=...)`` does not draw uniformly (``ctr_group_loss_logq_fwd``, same header comment).
 
 Inside a captured step (``graph.GraphedStep``) ``BCELoss`` on NeuralCF's table-row path launches nothing at all: the
-model's backward launch forms the gradient from (prob, target) itself and its second launch stores the loss
+model's backward launch forms the gradient from (prob, target) itself and its last launch stores the loss
 (``deferred_bce`` below, csrc/ncf_proj.hip).  Eager code never takes that road: its loss has to be valid when
 ``loss_fn`` returns."""
 from __future__ import annotations

@@ -770,8 +770,11 @@ class NcfProj:
             # rows, saved activations read; gz0 row stored once + two records
             "ncfp_bwd": lambda: (m * (16 + 16 + 8 + 2 * 256 + 4 * (32 + 16 + 8) + 256 + 32), 4 * m * tower + 2 * m * 8),
             # per slot: its record, the gz0 row and the partner row the record names read; (rows, 128) sums added
+            # (the slab reduction and the head fold left this launch: they ride with ncfp_finish, phase 4)
             "ncfp_segsum": lambda: (2 * m * (256 + 16 + 256) + rows * 512, 2 * 2 * m * 64 * 2),
             # sums + tables read, table gradients read-modify-written; three 64 x 64 products per row
+            # (+ on workgroups of their own: ncfp_bwd's slabs summed into the tower gradients, the head fold's chain
+            # rule and the fused loss -- a few hundred KB, not counted)
             "ncfp_finish": lambda: (rows * (512 + 512 + 4 * 256), 3 * 2 * rows * 64 * 64),
         }[which]
 
@@ -795,7 +798,7 @@ class NcfProj:
         """``grads[id(param)]``: where each parameter's gradient accumulates; ``zero``: the flat buffer behind them,
         cleared by the call's first launch.  With ``target`` (float32, one element per sample, any stride) ``gprob`` is
         not read: the gradient is the binary cross entropy's for an upstream of exactly 1, formed inside the per-sample
-        launch, and ``loss`` (a float32 scalar, optional) receives the mean loss from the call's second launch."""
+        launch, and ``loss`` (a float32 scalar, optional) receives the mean loss from the call's last launch."""
         if getattr(self, "_spent", False):
             # the first backward hands the plan buffer back to its holder: the next forward may have rebuilt it for
             # other ids by the time a second backward over this forward would read it

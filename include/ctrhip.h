@@ -485,8 +485,8 @@ int ctr_act_mask_bwd(float* g, int64_t ldg, const float* y, int64_t ldy, int64_t
  * the binary cross entropy's for an upstream gradient of exactly 1 -- (p - y) / max(p (1 - p), 1e-12) / batch, the
  * expression and the bits of ctr_bce_fwd's gprob_unit -- formed by the per-sample kernel from prob and target; gprob
  * is then not read and may be null.  With `loss` set as well the call STORES the mean loss there (ctr_bce_fwd's
- * value up to fp32 summation order, the same bits from run to run): the per-sample kernel sums the terms, the second
- * launch adds the workgroups' sums in a fixed order, so the word is valid once launch 2 of `phases` has run.  No
+ * value up to fp32 summation order, the same bits from run to run): the per-sample kernel sums the terms, the last
+ * launch adds the workgroups' sums in a fixed order, so the word is valid once launch 4 of `phases` has run.  No
  * launch, ticket or buffer is added.  Refused with CTR_EINVAL before anything is enqueued: `loss` without `target`,
  * ldtarget < 1, neither target nor gprob, and `loss` with an empty batch (there is no mean over no samples). */
 #define CTR_NCF_PROJ_MAX_ROWS 16384
@@ -515,8 +515,8 @@ typedef struct ctr_ncf_proj_grad {
   float* g_proj_w; int64_t ld_g_proj_w; float* g_proj_b; float* g_head_w; float* g_head_b;   /* (+=) */
   float* workspace; int64_t workspace_floats;     /* >= ctr_ncf_proj_workspace_floats(batch, users, items) */
   float* zero_buf; int64_t zero_floats;           /* nullable: cleared by the call's first launch (see ctr_embed_mlp_head_bwd) */
-  int32_t phases; int32_t reserved;               /* 0: the whole call; else a mask (1 per-sample kernel, 2 segment sums + slab
-                                                     reduction + head fold, 4 table-row products), issued in that order */
+  int32_t phases; int32_t reserved;               /* 0: the whole call; else a mask (1 per-sample kernel, 2 segment sums, 4 table-row
+                                                     products + slab reduction + head fold), issued in that order */
   const float* target; int64_t ldtarget;          /* nullable: (batch) BCE targets, element stride; set: gprob is not read */
   float* loss;                                    /* nullable, only with target: the mean BCE loss is stored here */
 } ctr_ncf_proj_grad_t;
