@@ -20,8 +20,8 @@
 // waves, two per SIMD, so that one wave's LDS reads and head sit beside its partner's matrix products.  A sixteen-pair
 // group costs 16 384 matrix-core issue cycles per SIMD and the weight prologue of the order of 10^4, so -- unlike
 // ncf_grid.hip -- a user tile does NOT get a workgroup of its own: gridDim.y is chosen so that the grid is a small
-// multiple of the CU count and every workgroup loops over many user tiles (deepfm_row_blocks below).
-#include "ctr_common.h"
+// multiple of the CU count and every workgroup loops over many user tiles (grid_host.h, grid_row_blocks).
+#include "grid_host.h"
 
 namespace {
 
@@ -37,6 +37,7 @@ constexpr int kItems = CTR_DEEPFM_GRID_ITEM_TILE;   // items of a workgroup
 static_assert(kItems == 16 * kWaves, "a wave owns sixteen items");
 
 #include "mfma16_tower.inc"
+#include "grid_frame.inc"
 
 constexpr int kHeadFloats = 16;                // b3, o0, o1, ob, pad
 constexpr int kFixedFloats = kWFloats + kBFloats + kN2 + kHeadFloats;
@@ -102,11 +103,7 @@ deepfm_grid_scores_kernel(const Tower T, const Grid G) {
     __syncthreads();                                  // the previous tile's rows are read
     {
       // the tile's rows, coalesced: every request before the first LDS store
-      auto user_of = [&](int row) {
-        const int64_t rr = r0 + (row < cnt ? row : cnt - 1);
-        const int64_t u = G.users ? G.users[rr] : G.user0 + rr;
-        return u < 0 ? 0 : u >= G.nu ? G.nu - 1 : u;  // (the caller validates the list: this keeps the reads inside)
-      };
+      auto user_of = [&](int row) { return grid_user(G.users, G.user0, G.nu, r0, cnt, row); };
       f32x4 vz[kStagePasses], vs;
       float va = 0.0f;
 #pragma unroll
@@ -154,42 +151,18 @@ deepfm_grid_scores_kernel(const Tower T, const Grid G) {
         d3 = fmaf(y[bk][0], wv[0], d3); d3 = fmaf(y[bk][1], wv[1], d3);
         d3 = fmaf(y[bk][2], wv[2], d3); d3 = fmaf(y[bk][3], wv[3], d3);
       }
-      d3 += __shfl_xor(d3, 16, 64);
-      d3 += __shfl_xor(d3, 32, 64);
-      dfm += __shfl_xor(dfm, 16, 64);
-      dfm += __shfl_xor(dfm, 32, 64);
-      const float h3 = fmaxf(d3 + b3, 0.0f);
-      const float fm = (au + bI) + dfm;
+      const float h3 = fmaxf(column_sum(d3) + b3, 0.0f);
+      const float fm = (au + bI) + column_sum(dfm);
       if (store) orow[(r0 + r) * G.ldo] = ctr_sigmoid(fmaf(o0, fm, fmaf(o1, h3, ob)));   // (the four lanes of an item agree)
     }
   }
 }
 
-// gridDim.y: user tiles are dealt round-robin over y workgroups per item tile.  One workgroup per CU runs at a time, so
-// the launch takes about ceil(x y / CUs) rounds of (prologue + ceil(utiles / y) tiles); the prologue is charged as 1/32
-// of a tile (10^4 cycles against kUT x 2 x 16 384).  The smallest y with the least cost among the grids of at most
-// kMaxRounds x CUs workgroups, so that a workgroup walks many tiles wherever there are many.
-constexpr int kMaxRounds = 8;
-int64_t deepfm_row_blocks(int64_t xtiles, int64_t utiles) {
-  const int64_t cap = kMaxRounds * kCtrCUs / xtiles > 1 ? kMaxRounds * kCtrCUs / xtiles : 1;
-  const int64_t ymax = utiles < cap ? utiles : cap;
-  int64_t best = 1, best_cost = -1;
-  for (int64_t y = 1; y <= ymax; ++y) {
-    const int64_t cost = ctr_ceil_div(xtiles * y, kCtrCUs) * (1 + 32 * ctr_ceil_div(utiles, y));
-    if (best_cost < 0 || cost < best_cost) best = y, best_cost = cost;
-  }
-  return best;
-}
-
-template <int E16>
-int launch(const Tower& T, const Grid& G, const dim3& grid, hipStream_t stream) {
-  constexpr size_t lds_bytes = sizeof(float) * (size_t)lds_floats(16 * E16);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(deepfm_grid_scores_kernel<E16>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-    return CTR_ELAUNCH;
-  hipLaunchKernelGGL(deepfm_grid_scores_kernel<E16>, grid, dim3(kThreads), lds_bytes, stream, T, G);
-  return ctr_launch_status();
-}
+// grid_row_blocks charges the weight prologue as 1/32 of a user tile: 10^4 cycles against kUT x 2 x 16 384
+constexpr int kTilesPerPrologue = 32;
+constexpr void (*kKernels[8])(const Tower, const Grid) = {   // by E / 16
+    deepfm_grid_scores_kernel<1>, deepfm_grid_scores_kernel<2>, deepfm_grid_scores_kernel<3>, deepfm_grid_scores_kernel<4>,
+    deepfm_grid_scores_kernel<5>, deepfm_grid_scores_kernel<6>, deepfm_grid_scores_kernel<7>, deepfm_grid_scores_kernel<8>};
 
 }  // namespace
 
@@ -198,35 +171,19 @@ extern "C" int ctr_deepfm_grid_scores(const float* zu, const float* zi, const fl
                                       const float* w2, const float* b2, const float* w3, const float* b3,
                                       const float* out_w, const float* out_b, const int64_t* users, int64_t user0,
                                       int64_t rows, float* out, int64_t ldo, int row_blocks, void* stream) {
-  CTR_REQUIRE(rows >= 0 && num_users >= 0 && num_items >= 0 && row_blocks >= 0, CTR_EINVAL);
+  CTR_REQUIRE(grid_users_ok(users, user0, rows, num_users, num_items, out, ldo) && row_blocks >= 0, CTR_EINVAL);
   CTR_REQUIRE(zu && zi && su && si && a && b && w2 && b2 && w3 && b3 && out_w && out_b, CTR_EINVAL);
-  CTR_REQUIRE(ldo >= num_items, CTR_EINVAL);
-  CTR_REQUIRE(users || (user0 >= 0 && user0 <= num_users && rows <= num_users - user0), CTR_EINVAL);
-  CTR_REQUIRE(rows == 0 || num_users >= 1, CTR_EINVAL);
-  CTR_REQUIRE(out || rows == 0 || num_items == 0, CTR_EINVAL);
   if (n1 != kN0 || n2 != kN2 || embed < 16 || embed > 128 || embed % 16 != 0) return CTR_ELIMIT;
-  if (num_users >= ((int64_t)1 << 31) || num_items >= ((int64_t)1 << 31)) return CTR_ELIMIT;
+  CTR_REQUIRE(grid_ids_fit(num_users, num_items), CTR_ELIMIT);
   if (!ctr_aligned16(zu) || !ctr_aligned16(zi) || !ctr_aligned16(su) || !ctr_aligned16(si) || !ctr_aligned16(w2))
     return CTR_EALIGN;
   if (rows == 0 || num_items == 0) return CTR_OK;
   Tower T;
   T.w[0] = w2; T.b[0] = b2; T.y[0] = nullptr; T.ldy[0] = 0;
   const int64_t utiles = ctr_ceil_div(rows, kUT), xtiles = ctr_ceil_div(num_items, kItems);
-  int64_t y = row_blocks > 0 ? row_blocks : deepfm_row_blocks(xtiles, utiles);
-  y = y < utiles ? y : utiles;
-  y = y < 65535 ? y : 65535;
+  const int64_t y = row_blocks > 0 ? row_blocks : grid_row_blocks(xtiles, utiles, kTilesPerPrologue);
   const Grid G{zu, zi, su, si, a, b, w3, b3, out_w, out_b, users, user0, rows, num_users, num_items, out, ldo, utiles};
   // item tiles along x (neighbouring workgroups share their user tile's rows in L2), row blocks along y
-  const dim3 grid((unsigned)xtiles, (unsigned)y);
-  hipStream_t st = (hipStream_t)stream;
-  switch (embed / 16) {
-    case 1: return launch<1>(T, G, grid, st);
-    case 2: return launch<2>(T, G, grid, st);
-    case 3: return launch<3>(T, G, grid, st);
-    case 4: return launch<4>(T, G, grid, st);
-    case 5: return launch<5>(T, G, grid, st);
-    case 6: return launch<6>(T, G, grid, st);
-    case 7: return launch<7>(T, G, grid, st);
-    default: return launch<8>(T, G, grid, st);
-  }
+  return grid_launch(kKernels[embed / 16 - 1], dim3((unsigned)xtiles, grid_clamp_y(y, utiles)), kThreads,
+                     sizeof(float) * (size_t)lds_floats(embed), stream, T, G);
 }

@@ -27,7 +27,7 @@
 // and under a permutation of the table.
 //
 // Cost: 44 matrix instructions per position and sixteen pairs (76 past kKeep), 2 (64 x 32 + 16 x 48) flop a pair.
-#include "ctr_common.h"
+#include "grid_host.h"
 
 namespace {
 
@@ -46,6 +46,7 @@ constexpr int kKeep = CTR_DIEN_GRID_KEEP;      // positions whose score stays in
 constexpr int kItems = 16 * kWaves;            // items of a workgroup
 
 #include "mfma16_tower.inc"
+#include "grid_frame.inc"
 
 constexpr int kLdsFloats = kWFloats + kBFloats + kPB * kHP + kWaves * kKeep * 16;
 constexpr int kStagePieces = kPB * (kHP / 4);                                   // 16-byte pieces of a block
@@ -83,9 +84,7 @@ __device__ __forceinline__ float position_score(const float* s_w, const float* s
     s = fmaf(y[b][0], w3[b][0], s); s = fmaf(y[b][1], w3[b][1], s);
     s = fmaf(y[b][2], w3[b][2], s); s = fmaf(y[b][3], w3[b][3], s);
   }
-  s += __shfl_xor(s, 16, 64);
-  s += __shfl_xor(s, 32, 64);
-  return s;
+  return column_sum(s);
 }
 
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -226,17 +225,8 @@ extern "C" int ctr_dien_grid_hidden(const float* at, const float* hp, int hp_by_
   T.w[0] = w2; T.b[0] = b2; T.y[0] = nullptr; T.ldy[0] = 0;
   const int64_t tiles = ctr_ceil_div(rows, kRT);
   const Grid G{at, hp, hp_by_position != 0, w3, b_ih, w_hh, b_hh, hist, rows, num_items, len, out, ldo, err_flag, tiles};
-  constexpr size_t lds_bytes = sizeof(float) * (size_t)kLdsFloats;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(dien_grid_hidden_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds_bytes) != hipSuccess)
-    return CTR_ELAUNCH;
-  // item tiles along x (neighbouring workgroups share their position block's rows in L2), row tiles along y: as many
-  // workgroups as fill the machine a few times over, each walking its share of the row tiles behind one weight prologue
+  // item tiles along x (neighbouring workgroups share their position block's rows in L2), row tiles along y
   const int64_t gx = ctr_ceil_div(num_items, kItems);
-  int64_t gy = ctr_ceil_div((int64_t)kCtrCUs * 8, gx);
-  gy = gy < tiles ? gy : tiles;
-  gy = gy < 65535 ? gy : 65535;
-  const dim3 grid((unsigned)gx, (unsigned)gy);
-  hipLaunchKernelGGL(dien_grid_hidden_kernel, grid, dim3(kThreads), lds_bytes, (hipStream_t)stream, T, G);
-  return ctr_launch_status();
+  return grid_launch(dien_grid_hidden_kernel, dim3((unsigned)gx, grid_history_y(gx, tiles)), kThreads,
+                     sizeof(float) * (size_t)kLdsFloats, stream, T, G);
 }

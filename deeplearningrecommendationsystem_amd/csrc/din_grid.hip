@@ -22,7 +22,7 @@
 //
 // Cost: 128 v_mfma_f32_16x16x4_f32 per position and sixteen pairs (16384 flop a pair and position), 4096 issue cycles
 // per SIMD; the weight prologue (32 KiB) is paid once per workgroup, which walks several row tiles.
-#include "ctr_common.h"
+#include "grid_host.h"
 
 namespace {
 
@@ -38,6 +38,7 @@ constexpr int kRT = 4;                         // history rows of a row tile (th
 constexpr int kItems = 16 * kWaves;            // items of a workgroup
 
 #include "mfma16_tower.inc"
+#include "grid_frame.inc"
 
 constexpr int kLdsFloats = kWFloats + kBFloats + kN[0] + kPB * (kN1 + kE);
 static_assert((kPB * (kN1 / 4)) % kThreads == 0 && (kPB * (kE / 4)) % kThreads == 0,
@@ -151,8 +152,7 @@ din_grid_pool_kernel(const Tower T, const Pool G) {
           s = fmaf(y[b][0], wv[0], s); s = fmaf(y[b][1], wv[1], s);
           s = fmaf(y[b][2], wv[2], s); s = fmaf(y[b][3], wv[3], s);
         }
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);                   // (the four lanes of a column agree, bitwise)
+        s = column_sum(s);                            // (the four lanes of a column agree, bitwise)
         // online softmax over the row's positions; this lane's columns 16q .. 16q + 15 of the weighted sum
         const float mnew = fmaxf(mx, s);
         const float scale = expf(mx - mnew), ev = expf(s - mnew);
@@ -202,17 +202,8 @@ extern "C" int ctr_din_grid_pool(const float* table, int64_t num_items, int embe
   T.w[0] = w2; T.b[0] = b2; T.y[0] = nullptr; T.ldy[0] = 0;
   const int64_t tiles = ctr_ceil_div(rows, kRT);
   const Pool G{table, at, ah, ah_by_position != 0, w3, hist, rows, num_items, len, out, ldo, err_flag, tiles};
-  constexpr size_t lds_bytes = sizeof(float) * (size_t)kLdsFloats;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(din_grid_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds_bytes) != hipSuccess)
-    return CTR_ELAUNCH;
-  // item tiles along x (neighbouring workgroups share their position block's rows in L2), row tiles along y: as many
-  // workgroups as fill the machine a few times over, each walking its share of the row tiles behind one weight prologue
+  // item tiles along x (neighbouring workgroups share their position block's rows in L2), row tiles along y
   const int64_t gx = ctr_ceil_div(num_items, kItems);
-  int64_t gy = ctr_ceil_div((int64_t)kCtrCUs * 8, gx);
-  gy = gy < tiles ? gy : tiles;
-  gy = gy < 65535 ? gy : 65535;
-  const dim3 grid((unsigned)gx, (unsigned)gy);
-  hipLaunchKernelGGL(din_grid_pool_kernel, grid, dim3(kThreads), lds_bytes, (hipStream_t)stream, T, G);
-  return ctr_launch_status();
+  return grid_launch(din_grid_pool_kernel, dim3((unsigned)gx, grid_history_y(gx, tiles)), kThreads,
+                     sizeof(float) * (size_t)kLdsFloats, stream, T, G);
 }

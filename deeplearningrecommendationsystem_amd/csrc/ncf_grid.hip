@@ -22,7 +22,7 @@
 // Cost: 44 v_mfma_f32_16x16x4_f32 per sixteen pairs (5376 flop a pair with the head), 1408 issue cycles per SIMD; the
 // weight prologue is of the order of 10^4 cycles per workgroup against 4 x 32 groups x
 // 1408 cycles per user tile, and a workgroup walks several user tiles once the grid's second dimension is exhausted.
-#include "ctr_common.h"
+#include "grid_host.h"
 
 namespace {
 
@@ -38,6 +38,7 @@ constexpr int kUT = 128;                       // users of a user tile: 64 KiB o
 constexpr int kItems = 16 * kWaves;            // items of a workgroup
 
 #include "mfma16_tower.inc"
+#include "grid_frame.inc"
 
 constexpr int kHeadFloats = 16;                // wfold[64 .. 71], cfold, pad
 constexpr int kLdsFloats = kWFloats + kBFloats + kHeadFloats + 2 * kUT * 64;
@@ -97,9 +98,7 @@ ncf_grid_scores_kernel(const Tower T, const Grid G) {
 #pragma unroll
       for (int e = 0; e < kStagePasses; ++e) {
         const int row = (threadIdx.x >> 4) + e * (kThreads / 16);
-        const int64_t rr = r0 + (row < cnt ? row : cnt - 1);
-        int64_t u = G.users ? G.users[rr] : G.user0 + rr;
-        u = u < 0 ? 0 : u >= G.nu ? G.nu - 1 : u;     // (the caller validates the list: this keeps the reads inside)
+        const int64_t u = grid_user(G.users, G.user0, G.nu, r0, cnt, row);
         vp[e] = ldg4(G.pu + u * kN0 + 4 * (threadIdx.x & 15));
         vg[e] = ldg4(G.gu + u * kP + 4 * (threadIdx.x & 15));
       }
@@ -147,8 +146,7 @@ ncf_grid_scores_kernel(const Tower T, const Grid G) {
         d2 = fmaf(y3[0][1], wv[1], d2); d2 = fmaf(y3[0][2], wv[2], d2); d2 = fmaf(y3[0][3], wv[3], d2);
         dot += q < 2 ? d2 : 0.0f;
       }
-      dot += __shfl_xor(dot, 16, 64);
-      dot += __shfl_xor(dot, 32, 64);
+      dot = column_sum(dot);
       if (store) orow[(r0 + r) * G.ldo] = ctr_act(dot + hc, G.act);   // (the four lanes of an item agree)
     }
   }
@@ -161,14 +159,11 @@ extern "C" int ctr_ncf_grid_scores(const float* p_user, const float* p_item, con
                                    const ctr_mlp_layer_t* layers, int nlayers, const float* wfold, const float* cfold,
                                    int fold_k, const int64_t* users, int64_t user0, int64_t rows, int act, float* out,
                                    int64_t ldo, void* stream) {
-  CTR_REQUIRE(rows >= 0 && num_users >= 0 && num_items >= 0 && nlayers >= 0, CTR_EINVAL);
+  CTR_REQUIRE(grid_users_ok(users, user0, rows, num_users, num_items, out, ldo) && nlayers >= 0, CTR_EINVAL);
   CTR_REQUIRE(p_user && p_item && gmf_user && gmf_item && layers && wfold && cfold, CTR_EINVAL);
-  CTR_REQUIRE(ldo >= num_items && act >= CTR_ACT_NONE && act <= CTR_ACT_SIGMOID, CTR_EINVAL);
-  CTR_REQUIRE(users || (user0 >= 0 && user0 <= num_users && rows <= num_users - user0), CTR_EINVAL);
-  CTR_REQUIRE(rows == 0 || num_users >= 1, CTR_EINVAL);
-  CTR_REQUIRE(out || rows == 0 || num_items == 0, CTR_EINVAL);
+  CTR_REQUIRE(act >= CTR_ACT_NONE && act <= CTR_ACT_SIGMOID, CTR_EINVAL);
   if (mf_dim != kP || width != kN0 || nlayers != kL || fold_k != kNL) return CTR_ELIMIT;
-  if (num_users >= ((int64_t)1 << 31) || num_items >= ((int64_t)1 << 31)) return CTR_ELIMIT;
+  CTR_REQUIRE(grid_ids_fit(num_users, num_items), CTR_ELIMIT);
   Tower T;
   for (int l = 0; l < kL; ++l) {
     const ctr_mlp_layer_t& s = layers[l];
@@ -182,12 +177,7 @@ extern "C" int ctr_ncf_grid_scores(const float* p_user, const float* p_item, con
   const int64_t utiles = ctr_ceil_div(rows, kUT);
   const Grid G{p_user, p_item, gmf_user, gmf_item, wfold, cfold, users, user0, rows, num_users, num_items, out, ldo, act,
                utiles};
-  constexpr size_t lds_bytes = sizeof(float) * (size_t)kLdsFloats;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(ncf_grid_scores_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds_bytes) != hipSuccess)
-    return CTR_ELAUNCH;
   // item tiles along x (neighbouring workgroups share their user tile's rows in L2), user tiles along y
-  const dim3 grid((unsigned)ctr_ceil_div(num_items, kItems), (unsigned)(utiles < 65535 ? utiles : 65535));
-  hipLaunchKernelGGL(ncf_grid_scores_kernel, grid, dim3(kThreads), lds_bytes, (hipStream_t)stream, T, G);
-  return ctr_launch_status();
+  const dim3 grid((unsigned)ctr_ceil_div(num_items, kItems), grid_clamp_y(utiles, utiles));
+  return grid_launch(ncf_grid_scores_kernel, grid, kThreads, sizeof(float) * (size_t)kLdsFloats, stream, T, G);
 }

@@ -34,8 +34,8 @@
 // eight waves, two per SIMD (amdgpu_waves_per_eu(2, 2): up to 256 registers a lane).  A sixteen-pair group is 176
 // matrix products in step 2 and E / 8 in step 1 (2 at E = 16, 32 at E = 256): 5696 .. 6656 matrix-core issue cycles of
 // its SIMD.  As in deepfm_grid.hip a user tile does NOT get a workgroup of its own: gridDim.y is chosen so that the
-// grid is a small multiple of the CU count (pnn_row_blocks below).
-#include "ctr_common.h"
+// grid is a small multiple of the CU count (grid_host.h, grid_row_blocks).
+#include "grid_host.h"
 
 namespace {
 
@@ -54,6 +54,7 @@ static_assert(kItems == 16 * kWaves, "a wave owns sixteen items");
 static_assert(kUT == 16, "a user tile is the sixteen rows of a matrix-core tile");
 
 #include "mfma16_tower.inc"
+#include "grid_frame.inc"
 
 constexpr int kHeadFloats = 48;                // the 32 output weights, the output bias, pad
 constexpr int kFixedFloats = kWFloats + kBFloats + kHeadFloats;
@@ -135,11 +136,7 @@ pnn_grid_scores_kernel(const Tower T, const Grid G) {
     const int64_t r0 = ut * kUT;
     const int cnt = (int)(G.rows - r0 < kUT ? G.rows - r0 : kUT);
     // rows past cnt repeat the tile's last user: read, multiplied, never stored
-    auto user_of = [&](int row) {
-      const int64_t rr = r0 + (row < cnt ? row : cnt - 1);
-      const int64_t u = G.users ? G.users[rr] : G.user0 + rr;
-      return u < 0 ? 0 : u >= G.nu ? G.nu - 1 : u;    // (the caller validates the list: this keeps the reads inside)
-    };
+    auto user_of = [&](int row) { return grid_user(G.users, G.user0, G.nu, r0, cnt, row); };
     __syncthreads();                                  // the previous tile's rows are read
     // the tile's ZU rows, coalesced: requested here, stored behind step 1
     const f32x4 vz = ldg4(G.zu + user_of(threadIdx.x >> 5) * kN1 + 4 * (threadIdx.x & 31));
@@ -202,28 +199,14 @@ pnn_grid_scores_kernel(const Tower T, const Grid G) {
         dot = fmaf(y3[b][0], wv[0], dot); dot = fmaf(y3[b][1], wv[1], dot);
         dot = fmaf(y3[b][2], wv[2], dot); dot = fmaf(y3[b][3], wv[3], dot);
       }
-      dot += __shfl_xor(dot, 16, 64);
-      dot += __shfl_xor(dot, 32, 64);
+      dot = column_sum(dot);
       if (store) orow[(r0 + r) * G.ldo] = ctr_sigmoid(dot + s_hd[kN3]);   // (the four lanes of an item agree)
     }
   }
 }
 
-// gridDim.y: user tiles are dealt round-robin over y workgroups per item tile.  One workgroup per CU runs at a time, so
-// the launch takes about ceil(x y / CUs) rounds of (prologue + ceil(utiles / y) tiles); the prologue is charged as 1/16
-// of a tile (10^4 cycles against kUT x 2 x 5696).  The smallest y with the least cost among the grids of at most
-// kMaxRounds x CUs workgroups, so that a workgroup walks many tiles wherever there are many.
-constexpr int kMaxRounds = 8;
-int64_t pnn_row_blocks(int64_t xtiles, int64_t utiles) {
-  const int64_t cap = kMaxRounds * kCtrCUs / xtiles > 1 ? kMaxRounds * kCtrCUs / xtiles : 1;
-  const int64_t ymax = utiles < cap ? utiles : cap;
-  int64_t best = 1, best_cost = -1;
-  for (int64_t y = 1; y <= ymax; ++y) {
-    const int64_t cost = ctr_ceil_div(xtiles * y, kCtrCUs) * (1 + 16 * ctr_ceil_div(utiles, y));
-    if (best_cost < 0 || cost < best_cost) best = y, best_cost = cost;
-  }
-  return best;
-}
+// grid_row_blocks charges the weight prologue as 1/16 of a user tile: 10^4 cycles against kUT x 2 x 5696
+constexpr int kTilesPerPrologue = 16;
 
 }  // namespace
 
@@ -232,14 +215,10 @@ extern "C" int ctr_pnn_grid_scores(const float* zu, const float* zi, const float
                                    const float* d2_w, const float* d2_b, const float* d3_w, const float* d3_b,
                                    const float* out_w, const float* out_b, const int64_t* users, int64_t user0,
                                    int64_t rows, float* out, int64_t ldo, int row_blocks, void* stream) {
-  CTR_REQUIRE(rows >= 0 && num_users >= 0 && num_items >= 0 && row_blocks >= 0, CTR_EINVAL);
+  CTR_REQUIRE(grid_users_ok(users, user0, rows, num_users, num_items, out, ldo) && row_blocks >= 0, CTR_EINVAL);
   CTR_REQUIRE(zu && zi && fu && fi && g && d2_w && d2_b && d3_w && d3_b && out_w && out_b, CTR_EINVAL);
-  CTR_REQUIRE(ldo >= num_items, CTR_EINVAL);
-  CTR_REQUIRE(users || (user0 >= 0 && user0 <= num_users && rows <= num_users - user0), CTR_EINVAL);
-  CTR_REQUIRE(rows == 0 || num_users >= 1, CTR_EINVAL);
-  CTR_REQUIRE(out || rows == 0 || num_items == 0, CTR_EINVAL);
   if (n1 != kN1 || n2 != kN[0] || n3 != kN3 || embed < 16 || embed > kMaxE || embed % 16 != 0) return CTR_ELIMIT;
-  if (num_users >= ((int64_t)1 << 31) || num_items >= ((int64_t)1 << 31)) return CTR_ELIMIT;
+  CTR_REQUIRE(grid_ids_fit(num_users, num_items), CTR_ELIMIT);
   if (!ctr_aligned16(zu) || !ctr_aligned16(zi) || !ctr_aligned16(fu) || !ctr_aligned16(fi) || !ctr_aligned16(d2_w) ||
       !ctr_aligned16(d3_w))
     return CTR_EALIGN;
@@ -248,16 +227,9 @@ extern "C" int ctr_pnn_grid_scores(const float* zu, const float* zi, const float
   T.w[0] = d2_w; T.b[0] = d2_b; T.y[0] = nullptr; T.ldy[0] = 0;
   T.w[1] = d3_w; T.b[1] = d3_b; T.y[1] = nullptr; T.ldy[1] = 0;
   const int64_t utiles = ctr_ceil_div(rows, kUT), xtiles = ctr_ceil_div(num_items, kItems);
-  int64_t y = row_blocks > 0 ? row_blocks : pnn_row_blocks(xtiles, utiles);
-  y = y < utiles ? y : utiles;
-  y = y < 65535 ? y : 65535;
+  const int64_t y = row_blocks > 0 ? row_blocks : grid_row_blocks(xtiles, utiles, kTilesPerPrologue);
   const Grid G{zu, zi, fu, fi, g, out_w, out_b, users, user0, rows, num_users, num_items, out, ldo, utiles, embed};
-  constexpr size_t lds_bytes = sizeof(float) * (size_t)kLdsFloats;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pnn_grid_scores_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-    return CTR_ELAUNCH;
   // item tiles along x (neighbouring workgroups share their user tile's rows in L2), row blocks along y
-  hipLaunchKernelGGL(pnn_grid_scores_kernel, dim3((unsigned)xtiles, (unsigned)y), dim3(kThreads), lds_bytes,
-                     (hipStream_t)stream, T, G);
-  return ctr_launch_status();
+  return grid_launch(pnn_grid_scores_kernel, dim3((unsigned)xtiles, grid_clamp_y(y, utiles)), kThreads,
+                     sizeof(float) * (size_t)kLdsFloats, stream, T, G);
 }

@@ -9,7 +9,8 @@ import torch
 from torch import nn
 
 from .. import _lib, ops, sparse, topn
-from ..ops import Layer
+from .._lib import FIELD_BAG, FIELD_ID_F32
+from ..ops import FieldSpec, Layer
 from ._grid import UserGridScorer
 
 
@@ -166,6 +167,20 @@ class _ModelFunction(torch.autograd.Function):
         return (None,) * (4 + ctx.n_inputs) + tuple(grads)
 
 
+def six_field_specs(tables, dim):
+    """[user, item, age, gender, occupation, movie] vectors at columns f*dim
+    (reference model/deepfm.py:45-54, model/pnn.py:113-121)"""
+    user, item, age, gender, occ, movie = tables
+    return [
+        FieldSpec(FIELD_ID_F32, dim, 0 * dim, table=user, src_col=0),
+        FieldSpec(FIELD_ID_F32, dim, 1 * dim, table=item, src_col=1),
+        FieldSpec(FIELD_BAG, dim, 2 * dim, table=age, src_col=2, bag_size=1),
+        FieldSpec(FIELD_BAG, dim, 3 * dim, table=gender, src_col=3, bag_size=2),
+        FieldSpec(FIELD_BAG, dim, 4 * dim, table=occ, src_col=5, bag_size=21),
+        FieldSpec(FIELD_BAG, dim, 5 * dim, table=movie, src_col=26, bag_size=19),
+    ]
+
+
 class FeatureModel(CtrModule):
     """models fed by the (B,45) float feature matrix of data/reader.py:98-112"""
 
@@ -271,6 +286,77 @@ class CatalogueScorer(UserGridScorer):
         topn.forward_grid(out, FORWARD_GRID_PAIRS, lambda r, i: self.model.forward(
             self.assembler.feature(users[r] if users is not None else r + start, i)))
         return out
+
+
+_USER_FIELDS, _ITEM_FIELDS = (0, 2, 3, 4), (1, 5)   # of six_field_specs: user, age, gender, occupation / item, movie
+
+
+class SixFieldGridScorer(CatalogueScorer):
+    """A six-field model on the user x item grid: every field vector belongs to the user or to the item, so what the
+    model computes ahead of its first nonlinearity splits into rows of a user-side and an item-side table, and a kernel
+    scores the pairs from those.  The rows of BOTH sides are made for the whole table at every public call (the weights
+    are read then), in passes of ``side_chunk`` rows at fixed positions: a table row's bits then do not depend on which
+    users were asked for.  A model supplies ``_side_buffers``, ``_side_rows`` and ``_grid_scores``; ``_side_prepare``
+    and ``_operands`` are for what a model makes beside the two sides' buffers."""
+
+    path = "grid"
+    row_blocks = 0               # 0: the launch's own geometry (tests set 1, 2 to reach the tile loop at small shapes)
+    side_chunk = 1 << 16         # table rows per pass of _side: bounds its (rows, 6E) buffer and the hook's own
+
+    def _side_prepare(self, p) -> None:
+        """runs once a side, in front of its allocations and its passes: what ``_side_rows`` reads and does not make"""
+
+    def _side_buffers(self, p, rows, dim, user_side: bool, dev) -> tuple:
+        """what ``_side`` returns for one side's table of ``rows`` rows, allocated"""
+        raise NotImplementedError
+
+    def _side_rows(self, p, x, emb, vec, lo, hi, user_side: bool, buffers) -> None:
+        """fill rows [lo, hi) of ``buffers`` from the feature rows ``x`` and their field vectors ``emb`` (``vec``: the
+        same as (rows, 6, E)); ``_zero_other`` in front of whatever reads ``emb`` as one side's"""
+        raise NotImplementedError
+
+    def _operands(self, p) -> tuple:
+        return ()                # what ``_shared`` returns behind the two sides; made before them
+
+    def _grid_scores(self, shared, users, user0, rows) -> torch.Tensor:
+        """the one kernel call, for ``rows`` >= 1"""
+        raise NotImplementedError
+
+    @staticmethod
+    def _fields(user_side: bool):
+        return _USER_FIELDS if user_side else _ITEM_FIELDS
+
+    def _zero_other(self, vec, user_side: bool) -> None:
+        vec[:, self._fields(not user_side), :] = 0.0             # the other side's columns add exact zeros
+
+    def _side(self, p, user_side: bool):
+        asm = self.assembler
+        dev, dim = self._device(), p.tables[0].shape[1]
+        rows = self.num_users if user_side else self.num_items
+        self._side_prepare(p)
+        buffers = self._side_buffers(p, rows, dim, user_side, dev)
+        flag = self.model._err_flag(dev)
+        for lo in range(0, rows, self.side_chunk):
+            hi = min(rows, lo + self.side_chunk)
+            ids, zero = torch.arange(lo, hi, device=dev), torch.zeros(hi - lo, dtype=torch.int64, device=dev)
+            x = asm.feature(ids, zero) if user_side else asm.feature(zero, ids)
+            # the field vectors exactly as the forward gathers them
+            emb = torch.empty((hi - lo, 6 * dim), dtype=torch.float32, device=dev)
+            ops.embed_fwd(six_field_specs([t.detach() for t in p.tables], dim), x, hi - lo, emb, flag)
+            self._side_rows(p, x, emb, emb.view(hi - lo, 6, dim), lo, hi, user_side, buffers)
+        return buffers
+
+    def _shared(self):
+        p = self.model._params()
+        self.model._need_device(p.tables[0], self.assembler.user_features)
+        rest = self._operands(p)
+        return (p, self._side(p, True), self._side(p, False)) + rest
+
+    def _scores(self, users, start, stop, shared=None):
+        rows = users.numel() if users is not None else stop - start
+        if rows == 0:
+            return torch.empty((0, self.num_items), dtype=torch.float32, device=self._device())
+        return self._grid_scores(shared, users, start, rows)
 
 
 def _segment_topk(scores: torch.Tensor, counts: torch.Tensor, k: int) -> np.ndarray:

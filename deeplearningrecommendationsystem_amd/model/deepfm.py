@@ -6,23 +6,8 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import ops
-from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec, Layer
-from .._lib import FIELD_BAG, FIELD_ID_F32
-from ._base import CatalogueScorer, FeatureModel, Params
-
-
-def six_field_specs(tables, dim):
-    """[user, item, age, gender, occupation, movie] vectors at columns f*dim
-    (reference model/deepfm.py:45-54, model/pnn.py:113-121)"""
-    user, item, age, gender, occ, movie = tables
-    return [
-        FieldSpec(FIELD_ID_F32, dim, 0 * dim, table=user, src_col=0),
-        FieldSpec(FIELD_ID_F32, dim, 1 * dim, table=item, src_col=1),
-        FieldSpec(FIELD_BAG, dim, 2 * dim, table=age, src_col=2, bag_size=1),
-        FieldSpec(FIELD_BAG, dim, 3 * dim, table=gender, src_col=3, bag_size=2),
-        FieldSpec(FIELD_BAG, dim, 4 * dim, table=occ, src_col=5, bag_size=21),
-        FieldSpec(FIELD_BAG, dim, 5 * dim, table=movie, src_col=26, bag_size=19),
-    ]
+from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
+from ._base import CatalogueScorer, FeatureModel, Params, SixFieldGridScorer, six_field_specs
 
 
 def field_vocabs(num_fields, vocab):
@@ -179,9 +164,8 @@ class DeepFM(FeatureModel):
         ``ctr_deepfm_grid_scores`` over table rows made once per call, not from the per-sample forward"""
         self._table_sizes()                                   # (refuses the num_fields= model)
         hidden = [self.linear.out_features] + [lin.out_features for lin in self.dnn_network]
-        if grid_path(hidden, self.user_embedding.embedding_dim) == "grid":
-            return _GridScorer(self, assembler)
-        return CatalogueScorer(self, assembler)
+        grid = grid_path(hidden, self.user_embedding.embedding_dim) == "grid"
+        return (_GridScorer if grid else CatalogueScorer)(self, assembler)
 
 
 def grid_path(hidden_units, embedding_dim) -> str:
@@ -191,64 +175,36 @@ def grid_path(hidden_units, embedding_dim) -> str:
     return "grid" if ops.deepfm_grid_supported(hidden_units, embedding_dim) else "forward"
 
 
-_SIDE_CHUNK = 1 << 16            # table rows per pass of _GridScorer._side: bounds its (rows, 6E) and (rows, H0) buffers
-_USER_FIELDS, _ITEM_FIELDS = (0, 2, 3, 4), (1, 5)   # of six_field_specs: user, age, gender, occupation / item, movie
-
-
-class _GridScorer(CatalogueScorer):
+class _GridScorer(SixFieldGridScorer):
     """DeepFM on the user x item grid.  Every column of the feature row belongs to the user or to the item and
     ``linear`` has no activation, so with SU / SI the sums of a side's field vectors
         fm = a[u] + b[i] + <SU[u], SI[i]>,   h1 = relu(ZU[u] + ZI[i]),   ZU / ZI = W1 (W0 . a side's columns of emb)
-    and the rest of the model runs per pair inside the kernel.  The rows of BOTH sides are made for the whole table
-    at every public call (the weights are read then), in passes of ``_SIDE_CHUNK`` rows at fixed positions: a table
-    row's bits then do not depend on which users were asked for."""
+    and the rest of the model runs per pair inside the kernel."""
 
-    path = "grid"
-    row_blocks = 0               # 0: the launch's own geometry (tests set 1, 2 to reach the tile loop at small shapes)
-
-    def _side(self, p, user_side: bool):
+    def _side_buffers(self, p, rows, dim, user_side, dev):
         """(Z (R, 256), S (R, E), first-order + wide + FM-square term (R,)) of every row of one side's table"""
-        model, asm = self.model, self.assembler
-        dev, dim = self._device(), p.tables[0].shape[1]
-        rows = self.num_users if user_side else self.num_items
-        mine, other = (_USER_FIELDS, _ITEM_FIELDS) if user_side else (_ITEM_FIELDS, _USER_FIELDS)
+        return (torch.empty((rows, p.deep[1].weight.shape[0]), dtype=torch.float32, device=dev),
+                torch.empty((rows, dim), dtype=torch.float32, device=dev),
+                torch.empty(rows, dtype=torch.float32, device=dev))
+
+    def _side_rows(self, p, x, emb, vec, lo, hi, user_side, buffers):
+        z, s, c = buffers
         w0, w1 = p.deep[0], p.deep[1]
         wide = p.wide_w.detach().reshape(-1)
-        z = torch.empty((rows, w1.weight.shape[0]), dtype=torch.float32, device=dev)
-        s = torch.empty((rows, dim), dtype=torch.float32, device=dev)
-        c = torch.empty(rows, dtype=torch.float32, device=dev)
-        flag = model._err_flag(dev)
-        for lo in range(0, rows, _SIDE_CHUNK):
-            hi = min(rows, lo + _SIDE_CHUNK)
-            ids, zero = torch.arange(lo, hi, device=dev), torch.zeros(hi - lo, dtype=torch.int64, device=dev)
-            x = asm.feature(ids, zero) if user_side else asm.feature(zero, ids)
-            # the field vectors exactly as the forward gathers them
-            emb = torch.empty((hi - lo, 6 * dim), dtype=torch.float32, device=dev)
-            ops.embed_fwd(six_field_specs([t.detach() for t in p.tables], dim), x, hi - lo, emb, flag)
-            vec = emb.view(hi - lo, 6, dim)
-            f = vec[:, mine, :]
-            total = f.sum(1)
-            s[lo:hi] = total
-            if user_side:
-                first = p.user1.detach()[lo:hi, 0] + (x[:, 2:26] * wide[:24]).sum(1) + p.wide_b.detach()
-            else:
-                first = p.item1.detach()[lo:hi, 0] + (x[:, 26:45] * wide[24:]).sum(1)
-            c[lo:hi] = first + 0.5 * ((total * total).sum(1) - (f * f).sum((1, 2)))
-            vec[:, other, :] = 0.0                           # the other side's columns add exact zeros
-            t = ops.linear_fwd(emb, w0.weight.detach(), None if user_side else w0.bias.detach())
-            ops.linear_fwd(t, w1.weight.detach(), None if user_side else w1.bias.detach(), out=z[lo:hi])
-        return z, s, c
+        f = vec[:, self._fields(user_side), :]
+        total = f.sum(1)
+        s[lo:hi] = total
+        if user_side:
+            first = p.user1.detach()[lo:hi, 0] + (x[:, 2:26] * wide[:24]).sum(1) + p.wide_b.detach()
+        else:
+            first = p.item1.detach()[lo:hi, 0] + (x[:, 26:45] * wide[24:]).sum(1)
+        c[lo:hi] = first + 0.5 * ((total * total).sum(1) - (f * f).sum((1, 2)))
+        self._zero_other(vec, user_side)
+        t = ops.linear_fwd(emb, w0.weight.detach(), None if user_side else w0.bias.detach())
+        ops.linear_fwd(t, w1.weight.detach(), None if user_side else w1.bias.detach(), out=z[lo:hi])
 
-    def _shared(self):
-        p = self.model._params()
-        self.model._need_device(p.tables[0], self.assembler.user_features)
-        return p, self._side(p, True), self._side(p, False)
-
-    def _scores(self, users, start, stop, shared=None):
+    def _grid_scores(self, shared, users, user0, rows):
         p, (zu, su, a), (zi, si, b) = shared
         w2, w3 = p.deep[2], p.deep[3]
-        rows = users.numel() if users is not None else stop - start
-        if rows == 0:
-            return torch.empty((0, self.num_items), dtype=torch.float32, device=self._device())
         return ops.deepfm_grid_scores(zu, zi, su, si, a, b, w2.weight.detach(), w2.bias, w3.weight, w3.bias, p.out_w,
-                                      p.out_b, users=users, user0=start, rows=rows, row_blocks=self.row_blocks)
+                                      p.out_b, users=users, user0=user0, rows=rows, row_blocks=self.row_blocks)

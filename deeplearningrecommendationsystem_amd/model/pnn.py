@@ -7,8 +7,8 @@ from torch.nn.init import xavier_normal_
 
 from .. import ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
-from ._base import CatalogueScorer, FeatureModel, Params
-from .deepfm import _ITEM_FIELDS, _USER_FIELDS, FieldsInput, field_vocabs, six_field_specs
+from ._base import _USER_FIELDS, CatalogueScorer, FeatureModel, Params, SixFieldGridScorer, six_field_specs
+from .deepfm import FieldsInput, field_vocabs
 from .._lib import FIELD_ID_I64
 
 
@@ -167,9 +167,8 @@ class PNN(FeatureModel):
         ``ctr_pnn_grid_scores`` over table rows made once per call, not from the per-sample forward"""
         self._table_sizes()                                   # (refuses the num_fields= model)
         hidden = [self.product.linear1.out_features] + [lin.out_features for lin in self.dnn.dnn_network]
-        if grid_path(hidden, self.user_embed.embedding_dim, self.product.model) == "grid":
-            return _GridScorer(self, assembler)
-        return CatalogueScorer(self, assembler)
+        grid = grid_path(hidden, self.user_embed.embedding_dim, self.product.model) == "grid"
+        return (_GridScorer if grid else CatalogueScorer)(self, assembler)
 
 
 def grid_path(hidden_units, embed_dim, model="in") -> str:
@@ -177,9 +176,6 @@ def grid_path(hidden_units, embed_dim, model="in") -> str:
     rows, then ``ctr_pnn_grid_scores`` -- where the library has that kernel, else "forward": the per-sample forward
     over feature rows assembled chunk by chunk.  A function of shapes alone."""
     return "grid" if ops.pnn_grid_supported(hidden_units, embed_dim, model) else "forward"
-
-
-_SIDE_CHUNK = 1 << 15            # table rows per pass of _GridScorer._side: bounds its (rows, 6E) and (rows, 256) buffers
 
 
 def _pair_columns():
@@ -196,59 +192,41 @@ def _pair_columns():
 _USER_PAIRS, _ITEM_PAIRS, _CROSS_PAIRS = _pair_columns()     # [1, 2, 3, 9, 10, 12], [8], [0, 4, 5, 6, 7, 11, 13, 14]
 
 
-class _GridScorer(CatalogueScorer):
+class _GridScorer(SixFieldGridScorer):
     """PNN (inner mode) on the user x item grid.  Every field vector belongs to the user or to the item and the
     product layer's output h0 has no activation in front of the first DNN layer D1, so
         z1 = D1 h0 + c1 = ZU[u] + ZI[i] + G d(u, i),   G = D1 W2[:, cross columns],   d: the eight cross products
     with ZU / ZI = D1 applied to a side's part of h0 (its columns of ``linear1``, its own products through ``linear2``;
     every bias on the item side), and the rest of the model runs per pair inside the kernel, which forms ``d`` from
-    the sides' field vectors FU (U, 4E) / FI (I, 2E).  The rows of BOTH sides are made for the whole table at every
-    public call (the weights are read then), in passes of ``_SIDE_CHUNK`` rows at fixed positions: a table row's bits
-    then do not depend on which users were asked for."""
+    the sides' field vectors FU (U, 4E) / FI (I, 2E)."""
 
-    path = "grid"
-    row_blocks = 0               # 0: the launch's own geometry (tests set 1, 2 to reach the tile loop at small shapes)
+    side_chunk = 1 << 15         # the pass also holds (rows, 16) products and (rows, 256) twice
 
-    def _side(self, p, user_side: bool):
+    def _side_prepare(self, p):
+        self.model._aligned_weight(p.w2)                     # ``linear2``'s padded copy, refreshed for ``_side_rows``
+
+    def _side_buffers(self, p, rows, dim, user_side, dev):
         """(Z (R, 128), F (R, 4E) or (R, 2E)) of every row of one side's table"""
-        model, asm = self.model, self.assembler
-        dev, dim = self._device(), p.tables[0].shape[1]
-        rows = self.num_users if user_side else self.num_items
-        mine, other = (_USER_FIELDS, _ITEM_FIELDS) if user_side else (_ITEM_FIELDS, _USER_FIELDS)
-        d1 = p.dnn[0]
-        w2 = model._aligned_weight(p.w2)
-        z = torch.empty((rows, d1.weight.shape[0]), dtype=torch.float32, device=dev)
-        f = torch.empty((rows, len(mine) * dim), dtype=torch.float32, device=dev)
-        flag = model._err_flag(dev)
-        for lo in range(0, rows, _SIDE_CHUNK):
-            hi = min(rows, lo + _SIDE_CHUNK)
-            ids, zero = torch.arange(lo, hi, device=dev), torch.zeros(hi - lo, dtype=torch.int64, device=dev)
-            x = asm.feature(ids, zero) if user_side else asm.feature(zero, ids)
-            # the field vectors exactly as the forward gathers them
-            emb = torch.empty((hi - lo, 6 * dim), dtype=torch.float32, device=dev)
-            ops.embed_fwd(six_field_specs([t.detach() for t in p.tables], dim), x, hi - lo, emb, flag)
-            vec = emb.view(hi - lo, 6, dim)
-            f[lo:hi] = vec[:, mine, :].reshape(hi - lo, -1)
-            vec[:, other, :] = 0.0                           # the other side's columns and products are exact zeros
-            prod = ops.allpairs_fwd(emb, 6, dim, out=model._padded_rows(hi - lo, 15, dev))
-            lz = ops.linear_fwd(emb, p.w1.detach(), None if user_side else p.b1.detach())
-            h0 = ops.linear_fwd(prod, w2, None if user_side else p.b2.detach(), residual=lz)
-            ops.linear_fwd(h0, d1.weight.detach(), None if user_side else d1.bias.detach(), out=z[lo:hi])
-        return z, f
+        return (torch.empty((rows, p.dnn[0].weight.shape[0]), dtype=torch.float32, device=dev),
+                torch.empty((rows, len(self._fields(user_side)) * dim), dtype=torch.float32, device=dev))
 
-    def _shared(self):
-        p = self.model._params()
-        self.model._need_device(p.tables[0], self.assembler.user_features)
+    def _side_rows(self, p, x, emb, vec, lo, hi, user_side, buffers):
+        z, f = buffers
+        d1, w2 = p.dnn[0], self.model._aligned_weight(p.w2, refresh=False)
+        f[lo:hi] = vec[:, self._fields(user_side), :].reshape(hi - lo, -1)
+        self._zero_other(vec, user_side)                     # (and with the columns the other side's products)
+        prod = ops.allpairs_fwd(emb, 6, vec.shape[2], out=self.model._padded_rows(hi - lo, 15, emb.device))
+        lz = ops.linear_fwd(emb, p.w1.detach(), None if user_side else p.b1.detach())
+        h0 = ops.linear_fwd(prod, w2, None if user_side else p.b2.detach(), residual=lz)
+        ops.linear_fwd(h0, d1.weight.detach(), None if user_side else d1.bias.detach(), out=z[lo:hi])
+
+    def _operands(self, p):
         d1 = p.dnn[0].weight.detach()
         cross = p.w2.detach()[:, _CROSS_PAIRS].t().contiguous()              # (8, 256): a cross column of W2 per row
-        g = ops.linear_fwd(cross, d1, None).t().contiguous()                 # (128, 8) = D1 W2[:, cross]
-        return p, self._side(p, True), self._side(p, False), g
+        return (ops.linear_fwd(cross, d1, None).t().contiguous(),)           # (128, 8) = D1 W2[:, cross]
 
-    def _scores(self, users, start, stop, shared=None):
+    def _grid_scores(self, shared, users, user0, rows):
         p, (zu, fu), (zi, fi), g = shared
         d2, d3 = p.dnn[1], p.dnn[2]
-        rows = users.numel() if users is not None else stop - start
-        if rows == 0:
-            return torch.empty((0, self.num_items), dtype=torch.float32, device=self._device())
         return ops.pnn_grid_scores(zu, zi, fu, fi, g, d2.weight, d2.bias, d3.weight, d3.bias, p.out.weight, p.out.bias,
-                                   users=users, user0=start, rows=rows, row_blocks=self.row_blocks)
+                                   users=users, user0=user0, rows=rows, row_blocks=self.row_blocks)

@@ -849,6 +849,58 @@ class NcfProj:
 
 
 # ---------------------------------------------------------------------------
+# the grid scorers' wrappers (csrc/*_grid.hip): what they check alike, under the calling wrapper's ``name``
+# ---------------------------------------------------------------------------
+def _grid_rows(name, users, user0, rows, nu, ni, out, device):
+    """(user0, rows, out) of a user-grid call: the rows are ``users`` (1-D int64), else the users ``user0 .. user0 +
+    rows`` (``rows`` None: up to the table's end); ``out`` is (rows, ni), checked or fresh"""
+    if users is not None:
+        _i64(users)
+        if users.dim() != 1:
+            raise ValueError(f"{name}: users must be 1-D")
+        rows, user0 = users.numel(), 0
+    elif rows is None:
+        rows = nu - user0
+    if out is None:
+        out = torch.empty((rows, ni), dtype=torch.float32, device=device)
+    out = _mat(out, "out")
+    if out.shape != (rows, ni):
+        raise ValueError(f"{name}: out must be ({rows}, {ni})")
+    return user0, rows, out
+
+
+def _history_rows(name, hist):
+    """(R, L) of the history matrix of a history-grid call"""
+    _i64(hist)
+    if hist.dim() != 2 or hist.shape[1] < 1:
+        raise ValueError(f"{name}: hist must be (R, L) with L >= 1, got {tuple(hist.shape)}")
+    return hist.shape
+
+
+def _history_out(name, out, pairs, dim, device):
+    """the (pairs, >= dim) left half of the fc operand: ``out`` checked, or a fresh one"""
+    if out is None:
+        out = torch.empty((pairs, dim), dtype=torch.float32, device=device)
+    out = _mat(out, "out")
+    if out.shape[0] != pairs or out.shape[1] < dim:
+        raise ValueError(f"{name}: out must be ({pairs}, >= {dim})")
+    return out
+
+
+def _f32_vectors(name, what, *tensors):
+    """``tensors`` flattened and contiguous on the device, float32 or ``name: what must be float32``"""
+    vecs = [t.detach().reshape(-1).contiguous() for t in tensors]
+    _lib.require_device(*vecs)
+    if any(t.dtype != torch.float32 for t in vecs):
+        raise ValueError(f"{name}: {what} must be float32")
+    return vecs
+
+
+def _attention_shapes_match(embed_size, attention_dims, want_embed, want_dims) -> bool:
+    return int(embed_size) == want_embed and tuple(tuple(int(v) for v in d) for d in attention_dims) == want_dims
+
+
+# ---------------------------------------------------------------------------
 # NeuralCF over the user x item grid (csrc/ncf_grid.hip)
 # ---------------------------------------------------------------------------
 def ncf_grid_supported(tables, hidden, proj) -> bool:
@@ -876,18 +928,7 @@ def ncf_grid_scores(p_u: torch.Tensor, p_i: torch.Tensor, gmf_u: torch.Tensor, g
     nu, ni = gmf_u.shape[0], gmf_i.shape[0]
     if p_u.shape[0] != nu or p_i.shape[0] != ni:
         raise ValueError("ncf_grid_scores: the projected tables and the GMF tables differ in rows")
-    if users is not None:
-        _i64(users)
-        if users.dim() != 1:
-            raise ValueError("ncf_grid_scores: users must be 1-D")
-        rows, user0 = users.numel(), 0
-    elif rows is None:
-        rows = nu - user0
-    if out is None:
-        out = torch.empty((rows, ni), dtype=torch.float32, device=gmf_u.device)
-    out = _mat(out, "out")
-    if out.shape != (rows, ni):
-        raise ValueError(f"ncf_grid_scores: out must be ({rows}, {ni})")
+    user0, rows, out = _grid_rows("ncf_grid_scores", users, user0, rows, nu, ni, out, gmf_u.device)
     arr = (_lib.MlpLayer * len(layers))()
     for k, layer in enumerate(layers):
         w = layer.weight
@@ -920,7 +961,7 @@ DIN_GRID_ATTENTION = ((128, 3 * DIN_GRID_EMBED), (64, 128), (1, 64))
 def din_grid_supported(embed_size: int, attention_dims) -> bool:
     """whether ``ctr_din_grid_pool`` takes a DIN of this embedding width whose attention ``Linear`` weights have the
     shapes ``attention_dims`` ((out, in) per layer).  A function of shapes alone: CPU or meta tensors will do."""
-    return int(embed_size) == DIN_GRID_EMBED and tuple(tuple(int(v) for v in d) for d in attention_dims) == DIN_GRID_ATTENTION
+    return _attention_shapes_match(embed_size, attention_dims, DIN_GRID_EMBED, DIN_GRID_ATTENTION)
 
 
 def din_grid_pool(table: torch.Tensor, at: torch.Tensor, ah: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
@@ -934,10 +975,7 @@ def din_grid_pool(table: torch.Tensor, at: torch.Tensor, ah: torch.Tensor, w2: t
     (``din_grid_supported`` says beforehand)."""
     table, at, ah, w2 = (_mat(t, w) for t, w in ((table, "table"), (at, "at"), (ah, "ah"), (w2, "w2")))
     _lib.require_device(b2, w3, err_flag)
-    _i64(hist)
-    if hist.dim() != 2 or hist.shape[1] < 1:
-        raise ValueError(f"din_grid_pool: hist must be (R, L) with L >= 1, got {tuple(hist.shape)}")
-    rows, length = hist.shape
+    rows, length = _history_rows("din_grid_pool", hist)
     ni, dim = table.shape
     if not (table.is_contiguous() and at.is_contiguous() and ah.is_contiguous() and w2.is_contiguous()
             and b2.is_contiguous() and w3.is_contiguous()):
@@ -948,11 +986,7 @@ def din_grid_pool(table: torch.Tensor, at: torch.Tensor, ah: torch.Tensor, w2: t
                          f"{rows} x {length} positions")
     if b2.numel() != n2 or w3.numel() != n2:
         raise ValueError("din_grid_pool: b2 and w3 must have one element per unit of w2")
-    if out is None:
-        out = torch.empty((rows * ni, dim), dtype=torch.float32, device=table.device)
-    out = _mat(out, "out")
-    if out.shape[0] != rows * ni or out.shape[1] < dim:
-        raise ValueError(f"din_grid_pool: out must be ({rows * ni}, >= {dim})")
+    out = _history_out("din_grid_pool", out, rows * ni, dim, table.device)
     if rows * ni == 0:
         return out
     # algorithmic: the table-side rows of the call read once (the row tiles re-read them from cache), the pooled rows
@@ -979,8 +1013,7 @@ DIEN_GRID_KEEP = _lib.CTR_DIEN_GRID_KEEP     # history positions whose score wai
 def dien_grid_supported(embed_size: int, attention_dims) -> bool:
     """whether ``ctr_dien_grid_hidden`` takes a DIEN of this embedding (= GRU) width whose attention ``Linear`` weights
     have the shapes ``attention_dims`` ((out, in) per layer).  A function of shapes alone: CPU or meta tensors will do."""
-    return (int(embed_size) == DIEN_GRID_EMBED
-            and tuple(tuple(int(v) for v in d) for d in attention_dims) == DIEN_GRID_ATTENTION)
+    return _attention_shapes_match(embed_size, attention_dims, DIEN_GRID_EMBED, DIEN_GRID_ATTENTION)
 
 
 def dien_grid_hidden(at: torch.Tensor, hp: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
@@ -997,10 +1030,7 @@ def dien_grid_hidden(at: torch.Tensor, hp: torch.Tensor, w2: torch.Tensor, b2: t
     _lib.require_device(b2, w3, b_ih, b_hh, err_flag)
     if any(t.dtype != torch.float32 for t in (b2, w3, b_ih, b_hh)):
         raise ValueError("dien_grid_hidden: b2, w3, b_ih and b_hh must be float32")
-    _i64(hist)
-    if hist.dim() != 2 or hist.shape[1] < 1:
-        raise ValueError(f"dien_grid_hidden: hist must be (R, L) with L >= 1, got {tuple(hist.shape)}")
-    rows, length = hist.shape
+    rows, length = _history_rows("dien_grid_hidden", hist)
     if not all(t.is_contiguous() for t in (at, hp, w2, b2, w3, b_ih, w_hh, b_hh)):
         raise ValueError("dien_grid_hidden: at, hp and the weights must be contiguous")
     ni, (n2, n1) = at.shape[0], w2.shape
@@ -1011,11 +1041,7 @@ def dien_grid_hidden(at: torch.Tensor, hp: torch.Tensor, w2: torch.Tensor, b2: t
     if b2.numel() != n2 or w3.numel() != n2 or b_ih.numel() != gates or b_hh.numel() != gates:
         raise ValueError("dien_grid_hidden: b2 and w3 must have one element per unit of w2, b_ih and b_hh one per row "
                          "of w_hh")
-    if out is None:
-        out = torch.empty((rows * ni, dim), dtype=torch.float32, device=at.device)
-    out = _mat(out, "out")
-    if out.shape[0] != rows * ni or out.shape[1] < dim:
-        raise ValueError(f"dien_grid_hidden: out must be ({rows * ni}, >= {dim})")
+    out = _history_out("dien_grid_hidden", out, rows * ni, dim, at.device)
     if rows * ni == 0:
         return out
     # algorithmic: the table-side rows of the call read once (the row tiles re-read them from cache), the states
@@ -1056,11 +1082,8 @@ def deepfm_grid_scores(zu: torch.Tensor, zi: torch.Tensor, su: torch.Tensor, si:
     user tiles, 0 for the launch's own choice; the scores do not depend on it.  A shape the kernel is not built for
     raises: there is no other path behind this call (``deepfm_grid_supported`` says beforehand)."""
     zu, zi, su, si, w2 = (_mat(t, w).contiguous() for t, w in ((zu, "zu"), (zi, "zi"), (su, "su"), (si, "si"), (w2, "w2")))
-    vecs = [t.detach().reshape(-1).contiguous() for t in (a, b, b2, w3, b3, out_w, out_b)]
-    _lib.require_device(*vecs)
-    if any(t.dtype != torch.float32 for t in vecs):
-        raise ValueError("deepfm_grid_scores: a, b and the weights must be float32")
-    a, b, b2, w3, b3, out_w, out_b = vecs
+    a, b, b2, w3, b3, out_w, out_b = _f32_vectors("deepfm_grid_scores", "a, b and the weights", a, b, b2, w3, b3, out_w,
+                                                  out_b)
     nu, ni, dim = zu.shape[0], zi.shape[0], su.shape[1]
     n2, n1 = w2.shape
     if su.shape[0] != nu or a.numel() != nu or si.shape != (ni, dim) or b.numel() != ni:
@@ -1069,18 +1092,7 @@ def deepfm_grid_scores(zu: torch.Tensor, zi: torch.Tensor, su: torch.Tensor, si:
         raise ValueError("deepfm_grid_scores: zu / zi must be as wide as a row of w2, b2 and w3 one element per unit of w2")
     if b3.numel() != 1 or out_w.numel() != 2 or out_b.numel() != 1:
         raise ValueError("deepfm_grid_scores: b3 and out_b hold one element, out_w two")
-    if users is not None:
-        _i64(users)
-        if users.dim() != 1:
-            raise ValueError("deepfm_grid_scores: users must be 1-D")
-        rows, user0 = users.numel(), 0
-    elif rows is None:
-        rows = nu - user0
-    if out is None:
-        out = torch.empty((rows, ni), dtype=torch.float32, device=zu.device)
-    out = _mat(out, "out")
-    if out.shape != (rows, ni):
-        raise ValueError(f"deepfm_grid_scores: out must be ({rows}, {ni})")
+    user0, rows, out = _grid_rows("deepfm_grid_scores", users, user0, rows, nu, ni, out, zu.device)
     # algorithmic: every table row of the call read once (the user tiles re-read item rows from cache), the scores
     # written; per pair the 256 -> 128 layer, the relu'd sum of the rows, the w3 dot and the FM dot
     rc = _timed("deepfm_grid_scores",
@@ -1125,11 +1137,7 @@ def pnn_grid_scores(zu: torch.Tensor, zi: torch.Tensor, fu: torch.Tensor, fi: to
     behind this call (``pnn_grid_supported`` says beforehand)."""
     zu, zi, fu, fi, g, d2_w, d3_w = (_mat(t.detach(), w).contiguous() for t, w in (
         (zu, "zu"), (zi, "zi"), (fu, "fu"), (fi, "fi"), (g, "g"), (d2_w, "d2_w"), (d3_w, "d3_w")))
-    vecs = [t.detach().reshape(-1).contiguous() for t in (d2_b, d3_b, out_w, out_b)]
-    _lib.require_device(*vecs)
-    if any(t.dtype != torch.float32 for t in vecs):
-        raise ValueError("pnn_grid_scores: the biases and out_w must be float32")
-    d2_b, d3_b, out_w, out_b = vecs
+    d2_b, d3_b, out_w, out_b = _f32_vectors("pnn_grid_scores", "the biases and out_w", d2_b, d3_b, out_w, out_b)
     nu, ni = zu.shape[0], zi.shape[0]
     (n2, n1), n3 = d2_w.shape, d3_w.shape[0]
     if fu.shape[0] != nu or fi.shape[0] != ni or fu.shape[1] % 4 or fi.shape[1] * 2 != fu.shape[1]:
@@ -1140,18 +1148,7 @@ def pnn_grid_scores(zu: torch.Tensor, zi: torch.Tensor, fu: torch.Tensor, fi: to
     if d3_w.shape[1] != n2 or d2_b.numel() != n2 or d3_b.numel() != n3 or out_w.numel() != n3 or out_b.numel() != 1:
         raise ValueError("pnn_grid_scores: d3_w must take d2_w's units, a bias holds one element per unit, out_w one per "
                          "unit of d3_w and out_b one")
-    if users is not None:
-        _i64(users)
-        if users.dim() != 1:
-            raise ValueError("pnn_grid_scores: users must be 1-D")
-        rows, user0 = users.numel(), 0
-    elif rows is None:
-        rows = nu - user0
-    if out is None:
-        out = torch.empty((rows, ni), dtype=torch.float32, device=zu.device)
-    out = _mat(out, "out")
-    if out.shape != (rows, ni):
-        raise ValueError(f"pnn_grid_scores: out must be ({rows}, {ni})")
+    user0, rows, out = _grid_rows("pnn_grid_scores", users, user0, rows, nu, ni, out, zu.device)
     # algorithmic: every table row of the call read once (the user tiles re-read item rows from cache), the scores
     # written; per pair the eight dots, the 128 x 8 product on the sum of the rows, the two layers and the output dot
     rc = _timed("pnn_grid_scores",

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """What every grid scorer launches and returns, as a listing two trees can be compared by: run from the root of the tree
 to be measured (a parent checkout beside the change, both loading one library through ``CTRHIP_LIB``), then ``diff``
-the two outputs (``profiles/grid_scorer_refactor.txt``).
+the two outputs (``profiles/grid_scorer_refactor.txt``, ``profiles/grid_frame_refactor.txt``).
 
-At the shapes of tests/test_gpu_ncf_grid.py, test_gpu_din_grid.py, test_gpu_dien_grid.py and test_gpu_deepfm_grid.py,
-with ``topn.SCORE_CHUNK_FLOATS`` lowered to five rows a chunk and an ``ops.KernelProfiler`` installed, public names only:
+At the shapes of tests/test_gpu_ncf_grid.py, test_gpu_din_grid.py, test_gpu_dien_grid.py, test_gpu_deepfm_grid.py and
+test_gpu_pnn_grid.py, with ``topn.SCORE_CHUNK_FLOATS`` lowered to five rows a chunk and an ``ops.KernelProfiler``
+installed, public names only:
 
   NeuralCF  33 x 130 at 64 / [128, 64, 32, 16, 8] ("grid") and 50 x 60 at 12 / [24, 12, 6] ("forward"):
             ``score_rows``, ``score_grid`` with a repeated list, ``recommend``
@@ -12,6 +13,7 @@ with ``topn.SCORE_CHUNK_FLOATS`` lowered to five rows a chunk and an ``ops.Kerne
             E = 16 and E = 8: ``score_histories``, ``history_scorer``, ``recommend`` with ``users=``
   DeepFM    33 x 258 at E = 16 / [512, 256, 128, 1] ("grid") and 21 x 30 at E = 8 / [32, 16, 1] ("forward"):
             the three ``catalogue_scorer`` calls
+  PNN       33 x 258 at E = 16 / (256, 128, 64, 32) ("grid") and 21 x 30 at E = 8 / [32, 16] ("forward"): the same
 
 ``recommend`` runs with n = 6 and with n = num_items + 3 plus ``exclude``.  Every entry prints the shape and the first 16
 hex digits of the SHA-256 of the result, then the recorded (label, bytes, flops) in call order."""
@@ -94,9 +96,13 @@ def main():
             torch.manual_seed(rows)
             model = spread(cls(ni, embed), ni)
             history_grid(f"{cls.__name__} {rows} x {ni} L {length} E {embed}", model, rows, ni, length)
-    for nu, ni, embed, hidden in ((33, 258, 16, [512, 256, 128, 1]), (21, 30, 8, [32, 16, 1])):
+    for name, nu, ni, embed, hidden in (("DeepFM", 33, 258, 16, [512, 256, 128, 1]), ("DeepFM", 21, 30, 8, [32, 16, 1]),
+                                        ("PNN", 33, 258, 16, [256, 128, 64, 32]), ("PNN", 21, 30, 8, [32, 16])):
         torch.manual_seed(nu)
-        model = spread(zoo.DeepFM(nu, ni, hidden, embed), ni)
+        if name == "DeepFM":
+            model = spread(zoo.DeepFM(nu, ni, hidden, embed), ni)
+        else:
+            model = spread(zoo.PNN(embed, hidden, num_users=nu, num_items=ni), ni)
         gen = torch.Generator().manual_seed(nu + ni)
         uf = torch.zeros((nu, 24))                           # age, gender and occupation one-hot; genres Bernoulli
         uf[:, 0] = torch.rand(nu, generator=gen)
@@ -104,7 +110,7 @@ def main():
         uf[torch.arange(nu), 3 + torch.randint(0, 21, (nu,), generator=gen)] = 1.0
         itf = (torch.rand((ni, 19), generator=gen) < 0.09).float()
         scorer = model.catalogue_scorer(FeatureAssembler(uf.to(DEV), itf.to(DEV)))
-        user_grid(f"DeepFM[{scorer.path}] {nu} x {ni} E {embed}", scorer, nu, ni)
+        user_grid(f"{name}[{scorer.path}] {nu} x {ni} E {embed}", scorer, nu, ni)
 
 
 if __name__ == "__main__":

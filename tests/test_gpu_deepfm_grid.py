@@ -28,13 +28,13 @@ import torch
 import torch.nn.functional as F
 
 import golden_util as gu
+from grid_cases import (ATOL, DEV, RTOL, error_and_frac as _frac, features as _features, frame as _frame,
+                        observed as _observed, rank64 as _rank64)
 from oracle import ctr_oracle as orc
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 IT, UT = 128, 16             # asserted against ops.DEEPFM_GRID_ITEM_TILE / ops.DEEPFM_GRID_USER_TILE below
 HIDDEN = (512, 256, 128, 1)
-RTOL, ATOL = 1e-5, 1e-6      # the project's tolerance for prob (tests/test_gpu_models.py)
 SHAPES_16 = [(1, 1), (5, 15), (5, 16), (5, 17), (3, IT - 1), (3, IT + 1), (33, 2 * IT + 2), (UT + 2, 37), (UT + 1, 20),
              (2 * UT + 1, 20)]
 SHAPES_128 = [(5, 16), (3, IT + 1), (33, 2 * IT + 2), (UT + 2, 37)]
@@ -56,26 +56,6 @@ def test_the_tiles_are_the_ones_the_shapes_were_chosen_for():
 
 
 # ------------------------------------------------------------------ the cases: CPU only, float64 reference
-def _features(nu, ni, gen):
-    """(user_features (nu, 24), item_features (ni, 19)) float32 of the module docstring"""
-    uf = torch.zeros((nu, 24))
-    uf[:, 0] = torch.rand(nu, generator=gen)
-    uf[torch.arange(nu), 1 + torch.randint(0, 2, (nu,), generator=gen)] = 1.0
-    uf[torch.arange(nu), 3 + torch.randint(0, 21, (nu,), generator=gen)] = 1.0
-    itf = (torch.rand((ni, 19), generator=gen) < 0.09).float()
-    if ni > 1:
-        itf[1] = 0.0
-    return uf, itf
-
-
-def _frame(uf, itf):
-    """the full (nu * ni, 45) feature frame, user-major"""
-    nu, ni = uf.shape[0], itf.shape[0]
-    u = torch.arange(nu).repeat_interleave(ni)
-    i = torch.arange(ni).repeat(nu)
-    return torch.cat([u[:, None].to(uf.dtype), i[:, None].to(uf.dtype), uf[u], itf[i]], dim=1)
-
-
 def _deep_z3(p64, x64):
     """float64 pre-activation of the last deep layer over the frame"""
     h = F.linear(torch.cat(orc.six_field_vectors(p64, x64, FIELDS), dim=1), p64["linear.weight"], p64["linear.bias"])
@@ -158,17 +138,6 @@ def _case(nu, ni, dim=16, hidden=HIDDEN):
     model.load_state_dict(cpu.state_dict())
     model = model.to(DEV).eval()
     return model, model.catalogue_scorer(FeatureAssembler(uf.to(DEV), itf.to(DEV))), scores
-
-
-def _rank64(scores64, allowed=None):
-    """float64 ranking, best first, ties by ascending id; rows of ``allowed`` False rank last"""
-    s = np.where(allowed, scores64, -np.inf) if allowed is not None else scores64
-    return np.argsort(-s, axis=1, kind="stable")
-
-
-def _frac(got, scores64):
-    err = np.abs(got.cpu().numpy().astype(np.float64) - scores64)
-    return err.max(), (err / (ATOL + RTOL * np.abs(scores64))).max()
 
 
 # ------------------------------------------------------------------ 1. against float64
@@ -264,17 +233,6 @@ def test_score_grid_matches_the_per_sample_forward(nu, ni, dim):
 
 
 # ------------------------------------------------------------------ 4. recommend
-def _observed(nu, ni, seed=3):
-    """an ObservedPairs with user 0 having seen everything, user 1 all but two items, the others a random third"""
-    from deeplearningrecommendationsystem_amd.data import ObservedPairs
-    seen = torch.rand((nu, ni), generator=torch.Generator().manual_seed(seed)) < 0.33
-    seen[0] = True
-    seen[1] = True
-    seen[1, [2, ni - 1]] = False
-    u, i = seen.nonzero(as_tuple=True)
-    return ObservedPairs(u.to(DEV), i.to(DEV), nu, ni), seen.numpy()
-
-
 def _own_ranking(scorer, users, n, observed):
     """topk_rows of the scorer's own scores after rank_mask, -1 where the survivors run out"""
     from deeplearningrecommendationsystem_amd import ops

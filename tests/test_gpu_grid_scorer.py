@@ -17,8 +17,9 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from grid_cases import DEV, observed
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SHAPES = [(33, 130, 5), (5, 17, None)]          # rows, items, rows per chunk (None: the default, one whole chunk)
 
 
@@ -39,14 +40,9 @@ def _scores(rows, ni):
 
 
 def _observed(nu, ni, seed=3):
-    """an ObservedPairs with user 0 having seen everything, user 1 all but two items, the others a random third"""
-    from deeplearningrecommendationsystem_amd.data import ObservedPairs
-    seen = torch.rand((nu, ni), generator=torch.Generator().manual_seed(seed)) < 0.33
-    seen[0] = True
-    seen[1] = True
-    seen[1, [2, ni - 1]] = False
-    u, i = seen.nonzero(as_tuple=True)
-    return ObservedPairs(u.to(DEV), i.to(DEV), nu, ni), seen
+    """``grid_cases.observed`` with the seen matrix as a tensor"""
+    pairs, seen = observed(nu, ni, seed)
+    return pairs, torch.from_numpy(seen)
 
 
 def _reference(scores, n, seen_rows):
