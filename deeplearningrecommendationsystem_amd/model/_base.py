@@ -297,11 +297,17 @@ class SixFieldGridScorer(CatalogueScorer):
     scores the pairs from those.  The rows of BOTH sides are made for the whole table at every public call (the weights
     are read then), in passes of ``side_chunk`` rows at fixed positions: a table row's bits then do not depend on which
     users were asked for.  A model supplies ``_side_buffers``, ``_side_rows`` and ``_grid_scores``; ``_side_prepare``
-    and ``_operands`` are for what a model makes beside the two sides' buffers."""
+    and ``_operands`` are for what a model makes beside the two sides' buffers, ``_field_specs`` for a model whose
+    embedding stage is not ``six_field_specs`` over its tables."""
 
     path = "grid"
     row_blocks = 0               # 0: the launch's own geometry (tests set 1, 2 to reach the tile loop at small shapes)
     side_chunk = 1 << 16         # table rows per pass of _side: bounds its (rows, 6E) buffer and the hook's own
+
+    def _field_specs(self, p, dim, dev) -> list:
+        """the embedding stage's field list of the six vectors at columns f * dim; a model whose tables are not the six
+        of ``six_field_specs`` brings its own"""
+        return six_field_specs([t.detach() for t in p.tables], dim)
 
     def _side_prepare(self, p) -> None:
         """runs once a side, in front of its allocations and its passes: what ``_side_rows`` reads and does not make"""
@@ -342,7 +348,7 @@ class SixFieldGridScorer(CatalogueScorer):
             x = asm.feature(ids, zero) if user_side else asm.feature(zero, ids)
             # the field vectors exactly as the forward gathers them
             emb = torch.empty((hi - lo, 6 * dim), dtype=torch.float32, device=dev)
-            ops.embed_fwd(six_field_specs([t.detach() for t in p.tables], dim), x, hi - lo, emb, flag)
+            ops.embed_fwd(self._field_specs(p, dim, dev), x, hi - lo, emb, flag)
             self._side_rows(p, x, emb, emb.view(hi - lo, 6, dim), lo, hi, user_side, buffers)
         return buffers
 

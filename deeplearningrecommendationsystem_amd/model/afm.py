@@ -8,7 +8,8 @@ from torch.nn.init import xavier_normal_
 from .. import ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, FieldSpec
 from .._lib import FIELD_BAG, FIELD_ID_F32
-from ._base import FeatureModel, Params
+from ._base import CatalogueScorer, FeatureModel, Params, SixFieldGridScorer
+from .pnn import _CROSS_PAIRS, _ITEM_PAIRS, _USER_PAIRS   # the 15 pair columns by side: AFM's pairs are PNN's
 
 NVEC, NPAIRS = 6, 15
 
@@ -115,3 +116,65 @@ class AFM(FeatureModel):
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)
+
+    def catalogue_scorer(self, assembler):
+        """as ``FeatureModel.catalogue_scorer``; where ``grid_path`` says "grid" the scores come from
+        ``ctr_afm_grid_scores`` over table rows made once per call, not from the per-sample forward"""
+        grid = grid_path(self.user_embedding.embedding_dim, self.attention_W.shape[1]) == "grid"
+        return (_GridScorer if grid else CatalogueScorer)(self, assembler)
+
+
+def grid_path(embedding_dim, attention_dim) -> str:
+    """how a ``catalogue_scorer`` scores an AFM of these shapes: "grid" -- user-side and item-side table rows, then
+    ``ctr_afm_grid_scores`` -- where the library has that kernel, else "forward": the per-sample forward over feature
+    rows assembled chunk by chunk.  A function of shapes alone."""
+    return "grid" if ops.afm_grid_supported(embedding_dim, attention_dim) else "forward"
+
+
+class _GridScorer(SixFieldGridScorer):
+    """AFM on the user x item grid.  Per pair product p the model needs s(p) = h . relu(W^T p + b_att) and t(p) = o . p
+    (``output_layer`` of the pooled vector is the pooled t), every field vector belongs to the user or to the item, and
+    a softmax can be merged from summaries, so
+        out = sigmoid(a[u] + b[i] + n / d),   (m, d, n) = the softmax sums over the user's six products (mU, dU, nU),
+                                              the item's one (sI, tI) and the eight cross products FU_a[u] * FI_b[i]
+    with the wide part split into a / b (every bias on the item side).  The kernel forms the cross products from the
+    sides' field vectors FU (U, 4E) / FI (I, 2E); a side's own products go through the forward's kernels here."""
+
+    side_chunk = 1 << 14         # the pass also holds the (rows * 15, E) products and a side's own with their hidden rows
+
+    def _field_specs(self, p, dim, dev):
+        return self.model._specs([t.detach() for t in p.tables], dim, dev)
+
+    def _side_buffers(self, p, rows, dim, user_side, dev):
+        """(S (R, 4): a, mU, dU, nU, or (R, 3): b, sI, tI; F (R, 4E) or (R, 2E)) of every row of one side's table"""
+        return (torch.empty((rows, 4 if user_side else 3), dtype=torch.float32, device=dev),
+                torch.empty((rows, len(self._fields(user_side)) * dim), dtype=torch.float32, device=dev))
+
+    def _side_rows(self, p, x, emb, vec, lo, hi, user_side, buffers):
+        s, f = buffers
+        rows, dim = hi - lo, vec.shape[2]
+        f[lo:hi] = vec[:, self._fields(user_side), :].reshape(rows, -1)
+        self._zero_other(vec, user_side)
+        pairs = self.model._padded_rows(rows * NPAIRS, dim, emb.device)
+        ops.pairprod_fwd(emb, NVEC, dim, pairs)
+        cols = _USER_PAIRS if user_side else _ITEM_PAIRS
+        own = pairs.view(rows, NPAIRS, dim)[:, cols, :].reshape(rows * len(cols), dim)
+        hidden = ops.linear_fwd(own, p.att_w.detach().t().contiguous(), p.att_b.detach(), ACT_RELU)
+        logit = ops.linear_fwd(hidden, p.att_h.detach().t().contiguous(), None, ACT_NONE).view(rows, len(cols))
+        t = ops.linear_fwd(own, p.out_w.detach(), None, ACT_NONE).view(rows, len(cols))
+        lin_w = p.lin_w.detach()[0]
+        split = 2 + self.assembler.user_features.shape[1]                     # feature columns [2, split) are the user's
+        if user_side:
+            m = logit.max(dim=1).values
+            e = torch.exp(logit - m[:, None])
+            s[lo:hi, 0] = p.user1.detach()[lo:hi, 0] + (x[:, 2:split] * lin_w[:split - 2]).sum(dim=1)
+            s[lo:hi, 1], s[lo:hi, 2], s[lo:hi, 3] = m, e.sum(dim=1), (e * t).sum(dim=1)
+        else:
+            s[lo:hi, 0] = (p.item1.detach()[lo:hi, 0] + (x[:, split:] * lin_w[split - 2:]).sum(dim=1)
+                           + p.lin_b.detach() + p.out_b.detach())
+            s[lo:hi, 1], s[lo:hi, 2] = logit[:, 0], t[:, 0]
+
+    def _grid_scores(self, shared, users, user0, rows):
+        p, (su, fu), (si, fi) = shared
+        return ops.afm_grid_scores(su, si, fu, fi, p.att_w, p.att_b, p.att_h, p.out_w, users=users, user0=user0,
+                                   rows=rows, row_blocks=self.row_blocks)

@@ -1164,6 +1164,60 @@ def pnn_grid_scores(zu: torch.Tensor, zi: torch.Tensor, fu: torch.Tensor, fi: to
 
 
 # ---------------------------------------------------------------------------
+# AFM over the user x item grid (csrc/afm_grid.hip)
+# ---------------------------------------------------------------------------
+AFM_GRID_ATTENTION = 64                     # attention_dim: four sixteen-unit blocks of the matrix cores
+AFM_GRID_MAX_EMBED = 128
+AFM_GRID_CROSS = 8                          # products of a user-side with an item-side field vector
+AFM_GRID_ITEM_TILE = _lib.CTR_AFM_GRID_ITEM_TILE     # items of a workgroup
+AFM_GRID_USER_TILE = _lib.CTR_AFM_GRID_USER_TILE     # users staged at a time
+
+
+def afm_grid_supported(embedding_dim, attention_dim) -> bool:
+    """whether ``ctr_afm_grid_scores`` takes a six-field AFM of this embedding width and this attention width.  A
+    function of the two shapes alone."""
+    dim = int(embedding_dim)
+    return int(attention_dim) == AFM_GRID_ATTENTION and 16 <= dim <= AFM_GRID_MAX_EMBED and dim % 16 == 0
+
+
+def afm_grid_scores(su: torch.Tensor, si: torch.Tensor, fu: torch.Tensor, fi: torch.Tensor, att_w: torch.Tensor,
+                    att_b: torch.Tensor, att_h: torch.Tensor, out_w: torch.Tensor, users: Optional[torch.Tensor] = None,
+                    user0: int = 0, rows: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                    row_blocks: int = 0) -> torch.Tensor:
+    """(rows, num_items) float32: ``sigmoid(a[u] + b[i] + sum_k w_k t_k)`` with ``w`` the softmax over the logits
+    ``s = att_h . relu(att_w^T p + att_b)`` of AFM's 15 pair products and ``t = out_w . p``: the user's six come as
+    ``su[u]`` = (a, max s, sum exp(s - max), sum exp(s - max) t), the item's one as ``si[i]`` = (b, s, t), and the eight
+    products of a vector of ``fu[u]`` (U, 4E) with a vector of ``fi[i]`` (I, 2E) are formed in the kernel
+    (ctr_afm_grid_scores), for the users ``users`` (1-D int64, validated by the caller) or ``user0 .. user0 + rows``
+    against every item.  ``att_w`` is (E, A) as the model stores it.  ``row_blocks``: workgroups that share an item
+    tile's user tiles, 0 for the launch's own choice; the scores do not depend on it.  A shape the kernel is not built
+    for raises: there is no other path behind this call (``afm_grid_supported`` says beforehand)."""
+    su, si, fu, fi, att_w = (_mat(t.detach(), w).contiguous() for t, w in (
+        (su, "su"), (si, "si"), (fu, "fu"), (fi, "fi"), (att_w, "att_w")))
+    att_b, att_h, out_w = _f32_vectors("afm_grid_scores", "att_b, att_h and out_w", att_b, att_h, out_w)
+    nu, ni = su.shape[0], si.shape[0]
+    dim, att = att_w.shape
+    if su.shape[1] != 4 or si.shape[1] != 3:
+        raise ValueError("afm_grid_scores: su must be (num_users, 4) and si (num_items, 3)")
+    if fu.shape != (nu, 4 * dim) or fi.shape != (ni, 2 * dim):
+        raise ValueError("afm_grid_scores: fu must be (num_users, 4E) and fi (num_items, 2E) for att_w (E, A)")
+    if att_b.numel() != att or att_h.numel() != att or out_w.numel() != dim:
+        raise ValueError("afm_grid_scores: att_b and att_h hold one element per column of att_w, out_w one per row")
+    user0, rows, out = _grid_rows("afm_grid_scores", users, user0, rows, nu, ni, out, su.device)
+    # algorithmic: every table row of the call read once (the user tiles re-read item rows from cache), the scores
+    # written; per pair the eight products, their attention maps, the dots with att_h and out_w, the softmax
+    rc = _timed("afm_grid_scores",
+                lambda: (4 * (rows * (4 + 4 * dim) + ni * (3 + 2 * dim) + rows * ni) + (8 * rows if users is not None else 0),
+                         rows * ni * AFM_GRID_CROSS * (3 * dim + 2 * dim * att + 3 * att + 8)),
+                _lib.load().ctr_afm_grid_scores, su.data_ptr(), si.data_ptr(), fu.data_ptr(), fi.data_ptr(), nu, ni,
+                dim, att, att_w.data_ptr(), att_b.data_ptr(), att_h.data_ptr(), out_w.data_ptr(),
+                _lib.ptr(users) if users is not None and rows else None, user0, rows,
+                _lib.ptr(out) if out.numel() else None, _ld(out) if rows else ni, int(row_blocks), _lib.stream_ptr())
+    _lib.check(rc, "ctr_afm_grid_scores")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # feature interactions
 # ---------------------------------------------------------------------------
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112

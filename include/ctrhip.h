@@ -644,6 +644,35 @@ int ctr_pnn_grid_scores(const float* zu, const float* zi, const float* fu, const
                         const int64_t* users /*nullable*/, int64_t user0, int64_t rows, float* out, int64_t ldo,
                         int row_blocks, void* stream);
 
+/* AFM (six fields) over the user x item grid (csrc/afm_grid.hip): the scores of `rows` users against EVERY item in one
+ * launch, with no feature matrix.  Every field vector belongs to the user (fields 0, 2, 3, 4) or to the item (1, 5), and
+ * per pair product p the model needs only s(p) = att_h . relu(att_w^T p + att_b) and t(p) = out_w . p, so it splits into
+ * table rows the caller makes with ctr_embed_fwd, ctr_pairprod_fwd and ctr_linear_fwd:
+ *   (s_c, t_c) of the eight cross products U0 I0, U0 I1, U1 I0, U1 I1, U2 I0, U2 I1, U3 I0, U3 I1 (elementwise);
+ *        U0..U3 = fu[u_r] (user, age, gender, occupation vectors, `embed` floats each), I0, I1 = fi[i] (item, movie)
+ *   w = softmax over the 15 logits: the user's six (summarised by mU = max s, dU = sum exp(s - mU), nU = sum exp(s - mU) t),
+ *        the item's one (sI, tI) and the eight s_c; the maximum runs along, so logits of any size are taken
+ *   out[r * ldo + i] = sigmoid(a[u_r] + b[i] + sum_k w_k t_k)
+ *   u_r = users[r] (users set: any order, repeats allowed) or user0 + r (users NULL; user0 + rows <= num_users)
+ * su (num_users, 4): a, mU, dU, nU per user; si (num_items, 3): b, sI, tI per item (b holds every bias); fu (num_users,
+ * 4 embed), fi (num_items, 2 embed); att_w is (embed, attention) as the model stores it, att_b and att_h have
+ * `attention` elements, out_w `embed`.  All dense row-major.
+ * Admitted: attention == 64, embed a multiple of 16 in 16 .. 128, num_users, num_items < 2^31; anything else is
+ * CTR_ELIMIT.  A null pointer, a negative count, ldo < num_items, row_blocks < 0 or a row range outside the user table
+ * is CTR_EINVAL; su / fu / fi / att_w not 16-byte aligned is CTR_EALIGN -- all before anything is enqueued, in that
+ * order.  rows == 0 or num_items == 0 enqueues nothing and returns CTR_OK.  Columns past num_items of a row of out are
+ * not touched.  A workgroup takes CTR_AFM_GRID_ITEM_TILE items and walks user tiles of CTR_AFM_GRID_USER_TILE rows;
+ * row_blocks > 0 is the number of workgroups that share an item tile's user tiles, 0 leaves it to the launch (a small
+ * multiple of the CU count in all).  The caller validates `users`: an id outside [0, num_users) is clamped into the
+ * table, not reported.  No atomics; a pair's score is a function of its user's rows, its item's rows and the weights
+ * alone, bitwise, whatever the rows, their order, the items' positions or row_blocks. */
+#define CTR_AFM_GRID_ITEM_TILE 128
+#define CTR_AFM_GRID_USER_TILE 16
+int ctr_afm_grid_scores(const float* su, const float* si, const float* fu, const float* fi, int64_t num_users,
+                        int64_t num_items, int embed, int attention, const float* att_w, const float* att_b,
+                        const float* att_h, const float* out_w, const int64_t* users /*nullable*/, int64_t user0,
+                        int64_t rows, float* out, int64_t ldo, int row_blocks, void* stream);
+
 /* gy: gradient of the LAST layer's output; gx (nullable): gradient of x.  workspace is
  * required: (number of workgroups <= 256) * sum_i (n_i*k_i + n_i) floats. */
 int ctr_mlp_bwd(const float* x, int64_t ldx, int64_t m, const ctr_mlp_layer_t* layers, int nlayers,
