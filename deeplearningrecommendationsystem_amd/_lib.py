@@ -34,6 +34,10 @@ CTR_PNN_GRID_ITEM_TILE = 128
 CTR_PNN_GRID_USER_TILE = 16
 CTR_AFM_GRID_ITEM_TILE = 128
 CTR_AFM_GRID_USER_TILE = 16
+CTR_LOWRANK_GRID_ITEM_TILE = 128
+CTR_LOWRANK_GRID_USER_TILE = 32
+CTR_WIDEDEEP_GRID_ITEM_TILE = 128
+CTR_WIDEDEEP_GRID_USER_TILE = 16
 FIELD_ID_I64, FIELD_ID_F32, FIELD_BAG, FIELD_DENSE, FIELD_PROD_I64 = range(5)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = range(3)
 
@@ -219,6 +223,8 @@ SIGNATURES = {
     "ctr_pnn_grid_scores": (_i, [_p, _p, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _l, _p, _l,
                                  _i, _p]),
     "ctr_afm_grid_scores": (_i, [_p, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _l, _l, _p, _l, _i, _p]),
+    "ctr_lowrank_grid_scores": (_i, [_p, _p, _p, _p, _l, _l, _i, _p, _l, _l, _p, _l, _i, _p]),
+    "ctr_widedeep_grid_scores": (_i, [_p, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _l, _p, _l, _i, _p]),
     "ctr_mlp_bwd": (_i, [_p, _l, _l, C.POINTER(MlpLayer), _i, _p, _l, _p, _l, _p, _l, _p]),
     "ctr_negative_sample": (_i, [_p, _l, _l, _l, _i, C.c_uint64, _p, _p, _p, _p]),
     "ctr_assemble_features": (_i, [_p, _p, _l, _p, _i, _l, _p, _i, _l, _p, _l, _p, _p]),

@@ -35,6 +35,7 @@ constexpr int kN2 = 128;                       // width of h2 = the w3 dot
 constexpr int kUT = CTR_DEEPFM_GRID_USER_TILE; // users of a user tile
 constexpr int kItems = CTR_DEEPFM_GRID_ITEM_TILE;   // items of a workgroup
 static_assert(kItems == 16 * kWaves, "a wave owns sixteen items");
+static_assert(CTR_WIDEDEEP_GRID_ITEM_TILE == kItems && CTR_WIDEDEEP_GRID_USER_TILE == kUT, "one template, one tiling");
 
 #include "mfma16_tower.inc"
 #include "grid_frame.inc"
@@ -59,7 +60,9 @@ struct Grid {
   int64_t utiles;
 };
 
-template <int E16>   // E = 16 E16: a lane holds E16 16-byte pieces of its item's SI row
+// E = 16 E16: a lane holds E16 16-byte pieces of its item's SI row.  E16 == 0 is Wide & Deep (ctr_widedeep_grid_scores):
+// the same model without the FM dot -- su / si, their registers and their LDS stage are compiled out
+template <int E16>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 deepfm_grid_scores_kernel(const Tower T, const Grid G) {
   constexpr int E = 16 * E16, E4 = E / 4;
@@ -76,7 +79,7 @@ deepfm_grid_scores_kernel(const Tower T, const Grid G) {
   const int64_t item = (int64_t)blockIdx.x * kItems + wave * 16 + n;
   const int64_t ic = item < G.ni ? item : G.ni - 1;   // items past the table: the last row, never stored
   // ---- prologue: the layer's weights, the head, this lane's pieces of its item's rows
-  f32x4 zI[16], sI[E16];
+  f32x4 zI[16], sI[E16 > 0 ? E16 : 1];
   float bI;
   {
     f32x4 wv[kFStagePer];
@@ -88,8 +91,10 @@ deepfm_grid_scores_kernel(const Tower T, const Grid G) {
     const float hv = *hp;
 #pragma unroll
     for (int j = 0; j < 16; ++j) zI[j] = ldg4(G.zi + ic * kN0 + 16 * j + 4 * q);
+    if constexpr (E16 > 0) {
 #pragma unroll
-    for (int k = 0; k < E16; ++k) sI[k] = ldg4(G.si + ic * E + E4 * q + 4 * k);
+      for (int k = 0; k < E16; ++k) sI[k] = ldg4(G.si + ic * E + E4 * q + 4 * k);
+    }
     bI = G.b[ic];
     stage_forward_store(s_w, s_b, wv, wdst, bv);
     if (threadIdx.x < kN2) s_w3[threadIdx.x] = w3v;
@@ -111,16 +116,19 @@ deepfm_grid_scores_kernel(const Tower T, const Grid G) {
         const int row = (threadIdx.x >> 6) + e * (kThreads / 64);
         vz[e] = ldg4(G.zu + user_of(row) * kN0 + 4 * (threadIdx.x & 63));
       }
-      const int srow = threadIdx.x / E4, spiece = threadIdx.x % E4;
-      const bool smine = threadIdx.x < kUT * E4;
-      vs = ldg4(G.su + user_of(smine ? srow : 0) * E + 4 * (smine ? spiece : 0));
+      constexpr int S4 = E16 > 0 ? E4 : 1;              // (Wide & Deep stages no SU row)
+      const int srow = threadIdx.x / S4, spiece = threadIdx.x % S4;
+      const bool smine = E16 > 0 && threadIdx.x < kUT * E4;
+      if constexpr (E16 > 0) vs = ldg4(G.su + user_of(smine ? srow : 0) * E + 4 * (smine ? spiece : 0));
       if (threadIdx.x < kUT) va = G.a[user_of(threadIdx.x)];
 #pragma unroll
       for (int e = 0; e < kStagePasses; ++e) {
         const int row = (threadIdx.x >> 6) + e * (kThreads / 64);
         *reinterpret_cast<f32x4*>(s_zu + row * kN0 + 4 * (threadIdx.x & 63)) = vz[e];
       }
-      if (smine) *reinterpret_cast<f32x4*>(s_su + srow * E + 4 * spiece) = vs;
+      if constexpr (E16 > 0) {
+        if (smine) *reinterpret_cast<f32x4*>(s_su + srow * E + 4 * spiece) = vs;
+      }
       if (threadIdx.x < kUT) s_a[threadIdx.x] = va;
     }
     __syncthreads();                                  // (the first tile: the weights and the head as well)
@@ -135,11 +143,13 @@ deepfm_grid_scores_kernel(const Tower T, const Grid G) {
       }
       // FM cross term: the four lanes of an item hold E/4 terms each
       float dfm = 0.0f;
+      if constexpr (E16 > 0) {
 #pragma unroll
-      for (int k = 0; k < E16; ++k) {
-        const f32x4 s = *reinterpret_cast<const f32x4*>(s_su + r * E + E4 * q + 4 * k);
-        dfm = fmaf(sI[k][0], s[0], dfm); dfm = fmaf(sI[k][1], s[1], dfm);
-        dfm = fmaf(sI[k][2], s[2], dfm); dfm = fmaf(sI[k][3], s[3], dfm);
+        for (int k = 0; k < E16; ++k) {
+          const f32x4 s = *reinterpret_cast<const f32x4*>(s_su + r * E + E4 * q + 4 * k);
+          dfm = fmaf(sI[k][0], s[0], dfm); dfm = fmaf(sI[k][1], s[1], dfm);
+          dfm = fmaf(sI[k][2], s[2], dfm); dfm = fmaf(sI[k][3], s[3], dfm);
+        }
       }
       const float au = s_a[r];
       f32x4 y[8];
@@ -152,7 +162,8 @@ deepfm_grid_scores_kernel(const Tower T, const Grid G) {
         d3 = fmaf(y[bk][2], wv[2], d3); d3 = fmaf(y[bk][3], wv[3], d3);
       }
       const float h3 = fmaxf(column_sum(d3) + b3, 0.0f);
-      const float fm = (au + bI) + column_sum(dfm);
+      float fm = au + bI;
+      if constexpr (E16 > 0) fm += column_sum(dfm);
       if (store) orow[(r0 + r) * G.ldo] = ctr_sigmoid(fmaf(o0, fm, fmaf(o1, h3, ob)));   // (the four lanes of an item agree)
     }
   }
@@ -163,6 +174,23 @@ constexpr int kTilesPerPrologue = 32;
 constexpr void (*kKernels[8])(const Tower, const Grid) = {   // by E / 16
     deepfm_grid_scores_kernel<1>, deepfm_grid_scores_kernel<2>, deepfm_grid_scores_kernel<3>, deepfm_grid_scores_kernel<4>,
     deepfm_grid_scores_kernel<5>, deepfm_grid_scores_kernel<6>, deepfm_grid_scores_kernel<7>, deepfm_grid_scores_kernel<8>};
+
+
+// the launch behind both entries: `embed` 0 is Wide & Deep
+int launch(const float* zu, const float* zi, const float* su, const float* si, const float* a, const float* b,
+           int64_t num_users, int64_t num_items, int embed, const float* w2, const float* b2, const float* w3,
+           const float* b3, const float* out_w, const float* out_b, const int64_t* users, int64_t user0, int64_t rows,
+           float* out, int64_t ldo, int row_blocks, void* stream) {
+  Tower T;
+  T.w[0] = w2; T.b[0] = b2; T.y[0] = nullptr; T.ldy[0] = 0;
+  const int64_t utiles = ctr_ceil_div(rows, kUT), xtiles = ctr_ceil_div(num_items, kItems);
+  const int64_t y = row_blocks > 0 ? row_blocks : grid_row_blocks(xtiles, utiles, kTilesPerPrologue);
+  const Grid G{zu, zi, su, si, a, b, w3, b3, out_w, out_b, users, user0, rows, num_users, num_items, out, ldo, utiles};
+  // item tiles along x (neighbouring workgroups share their user tile's rows in L2), row blocks along y
+  return grid_launch(embed ? kKernels[embed / 16 - 1] : deepfm_grid_scores_kernel<0>,
+                     dim3((unsigned)xtiles, grid_clamp_y(y, utiles)), kThreads,
+                     sizeof(float) * (size_t)lds_floats(embed), stream, T, G);
+}
 
 }  // namespace
 
@@ -178,12 +206,22 @@ extern "C" int ctr_deepfm_grid_scores(const float* zu, const float* zi, const fl
   if (!ctr_aligned16(zu) || !ctr_aligned16(zi) || !ctr_aligned16(su) || !ctr_aligned16(si) || !ctr_aligned16(w2))
     return CTR_EALIGN;
   if (rows == 0 || num_items == 0) return CTR_OK;
-  Tower T;
-  T.w[0] = w2; T.b[0] = b2; T.y[0] = nullptr; T.ldy[0] = 0;
-  const int64_t utiles = ctr_ceil_div(rows, kUT), xtiles = ctr_ceil_div(num_items, kItems);
-  const int64_t y = row_blocks > 0 ? row_blocks : grid_row_blocks(xtiles, utiles, kTilesPerPrologue);
-  const Grid G{zu, zi, su, si, a, b, w3, b3, out_w, out_b, users, user0, rows, num_users, num_items, out, ldo, utiles};
-  // item tiles along x (neighbouring workgroups share their user tile's rows in L2), row blocks along y
-  return grid_launch(kKernels[embed / 16 - 1], dim3((unsigned)xtiles, grid_clamp_y(y, utiles)), kThreads,
-                     sizeof(float) * (size_t)lds_floats(embed), stream, T, G);
+  return launch(zu, zi, su, si, a, b, num_users, num_items, embed, w2, b2, w3, b3, out_w, out_b, users, user0, rows, out,
+                ldo, row_blocks, stream);
+}
+
+// Wide & Deep: the same kernel template without the FM dot (model/widedeep.py)
+extern "C" int ctr_widedeep_grid_scores(const float* zu, const float* zi, const float* a, const float* b,
+                                        int64_t num_users, int64_t num_items, int n1, int n2, const float* w2,
+                                        const float* b2, const float* w3, const float* b3, const float* out_w,
+                                        const float* out_b, const int64_t* users, int64_t user0, int64_t rows,
+                                        float* out, int64_t ldo, int row_blocks, void* stream) {
+  CTR_REQUIRE(grid_users_ok(users, user0, rows, num_users, num_items, out, ldo) && row_blocks >= 0, CTR_EINVAL);
+  CTR_REQUIRE(zu && zi && a && b && w2 && b2 && w3 && b3 && out_w && out_b, CTR_EINVAL);
+  if (n1 != kN0 || n2 != kN2) return CTR_ELIMIT;
+  CTR_REQUIRE(grid_ids_fit(num_users, num_items), CTR_ELIMIT);
+  if (!ctr_aligned16(zu) || !ctr_aligned16(zi) || !ctr_aligned16(w2)) return CTR_EALIGN;
+  if (rows == 0 || num_items == 0) return CTR_OK;
+  return launch(zu, zi, nullptr, nullptr, a, b, num_users, num_items, 0, w2, b2, w3, b3, out_w, out_b, users, user0, rows,
+                out, ldo, row_blocks, stream);
 }

@@ -1,10 +1,10 @@
-// Host frame of the grid scorers ({ncf,din,dien,deepfm,pnn,afm}_grid.hip): what surrounds a grid kernel's launch -- the
+// Host frame of the grid scorers ({ncf,din,dien,deepfm,pnn,afm,lowrank}_grid.hip): what surrounds a grid kernel's launch -- the
 // argument checks the user-grid entries share, gridDim.y, and the launch itself.  Host code only: nothing here reaches
 // a kernel's instruction stream (device helpers: grid_frame.inc).
 #pragma once
 #include "ctr_common.h"
 
-// ---- the user x item entries (NeuralCF, DeepFM, PNN, AFM): rows are users[r], or user0 + r; out is (rows, >= num_items)
+// ---- the user x item entries (NeuralCF, DeepFM, Wide & Deep, PNN, AFM, low-rank): rows are users[r], or user0 + r; out is (rows, >= num_items)
 // every failure of this check is CTR_EINVAL
 static inline bool grid_users_ok(const int64_t* users, int64_t user0, int64_t rows, int64_t num_users, int64_t num_items,
                                  const float* out, int64_t ldo) {

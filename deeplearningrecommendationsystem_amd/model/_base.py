@@ -298,7 +298,9 @@ class SixFieldGridScorer(CatalogueScorer):
     are read then), in passes of ``side_chunk`` rows at fixed positions: a table row's bits then do not depend on which
     users were asked for.  A model supplies ``_side_buffers``, ``_side_rows`` and ``_grid_scores``; ``_side_prepare``
     and ``_operands`` are for what a model makes beside the two sides' buffers, ``_field_specs`` for a model whose
-    embedding stage is not ``six_field_specs`` over its tables."""
+    embedding stage is not ``six_field_specs`` over its tables; such a model also says through ``_tables`` which tables
+    those are, through ``_stage`` how wide a row of its stage is (FFM: twelve vectors; Wide & Deep: the 5E + 1 stack)
+    and through ``_zero_other`` which of its columns are the other side's."""
 
     path = "grid"
     row_blocks = 0               # 0: the launch's own geometry (tests set 1, 2 to reach the tile loop at small shapes)
@@ -308,6 +310,15 @@ class SixFieldGridScorer(CatalogueScorer):
         """the embedding stage's field list of the six vectors at columns f * dim; a model whose tables are not the six
         of ``six_field_specs`` brings its own"""
         return six_field_specs([t.detach() for t in p.tables], dim)
+
+    def _tables(self, p) -> list:
+        """the embedding tables of ``p``, every one of them ``dim`` wide"""
+        return p.tables
+
+    def _stage(self, rows, dim, dev) -> tuple:
+        """(the buffer the embedding stage fills for ``rows`` feature rows, the same by field vector -- or None)"""
+        emb = torch.empty((rows, 6 * dim), dtype=torch.float32, device=dev)
+        return emb, emb.view(rows, 6, dim)
 
     def _side_prepare(self, p) -> None:
         """runs once a side, in front of its allocations and its passes: what ``_side_rows`` reads and does not make"""
@@ -337,7 +348,7 @@ class SixFieldGridScorer(CatalogueScorer):
 
     def _side(self, p, user_side: bool):
         asm = self.assembler
-        dev, dim = self._device(), p.tables[0].shape[1]
+        dev, dim = self._device(), self._tables(p)[0].shape[1]
         rows = self.num_users if user_side else self.num_items
         self._side_prepare(p)
         buffers = self._side_buffers(p, rows, dim, user_side, dev)
@@ -347,14 +358,14 @@ class SixFieldGridScorer(CatalogueScorer):
             ids, zero = torch.arange(lo, hi, device=dev), torch.zeros(hi - lo, dtype=torch.int64, device=dev)
             x = asm.feature(ids, zero) if user_side else asm.feature(zero, ids)
             # the field vectors exactly as the forward gathers them
-            emb = torch.empty((hi - lo, 6 * dim), dtype=torch.float32, device=dev)
+            emb, vec = self._stage(hi - lo, dim, dev)
             ops.embed_fwd(self._field_specs(p, dim, dev), x, hi - lo, emb, flag)
-            self._side_rows(p, x, emb, emb.view(hi - lo, 6, dim), lo, hi, user_side, buffers)
+            self._side_rows(p, x, emb, vec, lo, hi, user_side, buffers)
         return buffers
 
     def _shared(self):
         p = self.model._params()
-        self.model._need_device(p.tables[0], self.assembler.user_features)
+        self.model._need_device(self._tables(p)[0], self.assembler.user_features)
         rest = self._operands(p)
         return (p, self._side(p, True), self._side(p, False)) + rest
 

@@ -8,7 +8,7 @@ from torch.nn.init import xavier_normal_
 from .. import ops
 from ..ops import FieldSpec
 from .._lib import FIELD_BAG, FIELD_ID_F32, FIELD_ID_I64
-from ._base import FeatureModel, Params
+from ._base import CatalogueScorer, FeatureModel, Params, SixFieldGridScorer
 
 # the 12 field-aware vectors in buffer order, and the reference's 15 dot products
 # (model/ffm.py:62-80) as index pairs into that order
@@ -29,6 +29,17 @@ _SOURCE = {"age": (FIELD_BAG, 2, 1), "gender": (FIELD_BAG, 3, 2), "occupation": 
 
 
 SHARDED = ("userid_user", "userid_item", "itemid_user", "itemid_item")  # the tables indexed by user / item id
+
+# on the user x item grid a vector belongs to the side its SOURCE column comes from: movie and itemid to the item
+_ITEM_VECTORS = tuple(k for k, name in enumerate(VECTORS) if name.split("_")[0] in ("movie", "itemid"))
+_USER_VECTORS = tuple(k for k in range(len(VECTORS)) if k not in _ITEM_VECTORS)
+_USER_PAIRS = tuple((i, j) for i, j in PAIRS if i in _USER_VECTORS and j in _USER_VECTORS)     # six
+_ITEM_PAIRS = tuple((i, j) for i, j in PAIRS if i in _ITEM_VECTORS and j in _ITEM_VECTORS)     # one
+_CROSS_PAIRS = tuple((i, j) if i in _USER_VECTORS else (j, i)
+                     for i, j in PAIRS if (i in _USER_VECTORS) != (j in _USER_VECTORS))         # eight, (user's, item's)
+_CROSS_USER = tuple(sorted({i for i, _ in _CROSS_PAIRS}))     # age_item, gender_item, occupation_item, userid_item
+_CROSS_ITEM = tuple(sorted({j for _, j in _CROSS_PAIRS}))     # movie_user, itemid_user
+assert len(_CROSS_PAIRS) == len(_CROSS_USER) * len(_CROSS_ITEM)   # every one with every one: the eight dots are ONE
 
 
 class FFM(FeatureModel):
@@ -124,3 +135,61 @@ class FFM(FeatureModel):
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)
+
+    def catalogue_scorer(self, assembler):
+        """as ``FeatureModel.catalogue_scorer``; where ``grid_path`` says "grid" the scores come from
+        ``ctr_lowrank_grid_scores`` over table rows made once per call, not from the per-sample forward"""
+        if self.sharded:
+            raise ValueError("the user x item grid wants the whole id tables on one device: sharded=True models are "
+                             "not scored this way")
+        grid = grid_path(self.age_user.embedding_dim) == "grid"
+        return (_GridScorer if grid else CatalogueScorer)(self, assembler)
+
+
+def grid_path(num_vector) -> str:
+    """how a ``catalogue_scorer`` scores an FFM of this ``num_vector``: "grid" -- user-side and item-side table rows,
+    then ``ctr_lowrank_grid_scores`` at rank ``num_vector`` -- where the library has that kernel, else "forward": the
+    per-sample forward over feature rows assembled chunk by chunk.  A function of the shape alone."""
+    return "grid" if int(num_vector) > 0 and ops.lowrank_grid_supported(num_vector) else "forward"
+
+
+class _GridScorer(SixFieldGridScorer):
+    """FFM on the user x item grid.  Of the 15 dots six lie on the user's side, one on the item's, and the eight that
+    cross are every vector of {age, gender, occupation, userid}_item with every vector of {movie, itemid}_user, so they
+    are ONE dot <A[u], B[i]> of the two sums.  The reference adds the second-order scalar to all 43 dense inputs of
+    ``linear``, which scales it by sW = sum(linear.weight):
+        logit = a[u] + b[i] + <sW A[u], B[i]>
+        a = user(u) + w[:24] . x_u + bias + sW (the six own dots),   b = item(i) + w[24:] . x_i + sW (the one own dot)"""
+
+    def _tables(self, p):
+        return [getattr(p, name).detach() for name in VECTORS]
+
+    def _field_specs(self, p, dim, dev):
+        return self.model._specs(self._tables(p), dim)
+
+    def _stage(self, rows, dim, dev):
+        emb = torch.empty((rows, len(VECTORS) * dim), dtype=torch.float32, device=dev)
+        return emb, emb.view(rows, len(VECTORS), dim)
+
+    def _side_buffers(self, p, rows, dim, user_side, dev):
+        """(the side's operand of the cross dot (R, k), its first-order + own second-order term (R,))"""
+        return (torch.empty((rows, dim), dtype=torch.float32, device=dev),
+                torch.empty(rows, dtype=torch.float32, device=dev))
+
+    def _side_rows(self, p, x, emb, vec, lo, hi, user_side, buffers):
+        c, first = buffers
+        w = p.lin_w.detach().reshape(-1)
+        sw = w.sum()
+        own = torch.zeros(hi - lo, dtype=torch.float32, device=emb.device)
+        for i, j in (_USER_PAIRS if user_side else _ITEM_PAIRS):
+            own = own + (vec[:, i, :] * vec[:, j, :]).sum(1)
+        if user_side:
+            c[lo:hi] = sw * vec[:, _CROSS_USER, :].sum(1)
+            first[lo:hi] = p.user1.detach()[lo:hi, 0] + (x[:, 2:26] * w[:24]).sum(1) + p.lin_b.detach() + sw * own
+        else:
+            c[lo:hi] = vec[:, _CROSS_ITEM, :].sum(1)
+            first[lo:hi] = p.item1.detach()[lo:hi, 0] + (x[:, 26:45] * w[24:]).sum(1) + sw * own
+
+    def _grid_scores(self, shared, users, user0, rows):
+        _, (cu, a), (ci, b) = shared
+        return ops.lowrank_grid_scores(cu, ci, a, b, users=users, user0=user0, rows=rows, row_blocks=self.row_blocks)

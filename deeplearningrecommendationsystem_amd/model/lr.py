@@ -7,7 +7,7 @@ from torch.nn.init import xavier_normal_
 
 from .. import ops
 from ..ops import ACT_SIGMOID
-from ._base import FeatureModel, Params
+from ._base import CatalogueScorer, FeatureModel, Params
 
 
 class LogisticRegression(FeatureModel):
@@ -52,3 +52,38 @@ class LogisticRegression(FeatureModel):
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)
+
+    def catalogue_scorer(self, assembler):
+        """as ``FeatureModel.catalogue_scorer``; the scores come from the rank-0 arm of ``ctr_lowrank_grid_scores`` over
+        one bias per user and one per item, made once per call, not from the per-sample forward"""
+        return _GridScorer(self, assembler)
+
+
+def grid_path() -> str:
+    """how a ``catalogue_scorer`` scores a LogisticRegression: always "grid" (the model has no shape to refuse)"""
+    return "grid"
+
+
+class _GridScorer(CatalogueScorer):
+    """LogisticRegression on the user x item grid: ``sigmoid(a[u] + b[i])`` with
+        a = user(u) + w[:24] . x_u + bias,   b = item(i) + w[24:] . x_i
+    both made for the whole tables at every public call, so a table row's bits do not depend on the users asked for."""
+
+    path = "grid"
+    row_blocks = 0               # 0: the launch's own geometry (tests set 1, 2 to reach the tile loop at small shapes)
+
+    def _shared(self):
+        p, asm = self.model._params(), self.assembler
+        self.model._need_device(p.user1, asm.user_features)
+        w = p.w.detach().reshape(-1)
+        a = p.user1.detach()[:, 0] + (asm.user_features * w[:24]).sum(1) + p.b.detach()
+        b = p.item1.detach()[:, 0] + (asm.item_features * w[24:]).sum(1)
+        return a, b
+
+    def _scores(self, users, start, stop, shared=None):
+        rows = users.numel() if users is not None else stop - start
+        if rows == 0:
+            return torch.empty((0, self.num_items), dtype=torch.float32, device=self.device)
+        a, b = shared
+        return ops.lowrank_grid_scores(None, None, a, b, users=users, user0=start, rows=rows,
+                                       row_blocks=self.row_blocks)

@@ -5,8 +5,9 @@ import torch
 from torch import nn
 from torch.nn.init import xavier_normal_
 
-from .. import ops
+from .. import ops, topn
 from ._base import CtrModule
+from ._grid import UserGridScorer
 
 
 class _MFFunction(torch.autograd.Function):
@@ -54,3 +55,61 @@ class MatrixFactorization(CtrModule):
             items = self.item_embeddings.weight[:num_items]
             scores = ops.linear_fwd(users.contiguous(), items.contiguous(), None)
             return ops.topk_rows(scores, num_items).cpu().numpy()
+
+    # ---- the user x item grid: row scorers and a bounded-workspace ranker (no gradients, training paths untouched)
+    def _table_sizes(self):
+        return self.user_embeddings.weight.shape[0], self.item_embeddings.weight.shape[0]
+
+    def score_rows(self, start: int, stop: int) -> torch.Tensor:
+        """(stop - start, num_items) float32 device tensor, fresh and row-major: the probabilities of users
+        [start, stop) against every item -- the ``scores(start, stop)`` callable ``ranking_metrics`` takes.  Not
+        chunked: the caller chose the rows."""
+        return _GridScorer(self).score_rows(start, stop)
+
+    def score_grid(self, users=None) -> torch.Tensor:
+        """(len(users), num_items) float32 probabilities for any 1-D list of user ids (repeats and any order allowed;
+        an id outside the table raises IndexError); ``None``: every user.  Not chunked: the caller chose the rows."""
+        return _GridScorer(self).score_grid(users)
+
+    def recommend(self, users=None, n: int = 20, exclude=None) -> torch.Tensor:
+        """(len(users), n) int64: the items with the highest probability, best first, ties by ascending item id.
+        ``exclude``: an ``ObservedPairs`` whose pairs are left out (``ops.rank_mask``), or None; rows with fewer than
+        ``n`` items left end in -1.  Users are scored in chunks, so the workspace stays bounded."""
+        return _GridScorer(self).recommend(users, n, exclude)
+
+
+def grid_path(embedding_size) -> str:
+    """how ``score_rows`` / ``score_grid`` / ``recommend`` score a model of this embedding size: "grid" --
+    ``ctr_lowrank_grid_scores`` over the two tables as they are -- where the library has that kernel, else "forward":
+    the per-sample forward over ids generated chunk by chunk"""
+    return "grid" if int(embedding_size) > 0 and ops.lowrank_grid_supported(embedding_size) else "forward"
+
+
+_FORWARD_CHUNK = 1 << 20     # pairs per forward call of the "forward" path
+
+
+class _GridScorer(UserGridScorer):
+    """score rows of the user x item grid of one model.  The operands are the weight tables themselves: no copy is
+    made, so a scorer is never stale."""
+
+    row_blocks = 0               # 0: the launch's own geometry (tests set 1, 2 to reach the tile loop at small shapes)
+
+    def __init__(self, model: MatrixFactorization):
+        super().__init__(*model._table_sizes(), model.user_embeddings.weight.device)
+        self.model = model
+        self.path = grid_path(model.user_embeddings.weight.shape[1])
+
+    def _shared(self):
+        tables = self.model.user_embeddings.weight.detach(), self.model.item_embeddings.weight.detach()
+        self.model._need_device(*tables)
+        return tables
+
+    def _scores(self, users, start, stop, shared) -> torch.Tensor:
+        rows = users.numel() if users is not None else stop - start
+        if self.path == "grid":
+            return ops.lowrank_grid_scores(*shared, None, None, users=users, user0=start, rows=rows,
+                                           row_blocks=self.row_blocks)
+        out = torch.empty((rows, self.num_items), dtype=torch.float32, device=self.device)
+        topn.forward_grid(out, _FORWARD_CHUNK,
+                          lambda r, i: self.model.forward(users[r] if users is not None else r + start, i))
+        return out

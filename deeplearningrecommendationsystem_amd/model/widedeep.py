@@ -7,7 +7,7 @@ from torch.nn.init import xavier_normal_
 
 from .. import ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, Layer
-from ._base import FeatureModel, Params
+from ._base import CatalogueScorer, FeatureModel, Params, SixFieldGridScorer
 from .deepcrossing import DeepCrossing
 
 
@@ -85,3 +85,68 @@ class WideDeep(FeatureModel):
 
     def recommendation(self, num_users, user_item, k):
         return self._rank_users(num_users, user_item, k)
+
+    def catalogue_scorer(self, assembler):
+        """as ``FeatureModel.catalogue_scorer``; where ``grid_path`` says "grid" the scores come from
+        ``ctr_widedeep_grid_scores`` over table rows made once per call, not from the per-sample forward"""
+        hidden = [self.linear.out_features] + [lin.out_features for lin in self.dnn_network]
+        return (_GridScorer if grid_path(hidden) == "grid" else CatalogueScorer)(self, assembler)
+
+
+def grid_path(hidden_units) -> str:
+    """how a ``catalogue_scorer`` scores a Wide & Deep of these ``hidden_units`` (any embedding width): "grid" --
+    user-side and item-side table rows, then ``ctr_widedeep_grid_scores`` -- where the library has that kernel, else
+    "forward": the per-sample forward over feature rows assembled chunk by chunk.  A function of the shape alone."""
+    return "grid" if ops.widedeep_grid_supported(hidden_units) else "forward"
+
+
+class _GridScorer(SixFieldGridScorer):
+    """Wide & Deep on the user x item grid.  Every column of the (5E + 1) stack belongs to the user (user, age, gender,
+    occupation) or to the item (item, movie) and ``linear`` has no activation, so
+        h1 = relu(ZU[u] + ZI[i]),   ZU / ZI = W1 (W0 . a side's columns of the stack),   wide = a[u] + b[i]
+    with every bias on the item side; the rest of the model runs per pair inside the kernel."""
+
+    def _field_specs(self, p, dim, dev):
+        return DeepCrossing._specs([t.detach() for t in p.tables], dim)
+
+    def _stage(self, rows, dim, dev):
+        return FeatureModel._padded_rows(rows, 5 * dim + 1, dev), None
+
+    def _zero_other(self, stack, user_side):
+        e = (stack.shape[1] - 1) // 5                              # [user | item | age | gender | occupation | movie]
+        if user_side:
+            stack[:, e:2 * e] = 0.0
+            stack[:, 4 * e + 1:] = 0.0
+        else:
+            stack[:, :e] = 0.0
+            stack[:, 2 * e:4 * e + 1] = 0.0
+
+    def _side_prepare(self, p):
+        # the first layer's rows are 5E + 1 floats long: the GEMM reads a copy padded to 16-byte rows, as the forward
+        # does (made here, at every public call: the model's own copy belongs to its training step)
+        w0 = p.deep[0].weight.detach()
+        self._w0 = FeatureModel._padded_rows(w0.shape[0], w0.shape[1], w0.device)
+        self._w0.copy_(w0)
+
+    def _side_buffers(self, p, rows, dim, user_side, dev):
+        """(Z (R, 256), first-order + wide term (R,)) of every row of one side's table"""
+        return (torch.empty((rows, p.deep[1].weight.shape[0]), dtype=torch.float32, device=dev),
+                torch.empty(rows, dtype=torch.float32, device=dev))
+
+    def _side_rows(self, p, x, stack, vec, lo, hi, user_side, buffers):
+        z, c = buffers
+        w0, w1 = p.deep[0], p.deep[1]
+        wide = p.wide_w.detach().reshape(-1)
+        if user_side:
+            c[lo:hi] = p.user1.detach()[lo:hi, 0] + (x[:, 2:26] * wide[:24]).sum(1)
+        else:
+            c[lo:hi] = p.item1.detach()[lo:hi, 0] + (x[:, 26:45] * wide[24:]).sum(1) + p.wide_b.detach()
+        self._zero_other(stack, user_side)
+        t = ops.linear_fwd(stack, self._w0, None if user_side else w0.bias.detach())
+        ops.linear_fwd(t, w1.weight.detach(), None if user_side else w1.bias.detach(), out=z[lo:hi])
+
+    def _grid_scores(self, shared, users, user0, rows):
+        p, (zu, a), (zi, b) = shared
+        w2, w3 = p.deep[2], p.deep[3]
+        return ops.widedeep_grid_scores(zu, zi, a, b, w2.weight.detach(), w2.bias, w3.weight, w3.bias, p.out_w, p.out_b,
+                                        users=users, user0=user0, rows=rows, row_blocks=self.row_blocks)

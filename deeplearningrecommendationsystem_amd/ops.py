@@ -1218,6 +1218,109 @@ def afm_grid_scores(su: torch.Tensor, si: torch.Tensor, fu: torch.Tensor, fi: to
 
 
 # ---------------------------------------------------------------------------
+# a biased low-rank product over the user x item grid (csrc/lowrank_grid.hip): MF, FFM, LR
+# ---------------------------------------------------------------------------
+LOWRANK_GRID_MAX_RANK = 256
+LOWRANK_GRID_ITEM_TILE = _lib.CTR_LOWRANK_GRID_ITEM_TILE     # items of a workgroup (a wave: 32 of them)
+LOWRANK_GRID_USER_TILE = _lib.CTR_LOWRANK_GRID_USER_TILE     # users staged at a time = rows of the matrix-core tile
+
+
+def lowrank_grid_supported(rank) -> bool:
+    """whether ``ctr_lowrank_grid_scores`` takes this rank: 0 (the biases alone) and every multiple of 16 up to 256"""
+    rank = int(rank)
+    return 0 <= rank <= LOWRANK_GRID_MAX_RANK and rank % 16 == 0
+
+
+def lowrank_grid_scores(cu: Optional[torch.Tensor], ci: Optional[torch.Tensor], a: Optional[torch.Tensor],
+                        b: Optional[torch.Tensor], *, users: Optional[torch.Tensor] = None, user0: int = 0,
+                        rows: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                        row_blocks: int = 0) -> torch.Tensor:
+    """(rows, num_items) float32: ``sigmoid((a[u] + b[i]) + <cu[u], ci[i]>)`` for the users ``users`` (1-D int64,
+    validated by the caller) or ``user0 .. user0 + rows`` against every item (ctr_lowrank_grid_scores).  ``cu`` (U, K) and
+    ``ci`` (I, K) are read as they are (no copy where they are contiguous); ``a`` (U) / ``b`` (I): None is zeros.  Rank 0
+    is ``cu = ci = None`` with both ``a`` and ``b``.  ``row_blocks``: workgroups that share an item tile's user tiles,
+    0 for the launch's own choice; the scores do not depend on it.  A rank the kernel is not built for raises: there is
+    no other path behind this call (``lowrank_grid_supported`` says beforehand)."""
+    if (cu is None) != (ci is None):
+        raise ValueError("lowrank_grid_scores: cu and ci come together")
+    if cu is not None:
+        cu, ci = _mat(cu.detach(), "cu").contiguous(), _mat(ci.detach(), "ci").contiguous()
+        nu, ni, rank = cu.shape[0], ci.shape[0], cu.shape[1]
+        if ci.shape[1] != rank:
+            raise ValueError("lowrank_grid_scores: cu and ci differ in width")
+    else:
+        if a is None or b is None:
+            raise ValueError("lowrank_grid_scores: rank 0 needs both a and b")
+        nu, ni, rank = a.numel(), b.numel(), 0
+    if a is not None:
+        (a,) = _f32_vectors("lowrank_grid_scores", "a", a)
+    if b is not None:
+        (b,) = _f32_vectors("lowrank_grid_scores", "b", b)
+    if (a is not None and a.numel() != nu) or (b is not None and b.numel() != ni):
+        raise ValueError("lowrank_grid_scores: a holds one element per row of cu, b one per row of ci")
+    device = cu.device if cu is not None else a.device
+    user0, rows, out = _grid_rows("lowrank_grid_scores", users, user0, rows, nu, ni, out, device)
+    # algorithmic: every table row of the call read once (the user tiles re-read item rows from cache), the scores
+    # written; per pair the dot, the biases and the sigmoid
+    rc = _timed("lowrank_grid_scores",
+                lambda: (4 * ((rows + ni) * (rank + 1) + rows * ni) + (8 * rows if users is not None else 0),
+                         rows * ni * (2 * rank + 2)),
+                _lib.load().ctr_lowrank_grid_scores, cu.data_ptr() if rank else None, ci.data_ptr() if rank else None,
+                a.data_ptr() if a is not None else None, b.data_ptr() if b is not None else None, nu, ni, rank,
+                _lib.ptr(users) if users is not None and rows else None, user0, rows,
+                _lib.ptr(out) if out.numel() else None, _ld(out) if rows else ni, int(row_blocks), _lib.stream_ptr())
+    _lib.check(rc, "ctr_lowrank_grid_scores")
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Wide & Deep over the user x item grid (csrc/deepfm_grid.hip: the DeepFM template without its FM dot)
+# ---------------------------------------------------------------------------
+WIDEDEEP_GRID_HIDDEN = DEEPFM_GRID_HIDDEN   # hidden_units[1:]; hidden_units[0] is free (folded into the table rows)
+WIDEDEEP_GRID_ITEM_TILE = _lib.CTR_WIDEDEEP_GRID_ITEM_TILE
+WIDEDEEP_GRID_USER_TILE = _lib.CTR_WIDEDEEP_GRID_USER_TILE
+
+
+def widedeep_grid_supported(hidden_units) -> bool:
+    """whether ``ctr_widedeep_grid_scores`` takes a Wide & Deep of these ``hidden_units``, at any embedding width"""
+    hidden = tuple(int(h) for h in hidden_units)
+    return len(hidden) == 4 and hidden[0] >= 1 and hidden[1:] == WIDEDEEP_GRID_HIDDEN
+
+
+def widedeep_grid_scores(zu: torch.Tensor, zi: torch.Tensor, a: torch.Tensor, b: torch.Tensor, w2: torch.Tensor,
+                         b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, out_w: torch.Tensor, out_b: torch.Tensor,
+                         *, users: Optional[torch.Tensor] = None, user0: int = 0, rows: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None, row_blocks: int = 0) -> torch.Tensor:
+    """(rows, num_items) float32: ``sigmoid(out_w[0] (a[u] + b[i]) + out_w[1] relu(w3 . relu(w2 relu(zu[u] + zi[i]) +
+    b2) + b3) + out_b)`` for the users ``users`` (1-D int64, validated by the caller) or ``user0 .. user0 + rows``
+    against every item (ctr_widedeep_grid_scores): ``deepfm_grid_scores`` without ``su`` and ``si``.  A shape the kernel
+    is not built for raises: there is no other path behind this call (``widedeep_grid_supported`` says beforehand)."""
+    zu, zi, w2 = (_mat(t.detach(), w).contiguous() for t, w in ((zu, "zu"), (zi, "zi"), (w2, "w2")))
+    a, b, b2, w3, b3, out_w, out_b = _f32_vectors("widedeep_grid_scores", "a, b and the weights", a, b, b2, w3, b3,
+                                                  out_w, out_b)
+    nu, ni = zu.shape[0], zi.shape[0]
+    n2, n1 = w2.shape
+    if a.numel() != nu or b.numel() != ni:
+        raise ValueError("widedeep_grid_scores: the rows of a side differ in number")
+    if zu.shape[1] != n1 or zi.shape[1] != n1 or b2.numel() != n2 or w3.numel() != n2:
+        raise ValueError("widedeep_grid_scores: zu / zi must be as wide as a row of w2, b2 and w3 one element per unit "
+                         "of w2")
+    if b3.numel() != 1 or out_w.numel() != 2 or out_b.numel() != 1:
+        raise ValueError("widedeep_grid_scores: b3 and out_b hold one element, out_w two")
+    user0, rows, out = _grid_rows("widedeep_grid_scores", users, user0, rows, nu, ni, out, zu.device)
+    # algorithmic: as deepfm_grid_scores, without the FM rows and their dot
+    rc = _timed("widedeep_grid_scores",
+                lambda: (4 * ((rows + ni) * (n1 + 1) + rows * ni) + (8 * rows if users is not None else 0),
+                         rows * ni * (2 * n1 * n2 + n1 + 2 * n2)),
+                _lib.load().ctr_widedeep_grid_scores, zu.data_ptr(), zi.data_ptr(), a.data_ptr(), b.data_ptr(), nu, ni,
+                n1, n2, w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), out_w.data_ptr(), out_b.data_ptr(),
+                _lib.ptr(users) if users is not None and rows else None, user0, rows,
+                _lib.ptr(out) if out.numel() else None, _ld(out) if rows else ni, int(row_blocks), _lib.stream_ptr())
+    _lib.check(rc, "ctr_widedeep_grid_scores")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # feature interactions
 # ---------------------------------------------------------------------------
 USER_COL, ITEM_COL, DENSE_COL0, NUM_DENSE = 0, 1, 2, 43  # the (B,45) layout of data/reader.py:98-112

@@ -673,6 +673,43 @@ int ctr_afm_grid_scores(const float* su, const float* si, const float* fu, const
                         const float* att_h, const float* out_w, const int64_t* users /*nullable*/, int64_t user0,
                         int64_t rows, float* out, int64_t ldo, int row_blocks, void* stream);
 
+/* A biased low-rank product over the user x item grid (csrc/lowrank_grid.hip): the grid of MatrixFactorization, FFM and
+ * LogisticRegression, the scores of `rows` users against EVERY item in one launch:
+ *   out[r * ldo + i] = sigmoid((a[u_r] + b[i]) + sum_k cu[u_r * rank + k] ci[i * rank + k])
+ *   u_r = users[r] (users set: any order, repeats allowed) or user0 + r (users NULL; user0 + rows <= num_users)
+ * cu (num_users, rank) / ci (num_items, rank) dense row-major; a (num_users) / b (num_items) nullable: NULL is zeros.
+ * rank == 0 takes cu == ci == NULL and needs a or b.  The dot is ONE chain per pair on v_mfma_f32_32x32x2_f32 (exact
+ * f32, k ascending), then (a + b) + dot, then the sigmoid.  Admitted: rank 0 and every multiple of 16 up to 256,
+ * num_users and num_items < 2^31; anything else is CTR_ELIMIT.  A null pointer (cu or ci at rank != 0, both biases at
+ * rank 0, out), a negative count, ldo < num_items, row_blocks < 0 or a row range outside the user table is CTR_EINVAL;
+ * cu / ci not 16-byte aligned is CTR_EALIGN -- all before anything is enqueued, in that order.  rows == 0 or
+ * num_items == 0 enqueues nothing and returns CTR_OK.  Columns past num_items of a row of out are not touched.  A
+ * workgroup takes CTR_LOWRANK_GRID_ITEM_TILE items (a wave 32 of them) and walks user tiles of
+ * CTR_LOWRANK_GRID_USER_TILE rows: a wave's store instruction writes 128 contiguous bytes of two score rows.
+ * row_blocks > 0 is the number of workgroups that share an item tile's user tiles, 0 leaves it to the launch.  The
+ * caller validates `users`: an id outside [0, num_users) is clamped into the table, not reported.  No atomics; a pair's
+ * score is a function of its user's row, its item's row and the two biases alone, bitwise, whatever the rows, their
+ * order, the items' positions, ldo or row_blocks. */
+#define CTR_LOWRANK_GRID_ITEM_TILE 128
+#define CTR_LOWRANK_GRID_USER_TILE 32
+int ctr_lowrank_grid_scores(const float* cu /*nullable*/, const float* ci /*nullable*/, const float* a /*nullable*/,
+                            const float* b /*nullable*/, int64_t num_users, int64_t num_items, int rank,
+                            const int64_t* users /*nullable*/, int64_t user0, int64_t rows, float* out, int64_t ldo,
+                            int row_blocks, void* stream);
+
+/* Wide & Deep over the user x item grid (csrc/deepfm_grid.hip): ctr_deepfm_grid_scores without its FM dot -- the same
+ * kernel template, su / si and their stage compiled out:
+ *   out[r * ldo + i] = sigmoid(out_w[0] (a[u_r] + b[i]) + out_w[1] relu(w3 . relu(w2 relu(zu[u_r] + zi[i]) + b2) + b3[0])
+ *                              + out_b[0])
+ * Arguments, refusals (n1 == 256 and n2 == 128 only; zu / zi / w2 16-byte aligned), tiles and the bitwise contract as
+ * there. */
+#define CTR_WIDEDEEP_GRID_ITEM_TILE 128
+#define CTR_WIDEDEEP_GRID_USER_TILE 16
+int ctr_widedeep_grid_scores(const float* zu, const float* zi, const float* a, const float* b, int64_t num_users,
+                             int64_t num_items, int n1, int n2, const float* w2, const float* b2, const float* w3,
+                             const float* b3, const float* out_w, const float* out_b, const int64_t* users /*nullable*/,
+                             int64_t user0, int64_t rows, float* out, int64_t ldo, int row_blocks, void* stream);
+
 /* gy: gradient of the LAST layer's output; gx (nullable): gradient of x.  workspace is
  * required: (number of workgroups <= 256) * sum_i (n_i*k_i + n_i) floats. */
 int ctr_mlp_bwd(const float* x, int64_t ldx, int64_t m, const ctr_mlp_layer_t* layers, int nlayers,
