@@ -23,6 +23,7 @@ CTR_NCF_PROJ_MAX_ROWS = 16384
 CTR_NCF_PROJ_COUNT_STRIDE = 72
 CTR_ROWS1_MAX_ROWS = 32768
 CTR_GDCF_MAX_DIM = 256
+CTR_SOFTMAX_FULL_MAX_DIM = 256
 CTR_GROUP_MAX_K = 4095
 CTR_SCORE_CHUNK = 65536
 CTR_GAUC_SMALL = 64
@@ -250,6 +251,9 @@ SIGNATURES = {
     "ctr_gdcf_workspace_bytes": (_i, [_l, _l, _i, C.POINTER(C.c_int64)]),
     "ctr_gdcf_rows": (_i, [_p, _p, _l, _l, _i, _p, _l, _p, _p, _p, _l, _p]),
     "ctr_gdcf_cols": (_i, [_p, _p, _l, _l, _i, _p, _l, _p, _p, _p]),
+    "ctr_softmax_full_workspace_bytes": (_i, [_l, _l, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "ctr_softmax_full_rows": (_i, [_p, _p, _l, _l, _i, _p, _p, _p, _p, _i, _p, _l, _p, _p]),
+    "ctr_softmax_full_cols": (_i, [_p, _p, _l, _l, _i, _p, _p, _p, _p, _p, _i, _p, _l, _p]),
     "ctr_rank_filter": (_i, [_p, _l, _l, _l, _p, _p, _l, _p, _l, _p, _p, _p]),
     "ctr_rank_table_slots": (_i, [_l, _l, C.POINTER(C.c_int64)]),
     "ctr_rank_metrics_lists": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p]),

@@ -6,6 +6,7 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import ops, topn
+from .._lib import FIELD_ID_I64
 from ._base import CtrModule
 from ._grid import UserGridScorer
 
@@ -27,6 +28,44 @@ class _MFFunction(torch.autograd.Function):
         return gu, gi, None, None, None
 
 
+def _softmax_rows(user_table, item_table, user_idx, item_idx, err_flag, grad):
+    """gather the users' rows (the embedding stage's id lookup: a bad id reads row 0 and raises the flag) and run the
+    row pass of the full softmax: (x, nll, lse, gx_unit)"""
+    batch, dim = user_idx.numel(), user_table.shape[1]
+    x = torch.empty((batch, dim), dtype=torch.float32, device=user_table.device)
+    if batch:
+        spec = ops.FieldSpec(FIELD_ID_I64, dim, 0, table=user_table, idx=user_idx)
+        ops.embed_fwd([spec], None, batch, x, err_flag)
+    return (x,) + ops.softmax_full_rows(x, item_table, item_idx, grad=grad, err_flag=err_flag)
+
+
+class _SoftmaxNLLFunction(torch.autograd.Function):
+    """nll of the item against the whole catalogue (csrc/softmax_full.hip); the (B, I) logits are never written"""
+
+    @staticmethod
+    def forward(ctx, user_table, item_table, user_idx, item_idx, err_flag):
+        need_u, need_i = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        x, nll, lse, gx = _softmax_rows(user_table, item_table, user_idx, item_idx, err_flag, grad=need_u)
+        ctx.save_for_backward(user_table, item_table, user_idx, item_idx, x if need_i else None,
+                              lse if need_i else None, gx, nll if need_i else None)
+        return nll
+
+    @staticmethod
+    def backward(ctx, gnll):
+        user_table, item_table, user_idx, item_idx, x, lse, gx, nll = ctx.saved_tensors
+        gnll = gnll.contiguous()
+        gu = gi = None
+        if ctx.needs_input_grad[0]:
+            # dX = gnll[b] dX_unit[b], added to the users' rows of the dense gradient; a bad id adds to no row
+            rows = user_table.shape[0]
+            ok = (user_idx >= 0) & (user_idx < rows)
+            gu = ops.zero_grads([user_table])[id(user_table)]
+            gu.index_add_(0, user_idx.clamp(0, rows - 1), gx * (gnll * ok).unsqueeze(1))
+        if ctx.needs_input_grad[1]:
+            gi = ops.softmax_full_cols(x, item_table, item_idx, lse, gnll, nll=nll)
+        return gu, gi, None, None, None
+
+
 class MatrixFactorization(CtrModule):
     """``MatrixFactorization(num_users, num_items, embedding_size)``;
     ``forward(user_indices, item_indices) -> (B,)`` probabilities
@@ -44,6 +83,26 @@ class MatrixFactorization(CtrModule):
         self._need_device(w_u, user_indices, item_indices)
         out = _MFFunction.apply(w_u, w_i, user_indices.contiguous(), item_indices.contiguous(),
                                 self._err_flag(w_u.device))
+        self._raise_if_bad_index()
+        return out
+
+    def softmax_nll(self, user_indices: torch.Tensor, item_indices: torch.Tensor) -> torch.Tensor:
+        """``(B,)`` float32: the cross entropy of each pair's item against EVERY item of the catalogue under the
+        scores ``<user, item>`` (no sigmoid, no temperature, no bias, nothing excluded),
+        ``log sum_i exp(<p_u, q_i>) - <p_u, q_t>``.  No sampler and no logit matrix: two fused matrix-core passes
+        (DESIGN.md section 4r).  Under ``no_grad`` the same values bitwise: the held-out log-likelihood."""
+        w_u, w_i = self.user_embeddings.weight, self.item_embeddings.weight
+        self._need_device(w_u, user_indices, item_indices)
+        user_indices, item_indices = user_indices.contiguous(), item_indices.contiguous()
+        if user_indices.dim() != 1 or user_indices.shape != item_indices.shape or user_indices.dtype != torch.int64 \
+                or item_indices.dtype != torch.int64:
+            raise ValueError(f"softmax_nll: expected two (B,) int64 id tensors, got {tuple(user_indices.shape)} "
+                             f"{user_indices.dtype} and {tuple(item_indices.shape)} {item_indices.dtype}")
+        flag = self._err_flag(w_u.device)
+        if torch.is_grad_enabled() and (w_u.requires_grad or w_i.requires_grad):
+            out = _SoftmaxNLLFunction.apply(w_u, w_i, user_indices, item_indices, flag)
+        else:
+            out = _softmax_rows(w_u.detach(), w_i.detach(), user_indices, item_indices, flag, grad=False)[1]
         self._raise_if_bad_index()
         return out
 

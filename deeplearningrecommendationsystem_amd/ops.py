@@ -1955,6 +1955,96 @@ def gdcf_cols(p: torch.Tensor, q: torch.Tensor, yt: torch.Tensor, gout: torch.Te
 
 
 # ---------------------------------------------------------------------------
+# full softmax over the catalogue (csrc/softmax_full.hip): nll of a target item against every item; the B x I logits
+# are never written
+# ---------------------------------------------------------------------------
+SOFTMAX_FULL_MAX_DIM = _lib.CTR_SOFTMAX_FULL_MAX_DIM
+SOFTMAX_FULL_MAX_SPLITS = 64
+
+
+def _softmax_full_operands(x: torch.Tensor, q: torch.Tensor, target: torch.Tensor, splits: int):
+    _lib.require_device(x, q, target)
+    for t, name in ((x, "X"), (q, "Q")):
+        if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"softmax_full: {name} must be a contiguous 2-D float32 tensor, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+    if x.shape[1] != q.shape[1]:
+        raise ValueError(f"softmax_full: X has {x.shape[1]} columns, Q {q.shape[1]}")
+    k = x.shape[1]
+    if not 1 <= k <= SOFTMAX_FULL_MAX_DIM:
+        raise ValueError(f"softmax_full: k = {k} outside [1, {SOFTMAX_FULL_MAX_DIM}] (CTR_SOFTMAX_FULL_MAX_DIM)")
+    if q.shape[0] < 1:
+        raise ValueError("softmax_full: Q needs at least one row")
+    if target.dim() != 1 or target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != x.shape[0]:
+        raise ValueError(f"softmax_full: the targets must be a contiguous ({x.shape[0]},) int64 tensor, got "
+                         f"{tuple(target.shape)} {target.dtype}")
+    if not 0 <= int(splits) <= SOFTMAX_FULL_MAX_SPLITS:
+        raise ValueError(f"softmax_full: splits = {splits} outside [0, {SOFTMAX_FULL_MAX_SPLITS}]")
+    return k
+
+
+def _softmax_full_row_vector(t: torch.Tensor, batch: int, what: str) -> None:
+    _lib.require_device(t)
+    if t.dim() != 1 or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != batch:
+        raise ValueError(f"softmax_full: {what} must be a contiguous ({batch},) float32 tensor, got {tuple(t.shape)} "
+                         f"{t.dtype}")
+
+
+def _softmax_full_workspace(batch, num_items, k, splits_rows, splits_cols, device):
+    ws = C.c_int64()
+    _lib.check(_lib.load().ctr_softmax_full_workspace_bytes(batch, num_items, k, splits_rows, splits_cols,
+                                                             C.byref(ws)), "ctr_softmax_full_workspace_bytes")
+    return torch.empty(ws.value // 4, dtype=torch.float32, device=device) if ws.value else None, ws.value
+
+
+def softmax_full_rows(x: torch.Tensor, q: torch.Tensor, target: torch.Tensor, grad: bool = True, splits: int = 0,
+                      err_flag: Optional[torch.Tensor] = None):
+    """row pass: (nll, lse, gx_unit) for query rows ``x`` (B, k), the item table ``q`` (I, k) and ``target`` (B,)
+    int64: lse[b] = log sum_i exp(<x[b], q[i]>), nll = lse - <x[b], q[t_b]>, and gx_unit = softmax(z[b]) q - q[t_b],
+    the gradient of nll[b] by x[b] (``grad=False``: None).  A target outside [0, I) is never read: nll = lse for that
+    row and ``err_flag`` (device int32) is set.  ``splits``: parts the item range is cut into (0: automatic)."""
+    k = _softmax_full_operands(x, q, target, splits)
+    b, n = x.shape[0], q.shape[0]
+    nll = torch.empty(b, dtype=torch.float32, device=x.device)
+    lse = torch.empty(b, dtype=torch.float32, device=x.device)
+    gx = torch.empty_like(x) if grad else None
+    if b == 0:
+        return nll, lse, gx
+    ws, nbytes = _softmax_full_workspace(b, n, k, int(splits), 1, x.device)
+    rc = _timed("softmax_full_rows" if grad else "softmax_full_rows_loss",
+                lambda: (4 * (b * k + n * k) + 8 * b + 8 * b + (4 * b * k if grad else 0) + 2 * nbytes,
+                         (4 if grad else 2) * b * n * k),
+                _lib.load().ctr_softmax_full_rows, x.data_ptr(), q.data_ptr(), b, n, k, target.data_ptr(),
+                nll.data_ptr(), lse.data_ptr(), _lib.ptr(gx), int(splits), _lib.ptr(ws), nbytes, _lib.ptr(err_flag),
+                _lib.stream_ptr())
+    _lib.check(rc, "ctr_softmax_full_rows")
+    return nll, lse, gx
+
+
+def softmax_full_cols(x: torch.Tensor, q: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, gout: torch.Tensor,
+                      splits: int = 0, nll: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """column pass: dQ (I, k) = G^T x with G[b, i] = gout[b] (exp(<x[b], q[i]> - lse[b]) - [i == t_b]); ``lse`` from
+    the row pass, ``gout`` (B,) float32 the upstream gradient of nll, read on the device.  ``splits``: parts the batch
+    is cut into (0: automatic).  ``nll``: the row pass's, when at hand: a target's entry is then gout expm1(-nll),
+    which keeps its digits where the target's probability nears 1 (a float32 lse alone cannot)."""
+    k = _softmax_full_operands(x, q, target, splits)
+    b, n = x.shape[0], q.shape[0]
+    _softmax_full_row_vector(lse, b, "lse")
+    _softmax_full_row_vector(gout, b, "the upstream gradient")
+    if nll is not None:
+        _softmax_full_row_vector(nll, b, "nll")
+    if b == 0:
+        return torch.zeros_like(q)
+    gq = torch.empty_like(q)
+    ws, nbytes = _softmax_full_workspace(b, n, k, 1, int(splits), x.device)
+    rc = _timed("softmax_full_cols", lambda: (4 * (b * k + 2 * n * k) + 20 * b + 2 * nbytes, 4 * b * n * k),
+                _lib.load().ctr_softmax_full_cols, x.data_ptr(), q.data_ptr(), b, n, k, target.data_ptr(),
+                lse.data_ptr(), _lib.ptr(nll), gout.data_ptr(), gq.data_ptr(), int(splits), _lib.ptr(ws), nbytes, _lib.stream_ptr())
+    _lib.check(rc, "ctr_softmax_full_cols")
+    return gq
+
+
+# ---------------------------------------------------------------------------
 # top-k ranking evaluation (csrc/rank_eval.hip); the CSRs are (offsets (rows + 1), ids) int64 device tensors, the
 # offsets already sliced to the rows of the call (they index ``ids`` absolutely)
 # ---------------------------------------------------------------------------

@@ -821,6 +821,37 @@ int ctr_gdcf_cols(const float* p, const float* q, int64_t num_users, int64_t num
                   int64_t ldyt, const float* gout, float* grad_q, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Full softmax over the catalogue: the cross entropy of a target item against every item.  For query rows x
+ * (batch, k), an item table q (num_items, k) (both float32 row-major, leading dimension k) and target (batch) int64:
+ *   z[b, i] = <x[b], q[i]>,  lse[b] = log sum_i exp(z[b, i]),  nll[b] = lse[b] - z[b, t_b],
+ *   G[b, i] = gout[b] (exp(z[b, i] - lse[b]) - [i == t_b]),  dX = G q,  dQ = G^T x.
+ * No temperature, no item bias, no exclusion.  The batch x num_items logits are never written: two fused fp32
+ * matrix-core passes (running maximum: exp never sees a positive argument), no atomics, so every output is bitwise
+ * reproducible.  1 <= k <= CTR_SOFTMAX_FULL_MAX_DIM, batch and num_items < 2^31, splits <= 64 (CTR_ELIMIT beyond).
+ * A target outside [0, num_items) is never dereferenced: that row has no indicator term, nll = lse, and *err_flag
+ * (device int32, may be NULL) is set to 1.  An empty batch is CTR_OK and enqueues nothing.
+ *
+ * splits: into how many parts a pass cuts the range it streams (items for the rows, batch rows for the columns) so
+ * that small shapes fill the device; 0: chosen from (batch, num_items, k) and the CU count.  With more than one part
+ * the partials go to `workspace` (device, at least ctr_softmax_full_workspace_bytes for these splits; 1 needs none)
+ * and a second launch merges them in ascending part order.
+ * ctr_softmax_full_rows: nll and lse (batch) and, when grad_x is not NULL, grad_x (batch, k) = dX for gout = 1:
+ *   softmax(z[b]) q - q[t_b]; the caller scales it by its upstream gradient.
+ * ctr_softmax_full_cols: grad_q (num_items, k) = dQ from the lse of the row pass and gout (batch) float32.  nll (may be
+ *   NULL): the row pass's nll; with it a target's entry is gout expm1(-nll), exact where its probability nears 1 (a
+ *   float32 lse alone leaves it an error of half an ulp of lse there).
+ * ---------------------------------------------------------------------- */
+#define CTR_SOFTMAX_FULL_MAX_DIM 256
+int ctr_softmax_full_workspace_bytes(int64_t batch, int64_t num_items, int k, int splits_rows, int splits_cols,
+                                     int64_t* bytes /*host, out*/);
+int ctr_softmax_full_rows(const float* x, const float* q, int64_t batch, int64_t num_items, int k,
+                          const int64_t* target, float* nll, float* lse, float* grad_x, int splits, void* workspace,
+                          int64_t workspace_bytes, int32_t* err_flag, void* stream);
+int ctr_softmax_full_cols(const float* x, const float* q, int64_t batch, int64_t num_items, int k,
+                          const int64_t* target, const float* lse, const float* nll, const float* gout, float* grad_q,
+                          int splits, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Top-k ranking evaluation (evaluator/ranking.py: Ranking, and data/reader.py:137-159: remove_itemid).
  *
  * Id sets are CSRs over `rows` users: off (rows + 1, absolute into ids, device), ids (nnz, ascending within a row,
