@@ -2045,6 +2045,103 @@ def softmax_full_cols(x: torch.Tensor, q: torch.Tensor, target: torch.Tensor, ls
 
 
 # ---------------------------------------------------------------------------
+# ALS (csrc/als.hip): the row solves of implicit-feedback alternating least squares; no (rows, k, k) tensor exists
+# ---------------------------------------------------------------------------
+ALS_MAX_DIM = _lib.CTR_ALS_MAX_DIM
+ALS_ERR_INDEX, ALS_ERR_PIVOT = 1, 2
+
+
+def als_supported(k) -> bool:
+    """does ``als_gram`` / ``als_solve_rows`` take tables of ``k`` columns: a multiple of 16 in [16, ALS_MAX_DIM]"""
+    return isinstance(k, int) and not isinstance(k, bool) and 16 <= k <= ALS_MAX_DIM and k % 16 == 0
+
+
+def _als_table(y: torch.Tensor, what: str) -> int:
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous() or y.shape[0] < 1:
+        raise ValueError(f"als: {what} must be a contiguous 2-D float32 tensor with at least one row, got "
+                         f"{tuple(y.shape)} {y.dtype}")
+    k = int(y.shape[1])
+    if not als_supported(k):
+        raise ValueError(f"als: k = {k} is not a multiple of 16 in [16, {ALS_MAX_DIM}] (CTR_ALS_MAX_DIM)")
+    if y.shape[0] >= 1 << 31:
+        raise ValueError("als: a table must have fewer than 2^31 rows")
+    return k
+
+
+def als_gram_workspace_bytes(rows: int, k: int) -> int:
+    ws = C.c_int64()
+    _lib.check(_lib.load().ctr_als_gram_workspace_bytes(int(rows), int(k), C.byref(ws)), "ctr_als_gram_workspace_bytes")
+    return ws.value
+
+
+def als_gram(y: torch.Tensor) -> torch.Tensor:
+    """(k, k) float32 ``y^T y`` of a (rows, k) table: partials over fixed slabs of rows, added in ascending order, so
+    the result is bitwise reproducible"""
+    k = _als_table(y, "the table")
+    _lib.require_device(y)
+    rows = y.shape[0]
+    nbytes = als_gram_workspace_bytes(rows, k)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=y.device)
+    gram = torch.empty((k, k), dtype=torch.float32, device=y.device)
+    rc = _timed("als_gram", lambda: (4 * rows * k + 2 * nbytes + 4 * k * k, rows * k * (k + 16)),
+                _lib.load().ctr_als_gram, y.data_ptr(), rows, k, gram.data_ptr(), ws.data_ptr(), nbytes,
+                _lib.stream_ptr())
+    _lib.check(rc, "ctr_als_gram")
+    return gram
+
+
+def als_solve_rows(y: torch.Tensor, gram: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor, reg: float,
+                   alpha: float, rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   err_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(count, k) float32: for every CSR row ``rows[j]`` (``None``: all rows, in order) the solution x of
+    ``(gram + alpha sum_{i in list} y_i y_i^T + reg I) x = (1 + alpha) sum_{i in list} y_i`` over the (y_rows, k) table
+    ``y``; ``indptr`` (csr_rows + 1) int64 and ``indices`` int32 as ``ObservedPairs`` keeps them.  A row is a bitwise
+    function of its list, ``y``, ``gram``, ``reg`` and ``alpha`` alone.  ``out``: a (count, k) float32 tensor with unit
+    inner stride to write into.  ``err_flag`` (device int32, OR-ed into): ALS_ERR_INDEX for an index outside ``y`` (never
+    read), ALS_ERR_PIVOT for a pivot that is not positive and finite; such rows are zeros."""
+    k = _als_table(y, "the table")
+    _lib.require_device(y, gram, indptr, indices, rows, out, err_flag)
+    if gram.shape != (k, k) or gram.dtype != torch.float32 or not gram.is_contiguous():
+        raise ValueError(f"als: gram must be a contiguous ({k}, {k}) float32 tensor, got {tuple(gram.shape)} {gram.dtype}")
+    if indptr.dim() != 1 or indptr.dtype != torch.int64 or not indptr.is_contiguous() or indptr.numel() < 2:
+        raise ValueError("als: indptr must be a contiguous (csr_rows + 1,) int64 tensor")
+    if indices.dim() != 1 or indices.dtype != torch.int32 or not indices.is_contiguous():
+        raise ValueError("als: indices must be a contiguous 1-D int32 tensor")
+    csr_rows = indptr.numel() - 1
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int64 or not rows.is_contiguous()):
+        raise ValueError("als: rows must be a contiguous 1-D int64 tensor")
+    count = csr_rows if rows is None else rows.numel()
+    if count >= 1 << 31:
+        raise ValueError("als: at most 2^31 - 1 rows a call")
+    reg, alpha = float(reg), float(alpha)
+    if reg != reg or alpha != alpha:
+        raise ValueError("als: reg and alpha must be numbers")
+    if err_flag is not None and (err_flag.dtype != torch.int32 or err_flag.numel() != 1):
+        raise ValueError("als: err_flag must be one int32")
+    if out is None:
+        out = torch.empty((count, k), dtype=torch.float32, device=y.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape != (count, k) or \
+            (count > 0 and out.stride(1) != 1) or (count > 1 and out.stride(0) < k):
+        raise ValueError(f"als: out must be a ({count}, {k}) float32 tensor with unit inner stride")
+    if count == 0:
+        return out
+    ldo = out.stride(0) if count > 1 else k
+    nnz = indices.numel()
+
+    def meta():      # 2 k^2 per list entry of the rows solved plus k^3 / 3 per row; read only under a profiler
+        at = None if rows is None else rows.clamp(0, csr_rows - 1)
+        entries = nnz if rows is None else int((indptr[at + 1] - indptr[at]).sum())
+        return (4 * entries * (k + 1) + 16 * count + 4 * count * k + 4 * k * k,
+                2 * k * k * entries + count * (k ** 3) // 3)
+    rc = _timed("als_solve_rows", meta,
+                _lib.load().ctr_als_solve_rows, y.data_ptr(), y.shape[0], k, gram.data_ptr(), indptr.data_ptr(),
+                _lib.ptr(indices) if nnz else None, csr_rows, _lib.ptr(rows), count, reg, alpha, out.data_ptr(), ldo,
+                _lib.ptr(err_flag), _lib.stream_ptr())
+    _lib.check(rc, "ctr_als_solve_rows")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # top-k ranking evaluation (csrc/rank_eval.hip); the CSRs are (offsets (rows + 1), ids) int64 device tensors, the
 # offsets already sliced to the rows of the call (they index ``ids`` absolutely)
 # ---------------------------------------------------------------------------

@@ -852,6 +852,36 @@ int ctr_softmax_full_cols(const float* x, const float* q, int64_t batch, int64_t
                           int splits, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * ALS: implicit-feedback matrix factorisation by alternating least squares (Hu, Koren & Volinsky 2008).  With the
+ * other table y (y_rows, k) fixed (float32 row-major, leading dimension k, 16-byte aligned) and gram = y^T y, row u of
+ * a CSR (indptr (csr_rows + 1) int64, indices int32 rows of y, both on the device) gets the solution of
+ *   (gram + alpha * sum_{i in N(u)} y_i y_i^T + reg I) x_u = (1 + alpha) * sum_{i in N(u)} y_i,
+ * the minimiser of sum_i c_ui (p_ui - <x_u, y_i>)^2 + reg |x_u|^2 over ALL rows i of y with c = 1 + alpha on the
+ * listed rows (p = 1) and c = 1 elsewhere (p = 0).  An empty list gives exact zeros.
+ * k a multiple of 16 in [16, CTR_ALS_MAX_DIM], rows, y_rows and count < 2^31 (CTR_ELIMIT beyond).
+ *
+ * ctr_als_gram: gram (k, k) = y^T y, full and symmetric.  Partials over fixed slabs of rows go to `workspace` (device,
+ *   at least ctr_als_gram_workspace_bytes) and a second launch adds them in ascending slab order: no atomics, the
+ *   result is bitwise reproducible.
+ * ctr_als_solve_rows: out[j] (count rows, leading dimension ldo >= k) = x of CSR row rows[j] (rows NULL: row j).  One
+ *   workgroup per row: the k x k system is assembled on the fp32 matrix cores, factorised (Cholesky) and solved in
+ *   LDS; no workspace, no (count, k, k) tensor.  A result is a bitwise function of the row's list, y, gram, reg and
+ *   alpha alone -- not of which rows are asked for, in what order or how often.  Guards through *err_flag (device
+ *   int32, may be NULL, OR-ed into, never cleared): an index outside [0, y_rows), a row id outside [0, csr_rows) or a
+ *   row with indptr[u + 1] < indptr[u] is never dereferenced, sets bit 1 and that out row is zeros (the CSR is
+ *   otherwise trusted: the call carries no nnz, so offsets past the end of `indices` cannot be told); a pivot that
+ *   is not a positive finite number (reg = 0 on a singular system, a NaN in y) or a non-finite result sets bit 2 and
+ *   that out row is zeros.  No NaN or Inf is ever stored.  count == 0 is CTR_OK and enqueues nothing; a null pointer or a bad size is CTR_EINVAL before a launch.
+ * ---------------------------------------------------------------------- */
+#define CTR_ALS_MAX_DIM 128
+int ctr_als_gram_workspace_bytes(int64_t rows, int k, int64_t* bytes /*host, out*/);
+int ctr_als_gram(const float* y, int64_t rows, int k, float* gram, void* workspace, int64_t workspace_bytes,
+                 void* stream);
+int ctr_als_solve_rows(const float* y, int64_t y_rows, int k, const float* gram, const int64_t* indptr,
+                       const int32_t* indices, int64_t csr_rows, const int64_t* rows /* NULL: 0 .. count-1 */,
+                       int64_t count, float reg, float alpha, float* out, int64_t ldo, int32_t* err_flag, void* stream);
+
+/* ------------------------------------------------------------------------
  * Top-k ranking evaluation (evaluator/ranking.py: Ranking, and data/reader.py:137-159: remove_itemid).
  *
  * Id sets are CSRs over `rows` users: off (rows + 1, absolute into ids, device), ids (nnz, ascending within a row,
