@@ -22,70 +22,19 @@ dev/cf_bench.py left out, for MF and Wide & Deep.  Kernel times come from a sepa
     python dev/lowrank_grid_bench.py --recommend --stats-csv out/prof_lowrank_grid/<...>_kernel_stats.csv --out profiles/lowrank_grid_bench.json
 """
 import argparse
-import csv
-import json
-import os
 import statistics
 import sys
-import time
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from deeplearningrecommendationsystem_amd import model as zoo  # noqa: E402
-from deeplearningrecommendationsystem_amd import ops, synth  # noqa: E402
-from deeplearningrecommendationsystem_amd.data import FeatureAssembler, ObservedPairs  # noqa: E402
-from deeplearningrecommendationsystem_amd.model._base import CatalogueScorer  # noqa: E402
+from _bench import DEV, F32_MFMA_PEAK, STORE_PEAK, emit, need_gpu, observed_set, stats, timed  # first: it puts the repository root on sys.path
+from _bench import lowrank_kernel_sums as kernel_times
+from deeplearningrecommendationsystem_amd import model as zoo
+from deeplearningrecommendationsystem_amd import ops, synth
+from deeplearningrecommendationsystem_amd.data import FeatureAssembler
+from deeplearningrecommendationsystem_amd.model._base import CatalogueScorer
 
-DEV = "cuda:0"
-F32_MFMA_PEAK = 155e12
-STORE_PEAK = 6.0e12          # plain stores, MI355X_MICROARCH.md
 MF_RANK, FFM_RANK, WD_EMBED, WD_HIDDEN = 64, 32, 128, [512, 256, 128, 1]
-
-
-def observed_set(a):
-    rng = np.random.default_rng(0)                                   # the observed set of dev/cf_bench.py
-    pop = 1.0 / np.arange(1, a.items + 1)
-    pop = pop[rng.permutation(a.items)]
-    u = torch.from_numpy(rng.integers(0, a.users, a.pairs)).to(DEV)
-    i = torch.from_numpy(rng.choice(a.items, size=a.pairs, p=pop / pop.sum())).to(DEV)
-    return ObservedPairs(u, i, a.users, a.items)
-
-
-def timed(fn, calls=1):
-    """seconds per call of ``calls`` back-to-back calls that end in one device synchronise"""
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / calls
-
-
-def stats(ts):
-    return {"median_ms": statistics.median(ts) * 1e3, "min_ms": min(ts) * 1e3, "max_ms": max(ts) * 1e3}
-
-
-def kernel_times(path):
-    """the kernels of an --only-kernels run: the library's by name (template arguments kept), torch's fill and sigmoid"""
-    out = {}
-    with open(path, newline="") as f:
-        for row in csv.DictReader(f):
-            name = row["Name"]
-            if "(anonymous namespace)::" in name and "at::native" not in name:
-                name = name.split("(anonymous namespace)::")[1].split("(")[0]
-            elif "FillFunctor" in name:
-                name = "torch_fill"
-            elif "sigmoid" in name.lower():
-                name = "torch_sigmoid_"
-            else:
-                continue
-            prev = out.get(name, {"calls": 0, "total_ms": 0.0})
-            calls, total = prev["calls"] + int(row["Calls"]), prev["total_ms"] + float(row["TotalDurationNs"]) / 1e6
-            out[name] = {"calls": calls, "total_ms": total, "average_us": total * 1e3 / calls}
-    return out
 
 
 def build(a):
@@ -107,6 +56,24 @@ def mf_before(net, rows):
         return ops.linear_fwd(net.user_embeddings.weight[:rows], net.item_embeddings.weight, None).sigmoid_()
 
 
+def grid_kernels(pairs, store_floor_s, kernels):
+    """the ``grid_kernels`` entries from ``kernels_rocprofv3``; ``store_floor_s`` is the median window of leg (d), seconds a call"""
+    out, score_bytes = {}, 4 * pairs
+    for name, v in kernels.items():
+        sec = v["average_us"] * 1e-6
+        if name.startswith("lowrank_grid_scores_kernel"):
+            rank = 16 * int(name.split("<")[1].split(">")[0])
+            out[name] = {"rank": rank, "average_us": v["average_us"], "pairs_per_s": pairs / sec,
+                         "score_bytes_per_s": score_bytes / sec, "share_of_plain_store_peak": score_bytes / sec / STORE_PEAK,
+                         "mfma_tflops": 2 * rank * pairs / sec / 1e12,
+                         "share_of_fp32_mfma_peak": 2 * rank * pairs / sec / F32_MFMA_PEAK,
+                         "share_of_store_floor_window": store_floor_s / sec}
+        elif name.startswith("deepfm_grid_scores_kernel"):
+            out[name] = {"average_us": v["average_us"], "pairs_per_s": pairs / sec,
+                         "share_of_fp32_mfma_peak": 2 * 256 * 128 * pairs / sec / F32_MFMA_PEAK}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=138_493)
@@ -120,8 +87,7 @@ def main():
     ap.add_argument("--stats-csv", help="rocprofv3 --stats kernel CSV of an --only-kernels run, merged into the result")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("lowrank_grid_bench.py needs the GPU: there is nothing to measure without one")
+    need_gpu("lowrank_grid_bench.py")
     nets, asm = build(a)
     rows, pairs = a.rows, a.rows * a.items
     score_bytes = 4 * pairs
@@ -181,28 +147,11 @@ def main():
             wall = timed(lambda: scorer.recommend(n=20, exclude=observed))
             res["recommend_all_users_n20"][name] = {"wall_s": wall, "pairs_per_s": a.users * a.items / wall}
     if a.stats_csv:
-        k = kernel_times(a.stats_csv)
-        res["kernels_rocprofv3"] = k
-        for name, v in k.items():
-            if name.startswith("lowrank_grid_scores_kernel"):
-                rank = 16 * int(name.split("<")[1].split(">")[0])
-                sec = v["average_us"] * 1e-6
-                entry = {"rank": rank, "average_us": v["average_us"], "pairs_per_s": pairs / sec,
-                         "score_bytes_per_s": score_bytes / sec, "share_of_plain_store_peak": score_bytes / sec / STORE_PEAK,
-                         "mfma_tflops": 2 * rank * pairs / sec / 1e12,
-                         "share_of_fp32_mfma_peak": 2 * rank * pairs / sec / F32_MFMA_PEAK}
-                entry["share_of_store_floor_window"] = med["store_floor"] / sec
-                res.setdefault("grid_kernels", {})[name] = entry
-            elif name.startswith("deepfm_grid_scores_kernel"):
-                sec = v["average_us"] * 1e-6
-                res.setdefault("grid_kernels", {})[name] = {
-                    "average_us": v["average_us"], "pairs_per_s": pairs / sec,
-                    "share_of_fp32_mfma_peak": 2 * 256 * 128 * pairs / sec / F32_MFMA_PEAK}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        res["kernels_rocprofv3"] = kernel_times(a.stats_csv)
+        entries = grid_kernels(pairs, med["store_floor"], res["kernels_rocprofv3"])
+        if entries:
+            res["grid_kernels"] = entries
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

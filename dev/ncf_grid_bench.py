@@ -18,58 +18,27 @@ the 155 TF fp32 matrix-core rate, comes from a separate run under the profiler:
     python dev/ncf_grid_bench.py --stats-csv out/prof_ncf_grid/<...>_kernel_stats.csv --out profiles/ncf_grid_bench.json
 """
 import argparse
-import csv
-import json
-import os
 import statistics
 import sys
-import time
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from deeplearningrecommendationsystem_amd import model as zoo  # noqa: E402
-from deeplearningrecommendationsystem_amd.data import ObservedPairs  # noqa: E402
+from _bench import DEV, F32_MFMA_PEAK, emit, need_gpu, observed_set, stats, timed  # first: it puts the repository root on sys.path
+from _bench import library_kernel_rows as kernel_times
+from deeplearningrecommendationsystem_amd import model as zoo
 
-DEV = "cuda:0"
-F32_MFMA_PEAK = 155e12
 TOWER_FLOP_PER_PAIR = 2 * (64 * 32 + 32 * 16 + 16 * 8)      # 5376: the three layers the kernel runs per pair
 
 
-def observed_set(a):
-    rng = np.random.default_rng(0)                                   # the observed set of dev/cf_bench.py
-    pop = 1.0 / np.arange(1, a.items + 1)
-    pop = pop[rng.permutation(a.items)]
-    u = torch.from_numpy(rng.integers(0, a.users, a.pairs)).to(DEV)
-    i = torch.from_numpy(rng.choice(a.items, size=a.pairs, p=pop / pop.sum())).to(DEV)
-    return ObservedPairs(u, i, a.users, a.items)
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0
-
-
-def stats(ts):
-    return {"median_ms": statistics.median(ts) * 1e3, "min_ms": min(ts) * 1e3, "max_ms": max(ts) * 1e3}
-
-
-def kernel_times(path):
-    """the library's kernels of an --only-kernels run: the grid kernel, and whatever the forward leg's chunks ran"""
-    out = {}
-    with open(path, newline="") as f:
-        for row in csv.DictReader(f):
-            if "(anonymous namespace)::" in row["Name"] and "at::native" not in row["Name"]:
-                name = row["Name"].split("(anonymous namespace)::")[1].split("(")[0].split("<")[0]
-                out[name] = {"calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) / 1e6,
-                             "average_us": float(row["AverageNs"]) / 1e3, "min_us": float(row["MinNs"]) / 1e3,
-                             "max_us": float(row["MaxNs"]) / 1e3}
-    return out
+def grid_kernel(pairs, kernels):
+    """the ``grid_kernel`` entry from ``kernels_rocprofv3``; None where the grid kernel is not in it"""
+    entry = None
+    for name, v in kernels.items():
+        if "ncf_grid_scores_kernel" in name:
+            flops = TOWER_FLOP_PER_PAIR * pairs / (v["average_us"] * 1e-6)
+            entry = {"average_us": v["average_us"], "tower_tflops": flops / 1e12,
+                     "share_of_fp32_mfma_peak": flops / F32_MFMA_PEAK, "pairs_per_s": pairs / (v["average_us"] * 1e-6)}
+    return entry
 
 
 def main():
@@ -85,8 +54,7 @@ def main():
     ap.add_argument("--stats-csv", help="rocprofv3 --stats kernel CSV of an --only-kernels run, merged into the result")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("ncf_grid_bench.py needs the GPU: there is nothing to measure without one")
+    need_gpu("ncf_grid_bench.py")
     torch.manual_seed(1234)
     with torch.device(DEV):
         net = zoo.NeuralCF(a.users, a.items, 64, [128, 64, 32, 16, 8]).eval()
@@ -134,19 +102,11 @@ def main():
         res["recommend_all_users_n20"] = {"wall_s": t, "observed_pairs": len(observed), "pairs_scored": a.users * ni,
                                           "pairs_per_s": a.users * ni / t}
     if a.stats_csv:
-        k = kernel_times(a.stats_csv)
-        res["kernels_rocprofv3"] = k
-        for name, v in k.items():
-            if "ncf_grid_scores_kernel" in name:
-                flops = TOWER_FLOP_PER_PAIR * pairs / (v["average_us"] * 1e-6)
-                res["grid_kernel"] = {"average_us": v["average_us"], "tower_tflops": flops / 1e12,
-                                      "share_of_fp32_mfma_peak": flops / F32_MFMA_PEAK,
-                                      "pairs_per_s": pairs / (v["average_us"] * 1e-6)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        res["kernels_rocprofv3"] = kernel_times(a.stats_csv)
+        entry = grid_kernel(pairs, res["kernels_rocprofv3"])
+        if entry:
+            res["grid_kernel"] = entry
+    emit(res, a.out)
 
 
 if __name__ == "__main__":
