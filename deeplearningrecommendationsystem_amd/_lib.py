@@ -258,6 +258,8 @@ SIGNATURES = {
     "ctr_als_gram_workspace_bytes": (_i, [_l, _i, C.POINTER(C.c_int64)]),
     "ctr_als_gram": (_i, [_p, _l, _i, _p, _p, _l, _p]),
     "ctr_als_solve_rows": (_i, [_p, _l, _i, _p, _p, _p, _l, _p, _l, _f, _f, _p, _l, _p, _p]),
+    "ctr_als_solve_rows_weighted": (_i, [_p, _l, _i, _p, _p, _p, _p, _l, _p, _l, _f, _f, _f, _f, _f, _f, _p, _l, _p,
+                                         _p]),
     "ctr_rank_filter": (_i, [_p, _l, _l, _l, _p, _p, _l, _p, _l, _p, _p, _p]),
     "ctr_rank_table_slots": (_i, [_l, _l, C.POINTER(C.c_int64)]),
     "ctr_rank_metrics_lists": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p]),

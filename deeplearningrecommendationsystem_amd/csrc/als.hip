@@ -25,6 +25,20 @@
 //   alone, so a result is a bitwise function of (list, Y, G, reg, alpha): not of which rows are asked for, in what
 //   order, how often, or of the grid.
 //
+//   als_solve_rows_weighted : the same frame for per-entry weights from a values array aligned with the CSR,
+//         (G + sum_e w_e y_e y_e^T + (reg + reg_per_entry n) I) x = sum_e t_e y_e,   w_e = fmaf(w1, v_e, w0),
+//         t_e = fmaf(t1, v_e, t0), n the list length, G = gram or 0 (confidences c = 1 + alpha v: (0, alpha, 1, alpha);
+//         explicit ratings, Zhou et al. 2008: no G, (1, 0, 0, 1), reg_per_entry).  The chunk's 32 values are read by
+//         32 threads beside the row loads (in flight under the products, as the rows are), turned into w_e and t_e
+//         (one fused multiply-add each) when the rows are stored, and staged in LDS with them; entries past the end
+//         of the list carry w = t = 0 and are not read.  w_e scales ONE
+//         operand of each product, the A-side read: lane (r, q) feeds entry 4 step + q, so it keeps the eight weights
+//         of its entries in registers for the chunk (two 16-byte LDS reads, the same address over a (., q) group).
+//         (w x_a) x_b and x_a (w x_b) round differently, so S is well defined only because every tile on or below the
+//         diagonal is formed once and nothing above the diagonal is ever read by (c).  The column sum is
+//         sum_e t_e x_e.  Every sum still runs in list order: a row is a bitwise function of (list, values, Y, G, the
+//         six scalars).  A non-finite value or scalar ends in the guards below: a zero row and bit 2.
+//
 // Guards, none of which traps: a CSR index outside [0, y_rows) (or a row id outside the CSR, or a row whose offsets run
 // backwards) is never dereferenced, sets bit 1 of *err_flag and gives a zero row; a pivot that is not a positive finite number, or a non-finite result,
 // sets bit 2 and gives a zero row.  No NaN or Inf is ever stored.  The flag is OR-ed with the only atomic of the file,
@@ -82,11 +96,25 @@ struct Tiles {
   __device__ __forceinline__ bool live(int i, int wave) const { return wave + kWaves * i < Geo<KB>::NT; }
 };
 
-// S += X^T X and the column sums over n gathered rows; row_of(e): the address of entry e's row of Y, or nullptr for a
-// row that counts as zeros.  On return every wave's tiles are in acc, a thread's column-sum share in cs, and the stage
-// buffers are dead (the last product is behind a barrier).
-template <int KB, typename RowOf>
-__device__ __forceinline__ void als_accumulate(int64_t n, RowOf row_of, float* __restrict__ stage,
+// the per-entry weights of als_accumulate.  NoWeights: every entry counts once, nothing is staged or multiplied.
+struct NoWeights {
+  static constexpr bool kOn = false;
+};
+// Weights: entry e of the row counts with w_e = fmaf(w1, values[e], w0) in S and t_e = fmaf(t1, values[e], t0) in the
+// column sum.  lds: 2 buffers of 2 kChunk floats, 16-byte aligned; a buffer holds w of entry e at (e % 4) * 8 + e / 4
+// -- the eight weights of lane group q are contiguous -- and t of entry e at kChunk + e.
+struct Weights {
+  static constexpr bool kOn = true;
+  const float* values;   // of the row: values[e] for e < n, nothing beyond is read
+  float w0, w1, t0, t1;
+  float* lds;
+};
+
+// S += X^T W X and the column sums sum_e t_e x_e over n gathered rows (W = I, t = 1 without weights); row_of(e): the
+// address of entry e's row of Y, or nullptr for a row that counts as zeros.  On return every wave's tiles are in acc,
+// a thread's column-sum share in cs, and the stage buffers are dead (the last product is behind a barrier).
+template <int KB, typename RowOf, typename Wt>
+__device__ __forceinline__ void als_accumulate(int64_t n, RowOf row_of, const Wt& wt, float* __restrict__ stage,
                                                const Tiles<KB>& tiles, f32x4 (&acc)[Geo<KB>::TPW], float& cs) {
   using G = Geo<KB>;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -94,6 +122,10 @@ __device__ __forceinline__ void als_accumulate(int64_t n, RowOf row_of, float* _
   const int64_t chunks = (n + kChunk - 1) / kChunk;
 
   f32x4 stg[G::kVecPer];
+  // the value of entry c * kChunk + tid (tid < kChunk) and whether the list has that entry; the value stays a load in
+  // flight until store() turns it into w and t, as the rows do
+  [[maybe_unused]] float val = 0.0f;
+  [[maybe_unused]] bool val_live = false;
   auto load = [&](int64_t c) {
 #pragma unroll
     for (int i = 0; i < G::kVecPer; ++i) {
@@ -105,6 +137,13 @@ __device__ __forceinline__ void als_accumulate(int64_t n, RowOf row_of, float* _
         if (src) stg[i] = *(const CTR_GLOBAL f32x4*)(src + 4 * (v % G::K4));
       }
     }
+    if constexpr (Wt::kOn) {
+      if (tid < kChunk) {
+        const int64_t e = c * kChunk + tid;
+        val_live = e < n;
+        if (val_live) val = wt.values[e];
+      }
+    }
   };
   auto store = [&](int buf) {
 #pragma unroll
@@ -112,6 +151,13 @@ __device__ __forceinline__ void als_accumulate(int64_t n, RowOf row_of, float* _
       const int v = tid + kThreads * i;
       if (v < G::kVec)
         *reinterpret_cast<f32x4*>(stage + buf * kChunk * G::XS + (v / G::K4) * G::XS + 4 * (v % G::K4)) = stg[i];
+    }
+    if constexpr (Wt::kOn) {
+      if (tid < kChunk) {
+        float* wb = wt.lds + buf * 2 * kChunk;
+        wb[(tid & 3) * (kChunk / 4) + (tid >> 2)] = val_live ? fmaf(wt.w1, val, wt.w0) : 0.0f;
+        wb[kChunk + tid] = val_live ? fmaf(wt.t1, val, wt.t0) : 0.0f;
+      }
     }
   };
 
@@ -126,19 +172,41 @@ __device__ __forceinline__ void als_accumulate(int64_t n, RowOf row_of, float* _
     const bool more = c + 1 < chunks;
     if (more) load(c + 1);
     const float* xb = stage + buf * kChunk * G::XS;
+    if constexpr (Wt::kOn) {
+      const float* wb = wt.lds + buf * 2 * kChunk;
+      const f32x4 w03 = *reinterpret_cast<const f32x4*>(wb + q * (kChunk / 4));       // entries q, 4 + q, 8 + q, 12 + q
+      const f32x4 w47 = *reinterpret_cast<const f32x4*>(wb + q * (kChunk / 4) + 4);   // ... 16 + q .. 28 + q
+      const float w[kChunk / 4] = {w03[0], w03[1], w03[2], w03[3], w47[0], w47[1], w47[2], w47[3]};
 #pragma unroll
-    for (int i = 0; i < G::TPW; ++i) {
-      if (tiles.live(i, wave)) {
-        const float* pa = xb + q * G::XS + 16 * tiles.ta[i] + r;
-        const float* pb = xb + q * G::XS + 16 * tiles.tb[i] + r;
+      for (int i = 0; i < G::TPW; ++i) {
+        if (tiles.live(i, wave)) {
+          const float* pa = xb + q * G::XS + 16 * tiles.ta[i] + r;
+          const float* pb = xb + q * G::XS + 16 * tiles.tb[i] + r;
 #pragma unroll
-        for (int s = 0; s < kChunk / 4; ++s) acc[i] = mfma4(pa[4 * s * G::XS], pb[4 * s * G::XS], acc[i]);
+          for (int s = 0; s < kChunk / 4; ++s) acc[i] = mfma4(w[s] * pa[4 * s * G::XS], pb[4 * s * G::XS], acc[i]);
+        }
       }
-    }
-    if (cs_group < G::kGroups) {
-      const float* pc = xb + cs_group * G::kPerGroup * G::XS + cs_col;
+      if (cs_group < G::kGroups) {
+        const float* pc = xb + cs_group * G::kPerGroup * G::XS + cs_col;
+        const float* pt = wb + kChunk + cs_group * G::kPerGroup;
 #pragma unroll
-      for (int e = 0; e < G::kPerGroup; ++e) cs += pc[e * G::XS];
+        for (int e = 0; e < G::kPerGroup; ++e) cs = fmaf(pt[e], pc[e * G::XS], cs);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < G::TPW; ++i) {
+        if (tiles.live(i, wave)) {
+          const float* pa = xb + q * G::XS + 16 * tiles.ta[i] + r;
+          const float* pb = xb + q * G::XS + 16 * tiles.tb[i] + r;
+#pragma unroll
+          for (int s = 0; s < kChunk / 4; ++s) acc[i] = mfma4(pa[4 * s * G::XS], pb[4 * s * G::XS], acc[i]);
+        }
+      }
+      if (cs_group < G::kGroups) {
+        const float* pc = xb + cs_group * G::kPerGroup * G::XS + cs_col;
+#pragma unroll
+        for (int e = 0; e < G::kPerGroup; ++e) cs += pc[e * G::XS];
+      }
     }
     if (more) store(buf ^ 1);
     __syncthreads();
@@ -162,7 +230,7 @@ __global__ __launch_bounds__(kThreads) void als_gram_slab_kernel(const float* __
 #pragma unroll
   for (int i = 0; i < G::TPW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   float cs = 0.0f;
-  als_accumulate<KB>(n, [&](int64_t e) { return Y + (row0 + e) * G::K; }, stage, tiles, acc, cs);
+  als_accumulate<KB>(n, [&](int64_t e) { return Y + (row0 + e) * G::K; }, NoWeights{}, stage, tiles, acc, cs);
   float* part = ws + (int64_t)blockIdx.x * G::K * G::K;
 #pragma unroll
   for (int i = 0; i < G::TPW; ++i) {
@@ -188,10 +256,23 @@ __global__ __launch_bounds__(kThreads) void als_gram_merge_kernel(const float* _
 // ---------------------------------------------------------------------------------------------------------------
 // row solves
 // ---------------------------------------------------------------------------------------------------------------
-template <int KB>
+// the scalars of one launch.  Unit: A = gram + alpha S + reg I, b = (1 + alpha) s.  Weighted: the weights are already
+// in S and s, A = (gram or 0) + S + (reg + reg_per_entry n) I, b = s.
+struct UnitSystem {
+  static constexpr bool kWeighted = false;
+  float reg, alpha;
+};
+struct WeightedSystem {
+  static constexpr bool kWeighted = true;
+  const float* values;   // aligned with indices
+  float w0, w1, t0, t1, reg, reg_per_entry;
+};
+
+// one kernel text, two families of instantiations that differ in `sys` alone
+template <int KB, typename Sys>
 __global__ __launch_bounds__(kThreads) void als_solve_rows_kernel(
     const float* __restrict__ Y, int64_t y_rows, const float* __restrict__ gram, const int64_t* __restrict__ indptr,
-    const int32_t* __restrict__ indices, int64_t csr_rows, const int64_t* __restrict__ rows, float reg, float alpha,
+    const int32_t* __restrict__ indices, int64_t csr_rows, const int64_t* __restrict__ rows, const Sys sys,
     float* __restrict__ out, int64_t ldo, int32_t* __restrict__ err_flag) {
   using G = Geo<KB>;
   constexpr int K = G::K, LDA = G::LDA;
@@ -236,19 +317,36 @@ __global__ __launch_bounds__(kThreads) void als_solve_rows_kernel(
         }
         return Y + id * K;
       },
+      [&] {
+        if constexpr (Sys::kWeighted) {
+          __shared__ __attribute__((aligned(16))) float s_wt[2 * 2 * kChunk];
+          return Weights{sys.values + p0, sys.w0, sys.w1, sys.t0, sys.t1, s_wt};
+        } else {
+          return NoWeights{};
+        }
+      }(),
       smem, tiles, acc, cs);
   if (bad_index) s_err = kErrIndex;   // every writer stores the same value
 
   // (b) the stage buffers are dead: A takes their place
   float* A = smem;
+  [[maybe_unused]] float diag = 0.0f;
+  if constexpr (Sys::kWeighted) diag = fmaf(sys.reg_per_entry, (float)n, sys.reg);
 #pragma unroll
   for (int i = 0; i < G::TPW; ++i) {
     if (tiles.live(i, wave)) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int ai = 16 * tiles.ta[i] + 4 * q + c, aj = 16 * tiles.tb[i] + r;
-        float v = fmaf(alpha, acc[i][c], gram[ai * K + aj]);
-        if (ai == aj) v += reg;
+        float v;
+        if constexpr (Sys::kWeighted) {
+          v = acc[i][c];
+          if (gram) v += gram[ai * K + aj];
+          if (ai == aj) v += diag;
+        } else {
+          v = fmaf(sys.alpha, acc[i][c], gram[ai * K + aj]);
+          if (ai == aj) v += sys.reg;
+        }
         A[ai * LDA + aj] = v;
       }
     }
@@ -259,7 +357,8 @@ __global__ __launch_bounds__(kThreads) void als_solve_rows_kernel(
     float s = 0.0f;
 #pragma unroll
     for (int g = 0; g < G::kGroups; ++g) s += s_cs[g * K + tid];
-    A[K * LDA + tid] = (1.0f + alpha) * s;
+    if constexpr (!Sys::kWeighted) s = (1.0f + sys.alpha) * s;
+    A[K * LDA + tid] = s;
   }
 
   // (c) A = L L^T by blocks of 16; row K becomes y
@@ -425,10 +524,36 @@ extern "C" int ctr_als_solve_rows(const float* y, int64_t y_rows, int k, const f
                   aligned_to(rows, 8) && aligned_to(out, 4) && aligned_to(err_flag, 4),
               CTR_EALIGN);
   hipStream_t s = (hipStream_t)stream;
-#define ALS_SOLVE(KB)                                                                                               \
-  hipLaunchKernelGGL((als_solve_rows_kernel<KB>), dim3((unsigned)count), dim3(kThreads), 0, s, y, y_rows, gram,     \
-                     indptr, indices, csr_rows, rows, reg, alpha, out, ldo, err_flag)
+  const UnitSystem sys{reg, alpha};
+#define ALS_SOLVE(KB)                                                                                             \
+  hipLaunchKernelGGL((als_solve_rows_kernel<KB, UnitSystem>), dim3((unsigned)count), dim3(kThreads), 0, s, y,     \
+                     y_rows, gram, indptr, indices, csr_rows, rows, sys, out, ldo, err_flag)
   ALS_CASES(ALS_SOLVE)
 #undef ALS_SOLVE
+  return ctr_launch_status();
+}
+
+extern "C" int ctr_als_solve_rows_weighted(const float* y, int64_t y_rows, int k, const float* gram,
+                                           const int64_t* indptr, const int32_t* indices, const float* values,
+                                           int64_t csr_rows, const int64_t* rows, int64_t count, float w0, float w1,
+                                           float t0, float t1, float reg, float reg_per_entry, float* out, int64_t ldo,
+                                           int32_t* err_flag, void* stream) {
+  CTR_REQUIRE(count >= 0 && y_rows >= 1 && csr_rows >= 1 && k >= 1, CTR_EINVAL);
+  if (count == 0) return CTR_OK;
+  // indices may be NULL: a CSR without a single pair, the only one that may come without values; gram may be NULL
+  CTR_REQUIRE(y && indptr && out && ldo >= k && (values || !indices), CTR_EINVAL);
+  CTR_REQUIRE(w0 == w0 && w1 == w1 && t0 == t0 && t1 == t1 && reg == reg && reg_per_entry == reg_per_entry,
+              CTR_EINVAL);
+  CTR_REQUIRE(dim_ok(k) && count < (1ll << 31) && y_rows < (1ll << 31), CTR_ELIMIT);
+  CTR_REQUIRE(aligned_to(y, 16) && aligned_to(gram, 4) && aligned_to(indptr, 8) && aligned_to(indices, 4) &&
+                  aligned_to(values, 4) && aligned_to(rows, 8) && aligned_to(out, 4) && aligned_to(err_flag, 4),
+              CTR_EALIGN);
+  hipStream_t s = (hipStream_t)stream;
+  const WeightedSystem sys{values, w0, w1, t0, t1, reg, reg_per_entry};
+#define ALS_SOLVE_W(KB)                                                                                           \
+  hipLaunchKernelGGL((als_solve_rows_kernel<KB, WeightedSystem>), dim3((unsigned)count), dim3(kThreads), 0, s, y, \
+                     y_rows, gram, indptr, indices, csr_rows, rows, sys, out, ldo, err_flag)
+  ALS_CASES(ALS_SOLVE_W)
+#undef ALS_SOLVE_W
   return ctr_launch_status();
 }

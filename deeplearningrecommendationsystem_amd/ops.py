@@ -2141,6 +2141,68 @@ def als_solve_rows(y: torch.Tensor, gram: torch.Tensor, indptr: torch.Tensor, in
     return out
 
 
+def als_solve_rows_weighted(y: torch.Tensor, gram: Optional[torch.Tensor], indptr: torch.Tensor, indices: torch.Tensor,
+                            values: torch.Tensor, w, t, reg: float, reg_per_entry: float = 0.0,
+                            rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                            err_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``als_solve_rows`` with a weight per list entry: ``values`` (nnz,) float32 is aligned with ``indices`` and, with
+    ``w = (w0, w1)``, ``t = (t0, t1)``, ``w_e = fma(w1, v_e, w0)``, ``t_e = fma(t1, v_e, t0)`` and n the row's list
+    length, a row solves ``(gram + sum_e w_e y_e y_e^T + (reg + reg_per_entry n) I) x = sum_e t_e y_e``; ``gram=None``:
+    no dense part.  Confidences ``1 + alpha v``: ``w = (0, alpha)``, ``t = (1, alpha)``; explicit ratings with the
+    regulariser weighted by the list length: ``gram=None``, ``w = (1, 0)``, ``t = (0, 1)``, ``reg=0``,
+    ``reg_per_entry``.  A row is a bitwise function of its list, its values, ``y``, ``gram`` and the six scalars alone.
+    ``rows``, ``out`` and ``err_flag`` as in ``als_solve_rows``; a non-finite value gives a zero row and ALS_ERR_PIVOT."""
+    k = _als_table(y, "the table")
+    if gram is not None and (gram.shape != (k, k) or gram.dtype != torch.float32 or not gram.is_contiguous()):
+        raise ValueError(f"als: gram must be None or a contiguous ({k}, {k}) float32 tensor, got {tuple(gram.shape)} "
+                         f"{gram.dtype}")
+    if indptr.dim() != 1 or indptr.dtype != torch.int64 or not indptr.is_contiguous() or indptr.numel() < 2:
+        raise ValueError("als: indptr must be a contiguous (csr_rows + 1,) int64 tensor")
+    if indices.dim() != 1 or indices.dtype != torch.int32 or not indices.is_contiguous():
+        raise ValueError("als: indices must be a contiguous 1-D int32 tensor")
+    if values.dim() != 1 or values.dtype != torch.float32 or not values.is_contiguous() or \
+            values.numel() != indices.numel():
+        raise ValueError("als: values must be a contiguous 1-D float32 tensor of the length of indices")
+    csr_rows = indptr.numel() - 1
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int64 or not rows.is_contiguous()):
+        raise ValueError("als: rows must be a contiguous 1-D int64 tensor")
+    count = csr_rows if rows is None else rows.numel()
+    if count >= 1 << 31:
+        raise ValueError("als: at most 2^31 - 1 rows a call")
+    try:
+        (w0, w1), (t0, t1) = (float(v) for v in w), (float(v) for v in t)
+    except (TypeError, ValueError):
+        raise ValueError("als: w and t must be pairs of numbers (w0, w1), (t0, t1)") from None
+    reg, reg_per_entry = float(reg), float(reg_per_entry)
+    if any(v != v for v in (w0, w1, t0, t1, reg, reg_per_entry)):
+        raise ValueError("als: w, t, reg and reg_per_entry must be numbers")
+    if err_flag is not None and (err_flag.dtype != torch.int32 or err_flag.numel() != 1):
+        raise ValueError("als: err_flag must be one int32")
+    _lib.require_device(y, gram, indptr, indices, values, rows, out, err_flag)      # after what needs no device to tell
+    if out is None:
+        out = torch.empty((count, k), dtype=torch.float32, device=y.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape != (count, k) or \
+            (count > 0 and out.stride(1) != 1) or (count > 1 and out.stride(0) < k):
+        raise ValueError(f"als: out must be a ({count}, {k}) float32 tensor with unit inner stride")
+    if count == 0:
+        return out
+    ldo = out.stride(0) if count > 1 else k
+    nnz = indices.numel()
+
+    def meta():      # als_solve_rows' with 4 B more read per entry; the dense part only where there is one
+        at = None if rows is None else rows.clamp(0, csr_rows - 1)
+        entries = nnz if rows is None else int((indptr[at + 1] - indptr[at]).sum())
+        return (4 * entries * (k + 2) + 16 * count + 4 * count * k + (4 * k * k if gram is not None else 0),
+                2 * k * k * entries + count * (k ** 3) // 3)
+    rc = _timed("als_solve_rows_weighted", meta,
+                _lib.load().ctr_als_solve_rows_weighted, y.data_ptr(), y.shape[0], k, _lib.ptr(gram),
+                indptr.data_ptr(), _lib.ptr(indices) if nnz else None, _lib.ptr(values) if nnz else None, csr_rows,
+                _lib.ptr(rows), count, w0, w1, t0, t1, reg, reg_per_entry, out.data_ptr(), ldo, _lib.ptr(err_flag),
+                _lib.stream_ptr())
+    _lib.check(rc, "ctr_als_solve_rows_weighted")
+    return out
+
+
 # ---------------------------------------------------------------------------
 # top-k ranking evaluation (csrc/rank_eval.hip); the CSRs are (offsets (rows + 1), ids) int64 device tensors, the
 # offsets already sliced to the rows of the call (they index ``ids`` absolutely)

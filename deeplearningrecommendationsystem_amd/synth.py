@@ -107,3 +107,27 @@ def implicit_split(num_users: int = NUM_USERS_ML100K, num_items: int = NUM_ITEMS
     test_u, test_i = torch.nonzero(test, as_tuple=True)
     assert bool(taken.any(1).all()) and bool(taken.any(0).all())
     return train_u, train_i, test_u, test_i
+
+
+def valued_split(seed: int = 5, rank: int = 8, noise: float = 0.5, **split):
+    """``implicit_split(seed=seed, **split)`` with a value on every pair, from a seeded affinity
+    ``a_ui = <f_u, g_i>`` of unit variance (``rank`` factors) plus N(0, ``noise``^2): play counts
+    ``1 + floor(exp(a + e))`` (float32, >= 1, heavy-tailed) on the training pairs and ratings
+    ``clip(round(3 + a + e'), 1, 5)`` on both splits.  Returns 0-based int64 ids and float32 values
+    ``(train_users, train_items, train_counts, train_ratings, test_users, test_items, test_ratings)``."""
+    train_u, train_i, test_u, test_i = implicit_split(seed=seed, **split)
+    num_users, num_items = int(train_u.max()) + 1, int(train_i.max()) + 1      # every user and item is in training
+    gen = generator(seed + 1000)
+    f = torch.randn(num_users, rank, generator=gen, dtype=torch.float64)
+    g = torch.randn(num_items, rank, generator=gen, dtype=torch.float64) / rank ** 0.5
+
+    def affinity(u, i):
+        return (f[u] * g[i]).sum(1), torch.randn(u.numel(), generator=gen, dtype=torch.float64) * noise
+
+    a, e = affinity(train_u, train_i)
+    counts = (1.0 + torch.floor(torch.exp(a + e))).float()
+    _, e = affinity(train_u, train_i)
+    ratings = torch.clamp(torch.round(3.0 + a + e), 1.0, 5.0).float()
+    a, e = affinity(test_u, test_i)
+    test_ratings = torch.clamp(torch.round(3.0 + a + e), 1.0, 5.0).float()
+    return train_u, train_i, counts, ratings, test_u, test_i, test_ratings

@@ -881,6 +881,25 @@ int ctr_als_solve_rows(const float* y, int64_t y_rows, int k, const float* gram,
                        const int32_t* indices, int64_t csr_rows, const int64_t* rows /* NULL: 0 .. count-1 */,
                        int64_t count, float reg, float alpha, float* out, int64_t ldo, int32_t* err_flag, void* stream);
 
+/* ctr_als_solve_rows_weighted: the same row solve with a weight per list entry.  values (nnz float32, device) is
+ * aligned with indices; entry e of a row of n entries counts with w_e = fmaf(w1, v_e, w0) and t_e = fmaf(t1, v_e, t0):
+ *   (G + sum_e w_e y_e y_e^T + (reg + reg_per_entry * n) I) x = sum_e t_e y_e,      G = gram, or 0 when gram is NULL.
+ *   confidences c = 1 + alpha v (Hu et al.):  gram,  (w0, w1, t0, t1) = (0, alpha, 1, alpha),  reg
+ *   explicit ratings, weighted-lambda (Zhou et al. 2008):  gram NULL,  (1, 0, 0, 1),  reg_per_entry
+ *   the unit system above, with v = 1:  gram,  (alpha, 0, 1 + alpha, 0),  reg   (not bitwise ctr_als_solve_rows)
+ * Arguments, limits, the one-workgroup-per-row frame, the guards and the meaning of the err_flag bits are those of
+ * ctr_als_solve_rows.  A row is a bitwise function of its list, its values, y, gram and the six scalars alone.
+ * Nothing at or past indptr[u + 1] is read, neither an index nor a value.  A non-finite value or scalar reaches the
+ * pivot / finite guard: bit 2 and a zero row, no NaN or Inf is stored.  A negative w_e is the caller's business; an
+ * indefinite system is caught by the pivot guard.  An empty list gives exact zeros whatever the scalars are.
+ * Refusals before a launch: CTR_EINVAL for values NULL where indices is not (indices NULL: a CSR without a pair), a
+ * NaN scalar, ldo < k or a null y / indptr / out; CTR_ELIMIT for k; count == 0 is CTR_OK and enqueues nothing. */
+int ctr_als_solve_rows_weighted(const float* y, int64_t y_rows, int k, const float* gram /* NULL: no dense part */,
+                                const int64_t* indptr, const int32_t* indices, const float* values, int64_t csr_rows,
+                                const int64_t* rows /* NULL: 0 .. count-1 */, int64_t count, float w0, float w1,
+                                float t0, float t1, float reg, float reg_per_entry, float* out, int64_t ldo,
+                                int32_t* err_flag, void* stream);
+
 /* ------------------------------------------------------------------------
  * Top-k ranking evaluation (evaluator/ranking.py: Ranking, and data/reader.py:137-159: remove_itemid).
  *
