@@ -338,6 +338,16 @@ int ctr_gru_fused_bwd(const float* x, int64_t ldx, const float* w_ih, const floa
  * <= 128, every n <= 128, k[i] == n[i-1], weights 16-byte aligned, intermediate
  * outputs 16-byte aligned with ldy % 4 == 0.  Anything else returns CTR_ELIMIT /
  * CTR_EALIGN without enqueueing; use ctr_linear_* layer by layer then.
+ * Which code: CTR_ELIMIT for a shape the kernels are not built for (more than 8
+ * layers, n or k above 128, k not a multiple of 8, a stack that does not fit LDS,
+ * more than 16 dW tiles of 32 x 32 in the backward, fewer workspace floats than
+ * the backward needs, head: p above 64, p not a multiple of 8, p + n_last above 192);
+ * CTR_EALIGN for x, an intermediate y or the head's x off a 16-byte boundary or
+ * with a leading dimension that is no multiple of 4.  A stack that no path could
+ * run is CTR_EINVAL, also without enqueueing: k < 8, k[i] != n[i-1], a null w or y,
+ * ldy < n, w off a 16-byte boundary, an unknown activation, and in the backward a
+ * layer without gw or gb (gb is required even where the forward's b was NULL).
+ * m == 0 is CTR_OK and enqueues nothing.
  * ---------------------------------------------------------------------- */
 typedef struct ctr_mlp_layer {
   const float* w;   /* (n, k) row-major */
