@@ -25,6 +25,8 @@ CTR_ROWS1_MAX_ROWS = 32768
 CTR_GDCF_MAX_DIM = 256
 CTR_SOFTMAX_FULL_MAX_DIM = 256
 CTR_ALS_MAX_DIM = 128
+CTR_GRAPH_MAX_DIM = 256
+CTR_GRAPH_SEGMENT = 512
 CTR_GROUP_MAX_K = 4095
 CTR_SCORE_CHUNK = 65536
 CTR_GAUC_SMALL = 64
@@ -260,6 +262,9 @@ SIGNATURES = {
     "ctr_als_solve_rows": (_i, [_p, _l, _i, _p, _p, _p, _l, _p, _l, _f, _f, _p, _l, _p, _p]),
     "ctr_als_solve_rows_weighted": (_i, [_p, _l, _i, _p, _p, _p, _p, _l, _p, _l, _f, _f, _f, _f, _f, _f, _p, _l, _p,
                                          _p]),
+    "ctr_graph_propagate_workspace_bytes": (_i, [_l, _i, C.POINTER(C.c_int64)]),
+    "ctr_graph_propagate": (_i, [_p, _l, _l, _i, _p, _p, _l, _l, _p, _p, _p, _l, _p, _l, _p, _l, _p, _l, _p, _l, _p,
+                                 _p]),
     "ctr_rank_filter": (_i, [_p, _l, _l, _l, _p, _p, _l, _p, _l, _p, _p, _p]),
     "ctr_rank_table_slots": (_i, [_l, _l, C.POINTER(C.c_int64)]),
     "ctr_rank_metrics_lists": (_i, [_p, _l, _p, _l, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p]),

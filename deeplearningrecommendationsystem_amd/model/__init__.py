@@ -16,5 +16,6 @@ from .lr import LogisticRegression
 from .nfm import NFM
 from .afm import AFM
 from .autorec import AutoRec
+from .lightgcn import LightGCN
 
-__all__ = ["MatrixFactorization", "NeuralCF", "DeepFM", "PNN", "FFM", "DeepCrossing", "DIN", "DIEN", "EmbeddingStage", "DeepCross", "WideDeep", "LogisticRegression", "NFM", "AFM", "AutoRec"]
+__all__ = ["MatrixFactorization", "NeuralCF", "DeepFM", "PNN", "FFM", "DeepCrossing", "DIN", "DIEN", "EmbeddingStage", "DeepCross", "WideDeep", "LogisticRegression", "NFM", "AFM", "AutoRec", "LightGCN"]

@@ -2204,6 +2204,168 @@ def als_solve_rows_weighted(y: torch.Tensor, gram: Optional[torch.Tensor], indpt
 
 
 # ---------------------------------------------------------------------------
+# graph propagation (csrc/graph_prop.hip): the CSR row sum of LightGCN; its backward is itself over the transposed CSR
+# ---------------------------------------------------------------------------
+GRAPH_MAX_DIM = _lib.CTR_GRAPH_MAX_DIM
+GRAPH_SEGMENT = _lib.CTR_GRAPH_SEGMENT     # a list is cut every GRAPH_SEGMENT entries from its own start
+GRAPH_ERR_INDEX, GRAPH_ERR_PLAN = 1, 2
+
+
+def graph_supported(k) -> bool:
+    """does ``graph_propagate`` take tables of ``k`` columns: a multiple of 16 in [16, GRAPH_MAX_DIM], the ranks
+    ``lowrank_grid_scores`` takes"""
+    return isinstance(k, int) and not isinstance(k, bool) and 16 <= k <= GRAPH_MAX_DIM and k % 16 == 0
+
+
+def _graph_indptr(indptr) -> int:
+    if not isinstance(indptr, torch.Tensor) or indptr.dim() != 1 or indptr.dtype != torch.int64 or \
+            not indptr.is_contiguous() or indptr.numel() < 2:
+        raise ValueError("graph: indptr must be a contiguous (num_rows + 1,) int64 tensor")
+    if indptr.numel() - 1 >= 1 << 31:
+        raise ValueError("graph: a CSR must have fewer than 2^31 rows")
+    return indptr.numel() - 1
+
+
+class GraphPlan:
+    """what an all-rows ``graph_propagate`` over one CSR needs from the host, built once (``graph_plan``): the work
+    items by descending list length, the segments of rows longer than GRAPH_SEGMENT as items of their own, the rows to
+    merge and the number of workspace slots.  Results do not depend on it."""
+
+    __slots__ = ("indptr", "num_rows", "work", "merge", "slots")
+
+    def __init__(self, indptr, num_rows, work, merge, slots):
+        self.indptr, self.num_rows, self.work, self.merge, self.slots = indptr, num_rows, work, merge, slots
+
+
+def graph_plan(indptr: torch.Tensor) -> GraphPlan:
+    """the plan of ``graph_propagate(..., rows=None)`` over the CSR with these offsets: one device-to-host sync here,
+    none in the calls that use it"""
+    num_rows = _graph_indptr(indptr)
+    _lib.require_device(indptr)
+    dev = indptr.device
+    length = indptr.diff()
+    order = torch.argsort(length, descending=True, stable=True)
+    nseg = ((length[order] + (GRAPH_SEGMENT - 1)) // GRAPH_SEGMENT).clamp_(min=1)
+    split = nseg > 1
+    slot_count = nseg * split
+    slot0 = slot_count.cumsum(0) - slot_count                    # first slot of a split row
+    first = nseg.cumsum(0) - nseg                                # first item of a row
+    nwork, slots, nsplit = torch.stack((nseg.sum(), slot_count.sum(), split.sum())).tolist()      # the sync
+    if nwork >= 1 << 31:
+        raise ValueError("graph: the CSR has 2^31 or more work items")
+    seg = torch.arange(nwork, device=dev) - torch.repeat_interleave(first, nseg, output_size=nwork)
+    slot = torch.where(torch.repeat_interleave(split, nseg, output_size=nwork),
+                       torch.repeat_interleave(slot0, nseg, output_size=nwork) + seg, -1)
+    work = torch.stack((torch.repeat_interleave(order, nseg, output_size=nwork), seg, slot, torch.zeros_like(seg)),
+                       dim=1).to(torch.int32).contiguous()
+    # the split rows are the longest: the first nsplit of the order
+    merge = torch.stack((order[:nsplit], slot0[:nsplit]), dim=1).to(torch.int32).contiguous() if nsplit else None
+    return GraphPlan(indptr, num_rows, work, merge, slots)
+
+
+def graph_workspace_bytes(slots: int, k: int) -> int:
+    ws = C.c_int64()
+    _lib.check(_lib.load().ctr_graph_propagate_workspace_bytes(int(slots), int(k), C.byref(ws)),
+               "ctr_graph_propagate_workspace_bytes")
+    return ws.value
+
+
+def _graph_scale(t, n, what):
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != (n,) or
+                          not t.is_contiguous()):
+        raise ValueError(f"graph: {what} must be a contiguous ({n},) float32 tensor or None")
+
+
+def graph_propagate(x: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor,
+                    scale_in: Optional[torch.Tensor] = None, scale_out: Optional[torch.Tensor] = None,
+                    rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    plan: Optional[GraphPlan] = None, err_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(count, k) float32: for every CSR row ``r = rows[j]`` (``None``: all rows, in order)
+    ``out[j] = scale_out[r] * sum_{e in list(r)} scale_in[indices[e]] * x[indices[e]]`` over the (x_rows, k) table
+    ``x`` (unit inner stride, a row stride that is a multiple of 4, 16-byte aligned); ``indptr`` (num_rows + 1) int64
+    and ``indices`` int32 as ``ObservedPairs`` keeps them; a scale that is ``None`` is ones.  A row is a bitwise
+    function of its list, the rows of ``x`` it names and the two scales alone: not of ``rows``, of ``plan`` or of the
+    run.  ``plan`` (``graph_plan(indptr)``, all-rows calls only) orders the work by list length and splits long lists
+    over waves.  ``out``: a (count, k) float32 tensor to write into, same layout rules as ``x``.  ``err_flag`` (device
+    int32, OR-ed into): GRAPH_ERR_INDEX for an index outside ``x`` (never read, it adds nothing); without an
+    ``err_flag`` the call reads a flag of its own (one sync) and raises ``IndexError``."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] < 1:
+        raise ValueError("graph: x must be a 2-D float32 tensor with at least one row")
+    x_rows, k = int(x.shape[0]), int(x.shape[1])
+    if not graph_supported(k):
+        raise ValueError(f"graph: k = {k} is not a multiple of 16 in [16, {GRAPH_MAX_DIM}] (CTR_GRAPH_MAX_DIM)")
+    if x_rows >= 1 << 31:
+        raise ValueError("graph: a table must have fewer than 2^31 rows")
+
+    def layout(t, n, what):
+        if t.stride(1) != 1 or (n > 1 and (t.stride(0) < k or t.stride(0) % 4)) or t.data_ptr() % 16:
+            raise ValueError(f"graph: {what} needs unit inner stride, a row stride that is a multiple of 4 and at "
+                             f"least {k}, and 16-byte alignment")
+        return t.stride(0) if n > 1 else k
+    ldx = layout(x, x_rows, "x")
+    num_rows = _graph_indptr(indptr)
+    if not isinstance(indices, torch.Tensor) or indices.dim() != 1 or indices.dtype != torch.int32 or \
+            not indices.is_contiguous():
+        raise ValueError("graph: indices must be a contiguous 1-D int32 tensor")
+    nnz = indices.numel()
+    if nnz >= 1 << 31:
+        raise ValueError("graph: a CSR must have fewer than 2^31 entries")
+    _graph_scale(scale_in, x_rows, "scale_in")
+    _graph_scale(scale_out, num_rows, "scale_out")
+    if rows is not None and (not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.dtype != torch.int64 or
+                             not rows.is_contiguous()):
+        raise ValueError("graph: rows must be a contiguous 1-D int64 tensor")
+    count = num_rows if rows is None else rows.numel()
+    if count >= 1 << 31:
+        raise ValueError("graph: at most 2^31 - 1 rows a call")
+    if plan is not None:
+        if not isinstance(plan, GraphPlan):
+            raise ValueError("graph: plan must come from graph_plan()")
+        if rows is not None:
+            raise ValueError("graph: a plan covers all rows in order; pass rows or a plan, not both")
+        if plan.num_rows != num_rows or plan.indptr.data_ptr() != indptr.data_ptr():
+            raise ValueError("graph: the plan was built for another CSR")
+    if err_flag is not None and (err_flag.dtype != torch.int32 or err_flag.numel() != 1):
+        raise ValueError("graph: err_flag must be one int32")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or
+                            out.shape != (count, k)):
+        raise ValueError(f"graph: out must be a ({count}, {k}) float32 tensor")
+    ldo = k if out is None or count == 0 else layout(out, count, "out")
+    _lib.require_device(x, indptr, indices, scale_in, scale_out, rows, out, err_flag)
+    if out is None:
+        out = torch.empty((count, k), dtype=torch.float32, device=x.device)
+    if count == 0:
+        return out
+    flag = err_flag if err_flag is not None else torch.zeros(1, dtype=torch.int32, device=x.device)
+    work = merge = ws = None
+    nbytes = 0
+    if plan is not None:
+        work, merge = plan.work, plan.merge
+        if plan.slots:
+            nbytes = graph_workspace_bytes(plan.slots, k)
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+
+    def meta():      # a gathered row and an index per entry, the out rows, the partials written and read back
+        at = None if rows is None else rows.clamp(0, num_rows - 1)
+        entries = nnz if rows is None else int((indptr[at + 1] - indptr[at]).sum())
+        return 4 * entries * (k + 1) + 4 * count * (k + 4) + 2 * nbytes, 2 * entries * k
+    rc = _timed("graph_propagate", meta,
+                _lib.load().ctr_graph_propagate, x.data_ptr(), x_rows, ldx, k, indptr.data_ptr(),
+                _lib.ptr(indices) if nnz else None, num_rows, nnz, _lib.ptr(scale_in), _lib.ptr(scale_out),
+                _lib.ptr(rows), count, _lib.ptr(work), 0 if work is None else work.shape[0], _lib.ptr(merge),
+                0 if merge is None else merge.shape[0], out.data_ptr(), ldo, _lib.ptr(ws), nbytes, flag.data_ptr(),
+                _lib.stream_ptr())
+    _lib.check(rc, "ctr_graph_propagate")
+    if err_flag is None:
+        bits = int(flag.item())
+        if bits & GRAPH_ERR_INDEX:
+            raise IndexError("graph: an index of the CSR is outside the table it indexes (or a row is outside the CSR)")
+        if bits:
+            raise RuntimeError(f"graph: the plan does not fit the call (error bits {bits:#x})")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # top-k ranking evaluation (csrc/rank_eval.hip); the CSRs are (offsets (rows + 1), ids) int64 device tensors, the
 # offsets already sliced to the rows of the call (they index ``ids`` absolutely)
 # ---------------------------------------------------------------------------

@@ -60,6 +60,10 @@ class Adam(torch.optim.Optimizer):
                 todo.append((p, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"]))
             if rows:
                 sparse.adam_rows(rows, group["lr"], group["betas"], group["eps"], group["weight_decay"], step)
+            # the launches write through raw pointers: tell autograd, as an in-place torch op would (what is keyed by a
+            # parameter's ``_version``, like LightGCN's propagation cache, must see the step)
+            for p, *_ in rows + todo:
+                torch.autograd.graph.increment_version(p)
             if not todo:
                 continue
             arr = (_lib.AdamTensor * len(todo))()

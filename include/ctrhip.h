@@ -911,6 +911,47 @@ int ctr_als_solve_rows_weighted(const float* y, int64_t y_rows, int k, const flo
                                 int32_t* err_flag, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Graph propagation (LightGCN, He et al. 2020): a sparse-times-dense row sum over a CSR.  For every requested row
+ *   out[j, :] = s_out[r] * sum_{e in [indptr[r], indptr[r+1])} s_in[indices[e]] * x[indices[e], :],    r = rows[j]
+ * x (x_rows, k) float32 with leading dimension ldx; indptr (num_rows + 1) int64 and indices (nnz) int32 as the other
+ * CSR entries take them; s_in (x_rows) and s_out (num_rows) float32, either NULL: ones; rows (count) int64, NULL: the
+ * rows 0 .. count-1; out (count, k) with leading dimension ldo.  k a multiple of 16 in [16, CTR_GRAPH_MAX_DIM];
+ * x_rows, num_rows, nnz, count, nwork and nmerge < 2^31 (CTR_ELIMIT beyond); x, out and workspace 16-byte aligned, ldx
+ * and ldo multiples of 4 (CTR_EALIGN otherwise).
+ *
+ * One wave sums one work item in registers, 16-byte loads per lane, the source scale read per entry and applied by one
+ * fused multiply-add; a lane without an entry adds nothing.  A list is cut every CTR_GRAPH_SEGMENT entries counted
+ * from its own start; segment sums are added in ascending segment order and the total is scaled once.  There is no
+ * float atomic, and out[j] is a bitwise function of the row's list, the source rows it names and the two scales -- not
+ * of which rows are asked for, of their order, of the plan, of the launch geometry or of the run.  An empty list gives
+ * exact zeros.  Source rows that no list names are never read.
+ *
+ * The plan (all of it optional, device memory, built once per CSR by the caller):
+ *   work  (nwork, 4) int32: (out row j, segment s, workspace slot, 0).  slot < 0: the wave walks the whole row and
+ *         writes out[j]; slot >= 0: the wave sums segment s alone into slot `slot` of the workspace (k floats a slot).
+ *         NULL (nwork = 0): every out row is one whole-row item.  Items run in the order given: longest rows first.
+ *   merge (nmerge, 2) int32: (out row j, first slot): out[j] = s_out * (slot + slot+1 + ...), one slot per segment of
+ *         the row, in a second launch.  Every row whose items carry slots must be listed here once.
+ *   workspace: at least ctr_graph_propagate_workspace_bytes(slots, k) bytes; may be NULL where nmerge == 0.
+ * Guards through *err_flag (device int32, may be NULL, OR-ed into, never cleared), none of which traps: an index
+ * outside [0, x_rows) is never dereferenced, adds nothing and sets bit 1, other rows are unaffected; a row id outside
+ * [0, num_rows) or offsets that run backwards or past nnz give a zero row and bit 1; a work or merge item that names
+ * an out row outside [0, count) or slots outside the workspace is skipped and sets bit 2.
+ * Refusals before a launch: CTR_EINVAL for a null x / indptr / out, indices NULL with nnz > 0, a negative size,
+ * ldx < k or ldo < k, work or merge NULL with a non-zero length (or the reverse), nmerge > 0 without work and
+ * workspace; then CTR_ELIMIT; then CTR_EALIGN.  count == 0 is CTR_OK and enqueues nothing.
+ * ---------------------------------------------------------------------- */
+#define CTR_GRAPH_MAX_DIM 256
+#define CTR_GRAPH_SEGMENT 512
+int ctr_graph_propagate_workspace_bytes(int64_t partials, int k, int64_t* bytes /*host, out*/);
+int ctr_graph_propagate(const float* x, int64_t x_rows, int64_t ldx, int k, const int64_t* indptr,
+                        const int32_t* indices, int64_t num_rows, int64_t nnz, const float* s_in /* NULL: ones */,
+                        const float* s_out /* NULL: ones */, const int64_t* rows /* NULL: 0 .. count-1 */,
+                        int64_t count, const int32_t* work, int64_t nwork, const int32_t* merge, int64_t nmerge,
+                        float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, int32_t* err_flag,
+                        void* stream);
+
+/* ------------------------------------------------------------------------
  * Top-k ranking evaluation (evaluator/ranking.py: Ranking, and data/reader.py:137-159: remove_itemid).
  *
  * Id sets are CSRs over `rows` users: off (rows + 1, absolute into ids, device), ids (nnz, ascending within a row,
