@@ -18,10 +18,18 @@ LIB_PATH = os.environ.get("CTRHIP_LIB", os.path.join(_HERE, "libctrhip.so"))  # 
 ABI_VERSION = 36
 DIN_TRIPLE, DIN_PAIR, DIN_H = 0, 1, 2  # layouts of the DIN attention operand (include/ctrhip.h)
 
+# every integer `#define CTR_*` of include/ctrhip.h that Python reads, once, under the header's name (tests/test_abi.py
+# holds each to the header)
+CTR_ELIMIT, CTR_EALIGN = -2, -4
 CTR_MAX_FIELDS = 32
 CTR_NCF_PROJ_MAX_ROWS = 16384
 CTR_NCF_PROJ_COUNT_STRIDE = 72
 CTR_ROWS1_MAX_ROWS = 32768
+CTR_TOPK_MAX_K = 4096
+CTR_CF_KNN_MAX_K = 64
+CTR_RANK_MAX_ROWS = 1 << 24
+CTR_RANK_MASK_BITS = 0xFFFFFFFF
+CTR_RANK_ERR_OFFSETS, CTR_RANK_ERR_LENGTH, CTR_RANK_ERR_SURVIVOR, CTR_RANK_ERR_COUNT = 1, 2, 4, 8
 CTR_GDCF_MAX_DIM = 256
 CTR_SOFTMAX_FULL_MAX_DIM = 256
 CTR_ALS_MAX_DIM = 128

@@ -31,7 +31,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import ops, topn
+from . import _lib, ops, topn
 from .data import Interactions, ObservedPairs
 from .model._grid import UserGridScorer
 
@@ -111,11 +111,11 @@ class ALS:
             raise ValueError("sweeps must not be negative")
         self._check(observed)
         if isinstance(observed, Interactions):
-            ops._lib.require_device(self.P, observed.values)
+            _lib.require_device(self.P, observed.values)
             self._users = _Side(observed)
             self._items = _Side(observed.transpose())
         else:
-            ops._lib.require_device(self.P, observed.indptr)
+            _lib.require_device(self.P, observed.indptr)
             users, items = _pairs_of(observed)
             self._users = _Side(observed)
             self._items = _Side(ObservedPairs(items, users, self.num_items, self.num_users))
@@ -176,7 +176,7 @@ class ALS:
 
     def _solve(self, side: _Side, fixed, rows):
         if self._flag is None:
-            ops._lib.require_device(fixed)
+            _lib.require_device(fixed)
             self._flag = torch.zeros(1, dtype=torch.int32, device=fixed.device)
         pairs = side.pairs
         if self.objective == "explicit":      # observed cells only: no Gram launch, reg times the list length

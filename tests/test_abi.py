@@ -244,7 +244,36 @@ def test_python_mirrors_of_header_limits_match(lib):
     limit changed in the header alone would send admitted shapes to a library that refuses them"""
     from deeplearningrecommendationsystem_amd import ops
     text = open(os.path.join(ROOT, "include", "ctrhip.h")).read()
-    defines = {k: int(v) for k, v in re.findall(r"^#define (CTR_[A-Z0-9_]+) (\d+)\b", text, flags=re.M)}
+    defines = _header_defines(text)
     for name in ("CTR_MAX_FIELDS", "CTR_NCF_PROJ_MAX_ROWS", "CTR_NCF_PROJ_COUNT_STRIDE", "CTR_ROWS1_MAX_ROWS"):
         assert getattr(lib, name) == defines[name], name
     assert ops.TOPK_MAX_K == defines["CTR_TOPK_MAX_K"]
+    # every mirror, not a chosen few: an int under a CTR_ name in _lib is a define of the header, and equal to it
+    mirrors = {name: value for name, value in vars(lib).items()
+               if name.startswith("CTR_") and isinstance(value, int) and not isinstance(value, bool)}
+    assert len(mirrors) >= 34 and {"CTR_TOPK_MAX_K", "CTR_RANK_MAX_ROWS", "CTR_ELIMIT"} <= set(mirrors)
+    for name, value in mirrors.items():
+        assert name in defines, f"_lib.{name} mirrors nothing: include/ctrhip.h has no such #define"
+        assert value == defines[name], f"_lib.{name} = {value}, the header says {defines[name]}"
+
+
+def _header_defines(text):
+    """{name: int} of every object-like ``#define CTR_*`` of the header whose value is an integer: decimal, hex with a
+    ``u`` suffix, ``(1ll << n)`` or a parenthesised negative; a trailing comment may follow"""
+    forms = ((r"(\d+)", int), (r"(0[xX][0-9a-fA-F]+)u", lambda v: int(v, 16)),
+             (r"\(1ll << (\d+)\)", lambda v: 1 << int(v)), (r"\((-\d+)\)", int))
+    defines = {}
+    for name, value in re.findall(r"^#define[ \t]+(CTR_[A-Z0-9_]+)[ \t]+(.+)$", text, flags=re.M):
+        value = re.sub(r"/\*.*|//.*", "", value).strip()
+        for pattern, convert in forms:
+            m = re.fullmatch(pattern, value)
+            if m:
+                defines[name] = convert(m.group(1))
+    return defines
+
+
+def test_header_define_parser_reads_every_form():
+    got = _header_defines("#define CTR_A 12   /* twelve */\n#define CTR_B 0xffffffffu\n#define CTR_C (1ll << 24)\n"
+                          "#define CTR_D (-4)  /* d */\n#define CTR_E  7 // e\n#define CTR_F(x) (2 * (x))\n"
+                          "#define CTR_G 1.5f\n#define OTHER 3\n")
+    assert got == dict(CTR_A=12, CTR_B=0xFFFFFFFF, CTR_C=1 << 24, CTR_D=-4, CTR_E=7)

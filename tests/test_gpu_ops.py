@@ -909,6 +909,38 @@ def test_fused_mlp_matches_layerwise_and_fp64(ops, m, dims, acts_):
         torch.testing.assert_close(gb.cpu(), rb.float(), rtol=1e-4, atol=1e-5 * scale)
 
 
+def test_fused_mlp_switch_on_the_package_chooses_the_arm(ops):
+    """``ops.FUSED_MLP`` is assigned on the package: off, ``mlp_fwd`` goes layer by layer (``linear_fwd[...]`` records,
+    no ``mlp_fused_fwd``); on, it is one ``mlp_fused_fwd`` launch; both give the same output.  The stack is the
+    smallest ``_fusable`` admits -- two 8 x 8 layers -- at 1024 rows: ``_fusable`` takes no batch below 1024, so at 64
+    rows both settings would run layer by layer and the test could not tell them apart."""
+    m, dim = 1024, 8
+    g = torch.Generator().manual_seed(1024)
+    x = torch.randn(m, dim, generator=g).to(DEV)
+    layers = [ops.Layer((torch.randn(dim, dim, generator=g) / dim ** 0.5).to(DEV), torch.randn(dim, generator=g).to(DEV),
+                        act) for act in (ops.ACT_RELU, ops.ACT_NONE)]
+    assert ops.dense._fusable(x, layers) and not ops.dense._fusable(x, layers[:1])
+
+    def run(fused):
+        profiler = ops.KernelProfiler()
+        ops.FUSED_MLP = fused
+        ops.set_profiler(profiler)
+        try:
+            out = ops.mlp_fwd(x, layers)[-1]
+        finally:
+            ops.set_profiler(None)
+        return out, [record[0] for record in profiler.records]
+    try:
+        out_l, labels_l = run(False)
+        out_f, labels_f = run(True)
+    finally:
+        ops.FUSED_MLP = True
+        ops.set_profiler(None)
+    assert "mlp_fused_fwd" not in labels_l and labels_l == [f"linear_fwd[{m}x{dim}x{dim}]"] * 2
+    assert labels_f == ["mlp_fused_fwd"]
+    torch.testing.assert_close(out_f, out_l, rtol=1e-5, atol=1e-5)
+
+
 @pytest.mark.parametrize("n,world", [(100000, 8), (37, 2), (1, 3), (0, 4), (5000, 1)])
 def test_shard_bucket_kernel(n, world):
     from deeplearningrecommendationsystem_amd.dist import HipShardBackend
